@@ -33,6 +33,8 @@ bench_detail.json beside this file (and to gpurun_out/ where that exists):
                         the other BASELINE configs, each measured in a fresh child process (`--object NAME`), reduced
                         to value / ms_per_step / fractions; the full objects are in bench_detail.json
   --full                adds full solves to convergence, the dominant kernel alone and the unfused kernel pair
+  --dump-outputs DIR    writes what the timed window computed (rank 0's shard) to DIR/*.npy: cost, lambda, status,
+                        iterations of every trajectory, x / u of a fixed seeded sample of them (64 MB at most)
 """
 import argparse
 import json
@@ -535,6 +537,8 @@ def single_process(args, ilqg, synth, guard):
     m.sync()
     dt = time.perf_counter() - t0
     active = m.active()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cost": cost, **{k: m.ints(k) for k in ("status", "iterations")}}, m.x, m.u)
     m.close()
     iter_bytes = algorithmic_bytes(4, 2, 0)["iteration"] * n_hor * per
     out = {
@@ -605,6 +609,30 @@ def write_detail(out):
         except OSError:
             pass
     return written
+
+
+DUMP_CAP = 64 * 10 ** 6  # bytes, all files of --dump-outputs together
+DUMP_SEED = 5
+
+
+def dump_outputs(directory, per_trajectory, get_x, get_u):
+    """--dump-outputs DIR: what the timed window computed, as DIR/<name>.npy in float64, so that two builds can be compared
+    output for output on the same inputs.  per_trajectory: {name: [B] array} of every trajectory (cost, lambda, status,
+    iterations); get_x / get_u: the solver's state and control trajectories [B, N+1, n_x] / [B, N, n_u], of which a fixed,
+    seeded sample of trajectories is written (x.npy, u.npy, their indices in sample.npy) so that the whole stays under
+    DUMP_CAP bytes"""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in per_trajectory.items()}
+    x, u = get_x(), get_u()
+    B = x.shape[0]
+    row = (x[0].size + u[0].size + 1) * 8
+    room = DUMP_CAP - sum(a.nbytes for a in arrays.values()) - 4096 * (len(arrays) + 3)  # (npy headers)
+    n = max(0, min(B, room // row))
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False)) if n < B else np.arange(B)
+    arrays.update(x=x[sample], u=u[sample], sample=sample.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(v))
+    assert sum(os.path.getsize(os.path.join(directory, k + ".npy")) for k in arrays) <= DUMP_CAP
 
 
 def _pick(d, *keys):
@@ -719,8 +747,11 @@ def child_object(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed iterations (default 20; 3 for --config5-variant and the config5 objects, 2 for config5_stored / config5_pair)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed iterations before the window (default 2; 1 for config 5)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed window, write what it computed to DIR/<name>.npy (dump_outputs(); at most 64 MB)")
     ap.add_argument("--config5-variant", choices=("factored", "stored", "pair"), default=None,
                     help="only BASELINE config 5 in one of its forms (the object `config5` of the default line), as its own JSON line")
     ap.add_argument("--workload", choices=("car", "synth"), default="car",
@@ -771,9 +802,17 @@ def main():
     ap.add_argument("--groups", type=int, default=0,
                     help="independent sets of trajectories advanced on separate HIP streams (0: library default)")
     args = ap.parse_args()
+    config5_only = args.config5_variant or (args.object or "").startswith("config5")
+    if args.steps is None:
+        args.steps = (2 if (args.object or "config5") != "config5" else 3) if config5_only else 20
+    if args.warmup is None:
+        args.warmup = 1 if config5_only else 2
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.object or args.config5_variant or args.solve or args.solve_one is not None or args.solve_stream is not None
+                              or args.rehearse_protocol):
+        ap.error("--dump-outputs goes with the benchmark window of the solver (the default run or --single-process)")
     if args.object:  # a child of the default run: no torch, no process group
-        if args.steps == 20 and args.object.startswith("config5"):
-            args.steps, args.warmup = (2 if args.object != "config5" else 3), 1
         return child_object(args)
 
     import torch
@@ -787,7 +826,7 @@ def main():
     if args.single_process and world == 1 and args.gpus > 1:
         return single_process(args, ilqg, synth, guard)
     if args.config5_variant:
-        guard.emit(json.dumps(config5(ilqg, synth, local, K=args.steps if args.steps != 20 else 3, W=min(args.warmup, 1), with_cpu=False, variant=args.config5_variant)))
+        guard.emit(json.dumps(config5(ilqg, synth, local, K=args.steps, W=min(args.warmup, 1), with_cpu=False, variant=args.config5_variant)))
         return
     if args.solve_stream is not None:
         local = int(os.environ.get("ILQG_DEVICE_ORDINAL", local))
@@ -881,6 +920,9 @@ def main():
     wave_mapping = s.problem.wave_mapping
     cost = gathered.cpu().numpy() if world > 1 and rank == 0 else s.scalar("cost")
     sweeps = None if rehearsal else float(s.ints("bp_calls").mean())  # backward sweeps (lambda retries) per trajectory, last iteration
+    if args.dump_outputs and rank == 0:  # (rank 0's shard of the job: trajectories 0..B-1)
+        dump_outputs(args.dump_outputs, dict({k: s.scalar(k) for k in ("cost", "lambda")}, **{k: s.ints(k) for k in ("status", "iterations")}),
+                     s.x, s.u)
     s.close()
 
     if rank == 0:

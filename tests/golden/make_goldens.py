@@ -462,8 +462,21 @@ def console_goldens():
             problem, fd, len(text.splitlines()), text.count("Back pass failed"), text.count("REJECTED"), text.splitlines()[-2:]))
 
 
+def vsref_goldens():
+    """tests/test_oracle_vs_ref.py: the reference build's outputs on that module's seeded inputs (solves of three CarParking
+    starts, random box QPs, the dense helpers of libref_pure.so), collected by the module's own functions"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_vs_ref as T
+    out = {}
+    for fd in (0, 1):
+        out.update({"solves_fd%d/%s" % (fd, k): v for k, v in T.solve_outputs(lib_path("ref", full_ddp=fd), fd).items()})
+    out.update({"boxqp/" + k: v for k, v in T.boxqp_outputs(Kernels(lib_path("ref"))).items()})
+    out.update({"dense/" + k: v for k, v in T.dense_outputs(Kernels(lib_path("pure"))).items()})
+    np.savez_compressed(os.path.join(HERE, "oracle_vs_ref.npz"), **out)
+
+
 def main(argv):
-    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 synth synthp console"""
+    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 synth synthp console vsref"""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     groups = {
         "brachi": brachi_goldens,
@@ -476,6 +489,7 @@ def main(argv):
         "synth": lambda: [synth_goldens(fd) for fd in (0, 1)],
         "synthp": lambda: synth_goldens(1, N=12, problem="synth16p", SYN_PARAMS=SYNP_PARAMS_TIGHT),
         "console": console_goldens,
+        "vsref": vsref_goldens,
     }
     for name in (argv or list(groups)):
         groups[name]()
