@@ -29,6 +29,7 @@
 
 #include "ilqg_batch.h"
 #include "ilqg_shim.h"
+#include "ilqg_rules.h"
 
 #define REC_HOST_SIZE_BASE (N_X + sizeofQxx + N_U + sizeofQuu + sizeofQxu + N_X * N_X + N_X * N_U + 2 * N_U)
 #if FULL_DDP
@@ -1171,7 +1172,7 @@ int line_search(tOptSet *o, int iter) {
          * from the stored x,u: its cost-only mode touches nothing else (iLQG_func.tem:160-176) */
         forward_pass(cand, o, 0.0, &tmp, 1);
     }
-    z = (expected > 0) ? dcost / expected : 0;
+    z = reduction_ratio(dcost, expected);
     if(DEBUG_FORWARDPASS) {
         /* what the reference says while it walks the step sizes one by one (line_search.c:44-66): the device has
          * tried them all at once and kept every cost and finite-flag, so the same walk is replayed here */
@@ -1179,7 +1180,7 @@ int line_search(tOptSet *o, int iter) {
         for(i = 0; i < tried && i < o->n_alpha; i++) {
             if(!ok[i])
                 SAY_SEARCH(2, ("line search: %-3d: prediction or objective failed with inf or nan\n", i + 1));
-            else if(!(-o->alpha[i] * (o->dV[0] + o->alpha[i] * o->dV[1]) > 0))
+            else if(!(expected_reduction(o->alpha[i], o->dV[0], o->dV[1]) > 0))
                 SAY_SEARCH(-1000, ("non-positive expected reduction: should not occur (dV[0]= %g, dV[1]= %g)\n", o->dV[0], o->dV[1]));
         }
         if(!accepted) SAY_SEARCH(2, ("max number of line searches reached\n"));
@@ -1268,16 +1269,6 @@ void cholesky_tri_inv(const double *L_, double *invA, const int n, double *x) {
     dense_call("cholesky_tri_inv()", 4, n, L_, TRI(n), NULL, 0, NULL, 0, invA, TRI(n), &flag);
 }
 
-static void lambda_increase(tOptSet *o, double *dlambda) {
-    *dlambda = max(*dlambda * o->lambdaFactor, o->lambdaFactor);
-    o->lambda = max(o->lambda * *dlambda, o->lambdaMin);
-}
-
-static void lambda_decrease(tOptSet *o, double *dlambda) {
-    *dlambda = min(*dlambda / o->lambdaFactor, 1.0 / o->lambdaFactor);
-    o->lambda = o->lambda * *dlambda * (o->lambda > o->lambdaMin);
-}
-
 /* Outer iteration for ONE trajectory, where the reference has it: on the host
  * (iLQG.c:224-379), with the two hot stages on the GPU.  `done` starts at 0, so
  * a calc_derivs failure in the first iteration returns 0 instead of reading an
@@ -1304,12 +1295,12 @@ int iLQG(tOptSet *o) {
                 done = 1;
             } else {
                 SAY_LOOP(1, ("Back pass failed.\n"));
-                lambda_increase(o, &dlambda);
+                lambda_up(o->lambdaFactor, o->lambdaMin, &o->lambda, &dlambda);
                 if(o->lambda > o->lambdaMax) break;
             }
         }
-        if(o->g_norm < o->tolGrad && o->lambda < 1e-5) {
-            lambda_decrease(o, &dlambda);
+        if(grad_converged(o->g_norm, o->tolGrad, o->lambda)) {
+            lambda_down(o->lambdaFactor, o->lambdaMin, &o->lambda, &dlambda);
             SAY_LOOP(1, ("\nSUCCESS: gradient norm < tolGrad\n"));
             break;
         }
@@ -1320,7 +1311,7 @@ int iLQG(tOptSet *o) {
             SAY_LOOP(1, ("iter: %-3d  cost: %-9.6g  reduction: %-9.3g  gradient: %-9.3g  z: %-5.3g log10(lam): %3.1f "
                          "w_pen_l: %-9.3g w_pen_f: %-9.3g\n", iter + 1, o->cost, o->dcost, o->g_norm,
                          o->dcost / o->expected, log10(o->lambda), o->w_pen_l, o->w_pen_f));
-            lambda_decrease(o, &dlambda);
+            lambda_down(o->lambdaFactor, o->lambdaMin, &o->lambda, &dlambda);
             makeCandidateNominal(o, 0);
             o->cost = o->new_cost;
             fresh = 1;
@@ -1331,7 +1322,7 @@ int iLQG(tOptSet *o) {
             update_multipliers(o, 0);
             forward_pass(o->nominal, o, 0.0, &o->cost, 1);
         } else {
-            lambda_increase(o, &dlambda);
+            lambda_up(o->lambdaFactor, o->lambdaMin, &o->lambda, &dlambda);
             if(o->w_pen_fact2 > 1.0) {
                 o->w_pen_l = min(o->w_pen_max_l, o->w_pen_l * o->w_pen_fact2);
                 o->w_pen_f = min(o->w_pen_max_f, o->w_pen_f * o->w_pen_fact2);

@@ -601,6 +601,7 @@ typedef traj_t eltraj_t;
 #include "ilqg_quad.hpp"  // 16-lane rows; only the wave mapping uses them
 #endif
 #include "ilqg_shim.h"
+#include "ilqg_rules.h"
 
 namespace {
 
@@ -692,13 +693,65 @@ struct DevPtrs {
     unsigned *spec_done; //   [B] 1 once the trajectory's result has been written
     unsigned *spec_out;  //   [B][SPEC_ATTEMPTS] how attempt j ended: 0 unknown, else kind | direct << 2 | row << 3
     int *spec_row_b;     //   [rows] the trajectory a row works on (-1: none)
-    double *spec_res;    //   [rows][8] what a row's attempt with a result leaves: lambda, dlambda, dV0, dV1, g_norm, status, bp_rc, sweeps
+    double *spec_res;    //   [rows][SPEC_SLOTS] what a row's attempt with a result leaves: its BackResult, see spec_put
     double *spec_gains;  //   [rows][N][NU + NXU] gains of a row's attempt that does not write the trajectory's records
     int spec_rows;
     double *nom;         // packed trajectory records, see nomp()
     double **p;
     int B, Bp, N;
 };
+
+// What the device backward pass leaves per trajectory (iLQG.c:245-303).  rc is the last sweep's: 0 ok, 1 failed, 2 its
+// derivatives failed.  Every backward kernel writes it with store_result, and clears ILQG_I_NEED_DERIVS itself: the lane-mapped
+// kernels on entry, the wave-mapped ones right before the store.
+struct BackResult {
+    int status;
+    double lambda, dlambda, dV0, dV1, g_norm;
+    int calls, rc;
+};
+__device__ __forceinline__ void store_result(const DevPtrs &P, int b, const BackResult &r) {
+    // (every backward kernel starts from an active trajectory; the lane mapping's kernels leave the status unwritten while
+    // it stays active, as they always did: an unconditional store costs k_backward<1> two registers)
+    if(WAVE_MAP || r.status != ILQG_ST_ACTIVE) P.i[ILQG_I_STATUS][b] = r.status;
+    P.f[ILQG_F_LAMBDA][b] = r.lambda;
+    P.f[ILQG_F_DLAMBDA][b] = r.dlambda;
+    P.f[ILQG_F_DV0][b] = r.dV0;
+    P.f[ILQG_F_DV1][b] = r.dV1;
+    P.f[ILQG_F_GNORM][b] = r.g_norm;
+    P.i[ILQG_I_BP_CALLS][b] = r.calls;
+    P.i[ILQG_I_BP_RC][b] = r.rc;
+}
+
+// The status after the retry loop (iLQG.c:267-303): the derivatives failed, no descent within the lambda schedule, the
+// gradient exit (which lowers lambda), or on to the line search.  single_sweep: the caller's loop decides, nothing ends here.
+__device__ __forceinline__ int back_status(int rc, double g_norm, double &lambda, double &dlambda, int single_sweep,
+                                           const ilqg_dev_opts_t &O) {
+    if(single_sweep) return ILQG_ST_ACTIVE;
+    if(rc == 2) return ILQG_ST_DERIVS_FAILED;
+    if(rc) return ILQG_ST_NO_DESCENT;
+    if(grad_converged(g_norm, O.tolGrad, lambda)) {
+        lambda_down(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
+        return ILQG_ST_CONVERGED_GRAD;
+    }
+    return ILQG_ST_ACTIVE;
+}
+
+// A BackResult as the speculative retries keep it per row in spec_res (doubles: every field is exact in one)
+enum { SPEC_LAMBDA, SPEC_DLAMBDA, SPEC_DV0, SPEC_DV1, SPEC_GNORM, SPEC_STATUS, SPEC_RC, SPEC_CALLS, SPEC_SLOTS };
+__device__ __forceinline__ void spec_put(double *res, const BackResult &r) {
+    res[SPEC_LAMBDA] = r.lambda;
+    res[SPEC_DLAMBDA] = r.dlambda;
+    res[SPEC_DV0] = r.dV0;
+    res[SPEC_DV1] = r.dV1;
+    res[SPEC_GNORM] = r.g_norm;
+    res[SPEC_STATUS] = (double)r.status;
+    res[SPEC_RC] = (double)r.rc;
+    res[SPEC_CALLS] = (double)r.calls;
+}
+__device__ __forceinline__ BackResult spec_get(const double *res) {
+    return {(int)res[SPEC_STATUS], res[SPEC_LAMBDA], res[SPEC_DLAMBDA], res[SPEC_DV0], res[SPEC_DV1], res[SPEC_GNORM],
+            (int)res[SPEC_CALLS], (int)res[SPEC_RC]};
+}
 
 // Nothing may be in flight when a prefetching loop is entered: the compiler's wait-count pass
 // merges the state of the loop entry with that of the back edge, and a load still pending from

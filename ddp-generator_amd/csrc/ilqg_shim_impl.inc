@@ -1011,16 +1011,14 @@ int ilqg_dev_rollout_init(ilqg_dev_t *d) {
 // wave mapping: derivative records are evaluated chunk by chunk into the work buffer and consumed by
 // the backward kernel of the same chunk.  do_derivs = 0 uses the records already in the buffer.
 // the most backward sweeps one call of the retry loop can make under these options (iLQG.c:261-283): sweep 0 at the lambda the
-// trajectory has, sweep j at the lambda j increases later, while lambda <= lambdaMax.  The longest schedule starts from
-// lambda = 0 with the smallest dlambda (every increase then multiplies by lambdaFactor only once more than the one before).
+// trajectory has, sweep j at the lambda j increases later (lambda_up, the step k_backward_quad's attempts take), while
+// lambda <= lambdaMax.  The longest schedule starts from lambda = 0 with the smallest dlambda (every increase then
+// multiplies by lambdaFactor only once more than the one before).
 static int spec_sweeps_at_most(const ilqg_dev_opts_t &O) {
     double lam = 0.0, dlam = 0.0;
     int sweeps = 1;
     while(sweeps <= 4096) {
-        const double t1 = dlam * O.lambdaFactor;
-        dlam = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-        const double t2 = lam * dlam;
-        lam = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
+        lambda_up(O.lambdaFactor, O.lambdaMin, &lam, &dlam);
         if(lam > O.lambdaMax || !(lam == lam)) break;
         sweeps++;
     }
@@ -1149,7 +1147,7 @@ static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_
                 const int per_wg = 4 * QUAD_WAVES;
                 const int wgs = (cnt + per_wg - 1) / per_wg, rows = (wgs < d->cus ? wgs : d->cus) * per_wg;
                 const int ri = try_buffer(d, &d->spec_ints, &d->spec_ints_bytes, ((size_t)(3 + SPEC_ATTEMPTS) * d->B + rows) * sizeof(unsigned), st);
-                const int rd = ri ? ri : try_buffer(d, &d->spec_doubles, &d->spec_doubles_bytes, (size_t)rows * (8 + (size_t)d->N * SPEC_GW) * sizeof(double), st);
+                const int rd = ri ? ri : try_buffer(d, &d->spec_doubles, &d->spec_doubles_bytes, (size_t)rows * (SPEC_SLOTS + (size_t)d->N * SPEC_GW) * sizeof(double), st);
                 if(ri == 1 || rd == 1) return 1;
                 if(ri == 2 || rd == 2) spec = false;
             }
@@ -1172,7 +1170,7 @@ static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_
                            P.spec_best = w + (2 + SPEC_ATTEMPTS) * nb;
                            P.spec_row_b = reinterpret_cast<int *>(w + (3 + SPEC_ATTEMPTS) * nb);
                            P.spec_res = d->spec_doubles;
-                           P.spec_gains = d->spec_doubles + (size_t)rows * 8;
+                           P.spec_gains = d->spec_doubles + (size_t)rows * SPEC_SLOTS;
                            P.spec_rows = rows;
                            g_spec_last = d;
                            (void)hipMemsetAsync(w, 0, (2 + SPEC_ATTEMPTS) * nb * sizeof(unsigned), q);

@@ -26,9 +26,8 @@ __global__ void k_select(DevPtrs P, ilqg_dev_opts_t O, int a0, int a1, int from_
         cnew = P.f[ILQG_F_ALPHA_COST][tile_ix(ILQG_MAX_ALPHA, i, b)];
         if(!ok) continue;
         dcost = cost - cnew;
-        expected = -a * (dV0 + a * dV1);
-        const double z = (expected > 0) ? dcost / expected : 0.0;
-        if(z > O.zMin) break;
+        expected = expected_reduction(a, dV0, dV1);
+        if(reduction_ratio(dcost, expected) > O.zMin) break;
         ok = 0;
     }
     // To the second stage: one atomicAdd per wavefront, its trajectories in order behind each other (the entries of
@@ -131,9 +130,7 @@ __global__ void k_update(DevPtrs P, ilqg_dev_opts_t O, int commit_s1, int commit
     int status = ILQG_ST_ACTIVE;
     int resweep = 0;
     if(P.i[ILQG_I_ACCEPTED][b]) {
-        const double t1 = dlambda / O.lambdaFactor, t2 = 1.0 / O.lambdaFactor;
-        dlambda = (t1 < t2) ? t1 : t2;
-        lambda = lambda * dlambda * (lambda > O.lambdaMin);
+        lambda_down(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
         P.f[ILQG_F_COST][b] = P.f[ILQG_F_NEW_COST][b];
         P.i[ILQG_I_NEED_DERIVS][b] = 1;
         if(P.f[ILQG_F_DCOST][b] < O.tolFun) status = ILQG_ST_CONVERGED_FUN;
@@ -145,10 +142,7 @@ __global__ void k_update(DevPtrs P, ilqg_dev_opts_t O, int commit_s1, int commit
             P.f[ILQG_F_WPEN_F][b] = (O.w_pen_max_f < wf) ? O.w_pen_max_f : wf;
             resweep = 1;
         }
-        const double t1 = dlambda * O.lambdaFactor;
-        dlambda = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-        const double t2 = lambda * dlambda;
-        lambda = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
+        lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
         if(lambda > O.lambdaMax) status = ILQG_ST_LAMBDA_MAX;
     }
     if(status == ILQG_ST_ACTIVE) {

@@ -405,32 +405,11 @@ __global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P,
             rc = backward_sweep(P, b, lambda, O.regType, dV0, dV1, g_norm);
         calls++;
         if(single_sweep || rc != 1) break;
-        // raise the regularisation and retry (iLQG.c:271-274)
-        const double t1 = dlambda * O.lambdaFactor;
-        dlambda = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-        const double t2 = lambda * dlambda;
-        lambda = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
+        lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);  // raise the regularisation and retry
         if(lambda > O.lambdaMax) break;
     }
-    if(!single_sweep) {
-        if(rc == 2) {
-            P.i[ILQG_I_STATUS][b] = ILQG_ST_DERIVS_FAILED;
-        } else if(rc) {
-            P.i[ILQG_I_STATUS][b] = ILQG_ST_NO_DESCENT;
-        } else if(g_norm < O.tolGrad && lambda < 1e-5) {  // iLQG.c:297-303
-            const double t1 = dlambda / O.lambdaFactor, t2 = 1.0 / O.lambdaFactor;
-            dlambda = (t1 < t2) ? t1 : t2;
-            lambda = lambda * dlambda * (lambda > O.lambdaMin);
-            P.i[ILQG_I_STATUS][b] = ILQG_ST_CONVERGED_GRAD;
-        }
-    }
-    P.f[ILQG_F_LAMBDA][b] = lambda;
-    P.f[ILQG_F_DLAMBDA][b] = dlambda;
-    P.f[ILQG_F_DV0][b] = dV0;
-    P.f[ILQG_F_DV1][b] = dV1;
-    P.f[ILQG_F_GNORM][b] = g_norm;
-    P.i[ILQG_I_BP_CALLS][b] = calls;
-    P.i[ILQG_I_BP_RC][b] = rc;
+    const int status = back_status(rc, g_norm, lambda, dlambda, single_sweep, O);
+    store_result(P, b, {status, lambda, dlambda, dV0, dV1, g_norm, calls, rc});
 }
 
 // ---------------------------------------------------------------------------
@@ -635,13 +614,10 @@ __global__ __launch_bounds__(2 * WAVE) void k_backward_split(DevPtrs P, ilqg_dev
             rc = result;
             if(!result) g_norm = gsum / ((double)(N - 1));
             calls++;
-            // raise the regularisation and retry (iLQG.c:271-274)
+            // raise the regularisation and retry
             sweeping = false;
             if(rc == 1) {
-                const double t1 = dlambda * O.lambdaFactor;
-                dlambda = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-                const double t2 = lambda * dlambda;
-                lambda = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
+                lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
                 sweeping = !(lambda > O.lambdaMax);
             }
         }
@@ -652,23 +628,8 @@ __global__ __launch_bounds__(2 * WAVE) void k_backward_split(DevPtrs P, ilqg_dev
     }
     if(dead) P.i[ILQG_I_STATUS][b] = ILQG_ST_DERIVS_FAILED;
     if(took_part) {
-        if(rc == 2) {
-            P.i[ILQG_I_STATUS][b] = ILQG_ST_DERIVS_FAILED;
-        } else if(rc) {
-            P.i[ILQG_I_STATUS][b] = ILQG_ST_NO_DESCENT;
-        } else if(g_norm < O.tolGrad && lambda < 1e-5) {  // iLQG.c:297-303
-            const double t1 = dlambda / O.lambdaFactor, t2 = 1.0 / O.lambdaFactor;
-            dlambda = (t1 < t2) ? t1 : t2;
-            lambda = lambda * dlambda * (lambda > O.lambdaMin);
-            P.i[ILQG_I_STATUS][b] = ILQG_ST_CONVERGED_GRAD;
-        }
-        P.f[ILQG_F_LAMBDA][b] = lambda;
-        P.f[ILQG_F_DLAMBDA][b] = dlambda;
-        P.f[ILQG_F_DV0][b] = dV0;
-        P.f[ILQG_F_DV1][b] = dV1;
-        P.f[ILQG_F_GNORM][b] = g_norm;
-        P.i[ILQG_I_BP_CALLS][b] = calls;
-        P.i[ILQG_I_BP_RC][b] = rc;
+        const int status = back_status(rc, g_norm, lambda, dlambda, 0, O);
+        store_result(P, b, {status, lambda, dlambda, dV0, dV1, g_norm, calls, rc});
     }
 }
 #else

@@ -242,8 +242,8 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
     // other lanes' values come by wavefront shuffles.  Every lane computes the test of its own step size.
     const double cost = P.f[ILQG_F_COST][b], dV0 = P.f[ILQG_F_DV0][b], dV1 = P.f[ILQG_F_DV1][b];
     const double my_dcost = cost - csum;
-    const double my_expected = -alpha * (dV0 + alpha * dV1);
-    const double my_z = (my_expected > 0) ? my_dcost / my_expected : 0.0;
+    const double my_expected = expected_reduction(alpha, dV0, dV1);
+    const double my_z = reduction_ratio(my_dcost, my_expected);
     const int my_pass = (ok && my_z > O.zMin) ? 1 : 0;
     double cnew = (a0 > 0) ? P.f[ILQG_F_NEW_COST][b] : 0.0;
     double dcost = P.f[ILQG_F_DCOST][b], expected = P.f[ILQG_F_EXPECTED][b];

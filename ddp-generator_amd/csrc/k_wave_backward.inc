@@ -635,38 +635,19 @@ __device__ __forceinline__ void backward_of_trajectory(StepLds &S, const double 
     }
     double lambda = P.f[ILQG_F_LAMBDA][b], dlambda = P.f[ILQG_F_DLAMBDA][b];
     double dV0 = 0.0, dV1 = 0.0, g_norm = P.f[ILQG_F_GNORM][b];
-    int calls = 0, rc, status = ILQG_ST_ACTIVE;
+    int calls = 0, rc;
     for(;;) {
         rc = backward_sweep_wave<FACT>(S, tables, P, b, bw, lambda, O.regType, dV0, dV1, g_norm);
         calls++;
         if(single_sweep || rc != 1) break;
-        const double t1 = dlambda * O.lambdaFactor;
-        dlambda = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-        const double t2 = lambda * dlambda;
-        lambda = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
+        lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
         if(lambda > O.lambdaMax) break;
         wave_sync();
     }
-    if(!single_sweep) {
-        if(rc) {
-            status = ILQG_ST_NO_DESCENT;
-        } else if(g_norm < O.tolGrad && lambda < 1e-5) {
-            const double t1 = dlambda / O.lambdaFactor, t2 = 1.0 / O.lambdaFactor;
-            dlambda = (t1 < t2) ? t1 : t2;
-            lambda = lambda * dlambda * (lambda > O.lambdaMin);
-            status = ILQG_ST_CONVERGED_GRAD;
-        }
-    }
+    const int status = back_status(rc, g_norm, lambda, dlambda, single_sweep, O);
     if(lane == 0) {
         P.i[ILQG_I_NEED_DERIVS][b] = 0;
-        P.i[ILQG_I_STATUS][b] = status;
-        P.f[ILQG_F_LAMBDA][b] = lambda;
-        P.f[ILQG_F_DLAMBDA][b] = dlambda;
-        P.f[ILQG_F_DV0][b] = dV0;
-        P.f[ILQG_F_DV1][b] = dV1;
-        P.f[ILQG_F_GNORM][b] = g_norm;
-        P.i[ILQG_I_BP_CALLS][b] = calls;
-        P.i[ILQG_I_BP_RC][b] = rc;
+        store_result(P, b, {status, lambda, dlambda, dV0, dV1, g_norm, calls, rc});
     }
 }
 
@@ -803,12 +784,6 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
         const int rowid = ((int)blockIdx.x * QUAD_WAVES + wave) * 4 + g;
         double *const my_gains = SPEC ? P.spec_gains + (size_t)rowid * N * SPEC_GW : nullptr;
         const int lead = lane & 48;  // the row's first lane: the one that talks to memory for the row
-        auto next_lambda = [&](double &lam, double &dlam) {  // iLQG.c:271-274
-            const double t1 = dlam * O.lambdaFactor;
-            dlam = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-            const double t2 = lam * dlam;
-            lam = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
-        };
         auto ld = [&](const unsigned *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
         // the row leaves its trajectory (busy -> false): one runner less
         auto leave = [&](bool mine) {
@@ -849,11 +824,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                     // (the result of a sweep that FAILED at the end of the lambda schedule — exit "no descent" — has gains for the
                     // steps above its failure only, and nothing reads the gains of a trajectory that has left the iteration: the
                     // records keep what the trajectory's own direct sweeps wrote, the row's buffer is not copied)
-#ifdef ILQG_COUNT_STEPS  // (measurement builds keep the steps walked where bp_rc is)
-                    const bool no_descent = false;
-#else
-                    const bool no_descent = rg && P.spec_res[(size_t)((unsigned)rwo >> 3) * 8 + 6] != 0.0;
-#endif
+                    const bool no_descent = rg && P.spec_res[(size_t)((unsigned)rwo >> 3) * SPEC_SLOTS + SPEC_STATUS] == ILQG_ST_NO_DESCENT;
                     if(rg && !(((unsigned)rwo >> 2) & 1u) && !no_descent) {
                         const double2 *src = reinterpret_cast<const double2 *>(P.spec_gains + (size_t)((unsigned)rwo >> 3) * N * SPEC_GW);
                         constexpr int PAIRS = SPEC_GW / 2;
@@ -881,16 +852,8 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                     }
                 }
                 if(got && c == 0) {
-                    const double *res = P.spec_res + (size_t)(wo >> 3) * 8;
                     P.i[ILQG_I_NEED_DERIVS][b] = 0;
-                    P.i[ILQG_I_STATUS][b] = (int)res[5];
-                    P.f[ILQG_F_LAMBDA][b] = res[0];
-                    P.f[ILQG_F_DLAMBDA][b] = res[1];
-                    P.f[ILQG_F_DV0][b] = res[2];
-                    P.f[ILQG_F_DV1][b] = res[3];
-                    P.f[ILQG_F_GNORM][b] = res[4];
-                    P.i[ILQG_I_BP_CALLS][b] = (int)res[7];
-                    P.i[ILQG_I_BP_RC][b] = (int)res[6];
+                    store_result(P, b, spec_get(P.spec_res + (size_t)(wo >> 3) * SPEC_SLOTS));
                 }
                 __threadfence();
             }
@@ -986,7 +949,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                                 g_norm = P.f[ILQG_F_GNORM][b];
                                 bool gone = false;
                                 for(int i = 0; i < attempt; i++) {
-                                    next_lambda(lambda, dlambda);
+                                    lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
                                     gone = gone || lambda > O.lambdaMax;
                                 }
                                 gone = gone || ld(&P.spec_done[b]) != 0u;
@@ -1066,42 +1029,28 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                 if(any_lane(failed || finished)) {
                     const bool ended = failed || finished;
                     bool result = false, retire = false;
-                    int status = ILQG_ST_ACTIVE, bp_rc = 0;
+                    int bp_rc = 0;
                     if(failed) {  // back_pass.c:168-171; the next lambda decides whether there is another attempt (iLQG.c:267-275)
                         double l2 = lambda, d2 = dlambda;
-                        next_lambda(l2, d2);
+                        lambda_up(O.lambdaFactor, O.lambdaMin, &l2, &d2);
                         if(l2 > O.lambdaMax) {
                             lambda = l2;
                             dlambda = d2;
                             result = true;
-                            status = ILQG_ST_NO_DESCENT;
                             bp_rc = 1;
                         }
                     }
                     if(finished) {
                         g_norm = gsum / ((double)(N - 1));  // N summands over N-1 (back_pass.c:254)
                         result = true;
-                        if(g_norm < O.tolGrad && lambda < 1e-5) {  // iLQG.c:297-303
-                            const double t1 = dlambda / O.lambdaFactor, t2 = 1.0 / O.lambdaFactor;
-                            dlambda = (t1 < t2) ? t1 : t2;
-                            lambda = lambda * dlambda * (lambda > O.lambdaMin);
-                            status = ILQG_ST_CONVERGED_GRAD;
-                        }
                     }
-                    if(ended && result && c == 0) {
-                        double *res = P.spec_res + (size_t)rowid * 8;
-                        res[0] = lambda;
-                        res[1] = dlambda;
-                        res[2] = dV0;
-                        res[3] = dV1;
-                        res[4] = g_norm;
-                        res[5] = (double)status;
-                        res[6] = (double)bp_rc;
+                    // (never single_sweep here: the shim speculates only where the retry loop runs on the device)
+                    const int status = result ? back_status(bp_rc, g_norm, lambda, dlambda, 0, O) : ILQG_ST_ACTIVE;
 #ifdef ILQG_COUNT_STEPS
-                        res[6] = (double)walked;
+                    bp_rc = walked;
 #endif
-                        res[7] = (double)(attempt + 1);
-                    }
+                    if(ended && result && c == 0)
+                        spec_put(P.spec_res + (size_t)rowid * SPEC_SLOTS, {status, lambda, dlambda, dV0, dV1, g_norm, attempt + 1, bp_rc});
                     __threadfence();  // the attempt's gains and scalars are out before it is said to have ended
                     if(ended && c == 0) {
                         if(result) atomicMin(&P.spec_best[b], (unsigned)attempt);
@@ -1126,7 +1075,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                             const int na = (int)(old & 0xffffu);
                             bool gone = na >= SPEC_ATTEMPTS;
                             for(int i = attempt; i < na; i++) {
-                                next_lambda(lambda, dlambda);
+                                lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
                                 gone = gone || lambda > O.lambdaMax;
                             }
                             if(gone) {
@@ -1160,10 +1109,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                     bp_rc = 1;
                     done = true;
                     if(!single_sweep) {
-                        const double t1 = dlambda * O.lambdaFactor;
-                        dlambda = (t1 > O.lambdaFactor) ? t1 : O.lambdaFactor;
-                        const double t2 = lambda * dlambda;
-                        lambda = (t2 > O.lambdaMin) ? t2 : O.lambdaMin;
+                        lambda_up(O.lambdaFactor, O.lambdaMin, &lambda, &dlambda);
                         if(!(lambda > O.lambdaMax)) {
                             done = false;
                             start = true;
@@ -1177,31 +1123,13 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                     k--;
                 }
                 if(done) {
-                    int status = ILQG_ST_ACTIVE;
-                    if(!single_sweep) {
-                        if(bp_rc) {
-                            status = ILQG_ST_NO_DESCENT;
-                        } else if(g_norm < O.tolGrad && lambda < 1e-5) {  // iLQG.c:297-303
-                            const double t1 = dlambda / O.lambdaFactor, t2 = 1.0 / O.lambdaFactor;
-                            dlambda = (t1 < t2) ? t1 : t2;
-                            lambda = lambda * dlambda * (lambda > O.lambdaMin);
-                            status = ILQG_ST_CONVERGED_GRAD;
-                        }
-                    }
+                    const int status = back_status(bp_rc, g_norm, lambda, dlambda, single_sweep, O);
+#ifdef ILQG_COUNT_STEPS
+                    bp_rc = walked;
+#endif
                     if(c == 0) {
                         P.i[ILQG_I_NEED_DERIVS][b] = 0;
-                        P.i[ILQG_I_STATUS][b] = status;
-                        P.f[ILQG_F_LAMBDA][b] = lambda;
-                        P.f[ILQG_F_DLAMBDA][b] = dlambda;
-                        P.f[ILQG_F_DV0][b] = dV0;
-                        P.f[ILQG_F_DV1][b] = dV1;
-                        P.f[ILQG_F_GNORM][b] = g_norm;
-                        P.i[ILQG_I_BP_CALLS][b] = calls;
-#ifdef ILQG_COUNT_STEPS
-                        P.i[ILQG_I_BP_RC][b] = walked;
-#else
-                        P.i[ILQG_I_BP_RC][b] = bp_rc;
-#endif
+                        store_result(P, b, {status, lambda, dlambda, dV0, dV1, g_norm, calls, bp_rc});
                     }
                     busy = false;
                 }
