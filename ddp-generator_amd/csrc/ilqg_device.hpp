@@ -15,6 +15,7 @@
 //   back_step                                     back_pass.c:80-251 (one time step)
 #pragma once
 #include <hip/hip_runtime.h>
+#include "ilqg_rules.h"
 
 namespace ilqg {
 
@@ -427,34 +428,8 @@ ILQG_DEV double qp_value(const double *H, const double *g, const double *x) {
     return v;
 }
 
-// The acceptance test of the backtracking line search, boxQP.c:219:
-//     (vc - oldvalue) / (step * sdotg) >= armijo          (step > 0, sdotg < 0)
-// decided without the division wherever the outcome is beyond doubt: with n = vc - oldvalue, d = step*sdotg < 0
-// the quotient is >= armijo iff n <= armijo*d.  Both sides carry a few rounding errors of relative size 2^-53
-// each, so the comparison is trusted only outside a band of relative width 1e-15 (nine times that) around
-// armijo*d; inside the band — and for NaN, where every comparison fails — the reference's own expression is
-// evaluated.  The result is therefore always the reference's.
-ILQG_DEV bool armijo_passes(double vc, double oldvalue, double step, double sdotg, double armijo) {
-    const double n = vc - oldvalue, d = step * sdotg;
-    const double t = armijo * d, m = fabs(t) * 1e-15;
-    if(n < t - m) return true;
-    if(n > t + m) return false;
-    return (n / d) >= armijo;
-}
-
-// The same test in two parts, for callers that evaluate several trials before branching: the quick verdict
-// (+1 passes, -1 fails, 0 too close to call) without any control flow, and the reference's expression for the rest.
-#ifndef ARMIJO_TRIALS
-#define ARMIJO_TRIALS 2
-#endif
-#ifndef ARMIJO_TRIALS_LATE
-#define ARMIJO_TRIALS_LATE 4
-#endif
-ILQG_DEV int armijo_quick(double vc, double oldvalue, double step, double sdotg, double armijo) {
-    const double n = vc - oldvalue, d = step * sdotg;
-    const double t = armijo * d, m = fabs(t) * 1e-15;
-    return (n < t - m) ? 1 : ((n > t + m) ? -1 : 0);
-}
+// Armijo trials per trip of box_qp's line search: in the first trip, and in every later one
+constexpr int ARMIJO_TRIP_FIRST = 2, ARMIJO_TRIP_LATE = 4;
 // number of the last Armijo trial the reference can reach: trial k uses step_k = step_{k-1} * stepDec (step_0 = 1), and
 // after a failed trial k the loop returns 2 if step_{k+1} < minStep (boxQP.c:221-224).  The same IEEE products as at
 // run time, evaluated by the compiler.
@@ -466,11 +441,8 @@ constexpr int armijo_last_trial(double step_dec, double min_step) {
     }
     return 4096;
 }
-constexpr int ARMIJO_LAST = armijo_last_trial(0.6, 1e-22);
+constexpr int ARMIJO_LAST = armijo_last_trial(BOXQP_STEP_DEC, BOXQP_MIN_STEP);
 static_assert(ARMIJO_LAST > 8 && ARMIJO_LAST < 200, "0.6^k falls below 1e-22 near k = 99");
-ILQG_DEV bool armijo_exact(double vc, double oldvalue, double step, double sdotg, double armijo) {
-    return ((vc - oldvalue) / (step * sdotg)) >= armijo;
-}
 
 // Projected-Newton box QP.  Same iteration, constants and return codes as
 // boxQP.c:39-238.  One representational difference: the reference compacts
@@ -492,16 +464,13 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
     // anyway, so the work a finished lane still steps through costs no time.  Results, codes and the state
     // left in x / clamp / invH at each exit are the reference's.
     constexpr int T = tri(M);
-    const int max_iter = 100;
-    const double min_grad = 1e-8, min_rel_improve = 1e-8, step_dec = 0.6, min_step = 1e-22, armijo = 0.1;
     double grad[M], search[M];
     double value, oldvalue = 0.0;
     int rc = 0;  // 0: iterating
 
 #pragma unroll
     for(int i = 0; i < M; i++) {
-        if(x[i] > upper[i]) x[i] = upper[i];
-        if(x[i] < lower[i]) x[i] = lower[i];
+        BOXQP_CLIP(x[i], lower[i], upper[i]);
         clamp[i] = 0;
     }
 #pragma unroll
@@ -515,8 +484,8 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
     bool pd_of[NPAT];
     if constexpr(TABLE) chol_pattern_table<M>(H, inv_of, pd_of);
 
-    for(int iter = 0; iter < max_iter; iter++) {
-        if(iter > 0 && (oldvalue - value) < min_rel_improve * fabs(oldvalue)) rc = 4;  // boxQP.c:85-86
+    for(int iter = 0; iter < BOXQP_MAX_ITER; iter++) {
+        if(iter > 0 && BOXQP_STALL(oldvalue, value)) rc = BOXQP_STALLED;
         const bool live0 = (rc == 0);
         oldvalue = live0 ? value : oldvalue;
 
@@ -532,9 +501,9 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
             grad[i] = g[i] + hx;
             const int was = clamp[i];
             int now;
-            if(x[i] <= lower[i] && grad[i] > 0)
+            if(BOXQP_AT_LOWER(x[i], lower[i], grad[i]))
                 now = 1;
-            else if(x[i] >= upper[i] && grad[i] < 0)
+            else if(BOXQP_AT_UPPER(x[i], upper[i], grad[i]))
                 now = 2;
             else {
                 now = 0;
@@ -546,7 +515,7 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
             clamp[i] = live0 ? now : was;
         }
         n_free_out = live0 ? n_free : n_free_out;
-        if(live0 && all_clamped) rc = 6;  // boxQP.c:124-126
+        if(live0 && all_clamped) rc = BOXQP_ALL_CLAMPED;
 
         // factor + explicit inverse of the free block when the free set changed (boxQP.c:129-146)
         if(pf) pf->probe(2);
@@ -570,7 +539,7 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
                 pd = is ? pd_of[p] : pd;
             }
             const bool fresh = (rc == 0) & ((iter == 0) | changed);
-            if(fresh & !pd) rc = -1;
+            if(fresh & !pd) rc = BOXQP_NOT_PD;
 #pragma unroll
             for(int i = 0; i < T; i++) invH[i] = (fresh & pd) ? inv[i] : invH[i];
         } else if(rc == 0 && (iter == 0 || changed)) {
@@ -581,13 +550,13 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
                 for(int i = 0; i <= j; i++)
                     Hm[ut(i, j)] = (clamp[i] || clamp[j]) ? ((i == j) ? 1.0 : 0.0) : H[ut(i, j)];
             const bool pd = chol_factor_inverse<M>(Hm, inv);
-            if(!pd) rc = -1;
+            if(!pd) rc = BOXQP_NOT_PD;
 #pragma unroll
             for(int i = 0; i < T; i++) invH[i] = pd ? inv[i] : invH[i];
         }
         if(pf) pf->probe(3);
 
-        if(rc == 0 && gnorm < min_grad * min_grad) rc = 5;  // boxQP.c:149-150
+        if(rc == 0 && BOXQP_GRAD_SMALL(gnorm)) rc = BOXQP_SMALL_GRAD;
 
         // search(free) = -invH(free,free) * (g + H x_clamped)(free) - x(free); search(clamped) = 0
         double gc[M];
@@ -610,14 +579,14 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
         double sdotg = 0.0;
 #pragma unroll
         for(int i = 0; i < M; i++) sdotg += search[i] * grad[i];
-        if(rc == 0 && sdotg >= 0.0) rc = -2;  // boxQP.c:189-196
+        if(rc == 0 && sdotg >= 0.0) rc = BOXQP_NO_DESCENT;  // boxQP.c:189-196
 
         // Armijo backtracking (boxQP.c:199-227): step = 1, 0.6, 0.6*0.6, ... until the candidate passes.
         // Most calls pass at once, but the lanes of a wavefront wait for the slowest one (measured: 1.9 trials
         // per lane, 15 per wavefront by iteration 20 of the benchmark: a third of the backward step), so the loop
         // is built for the long case and every trial is as few instructions as the reference's arithmetic allows:
         //  * several consecutive step sizes per trip as independent instruction streams (2 in the first trip,
-        //    ARMIJO_TRIALS_LATE in the later ones, when only the slow lanes are left);
+        //    ARMIJO_TRIP_LATE in the later ones, when only the slow lanes are left);
         //  * the acceptance test without the division wherever the outcome is beyond doubt: with
         //    n = vc - oldvalue and d = step*sdotg < 0 the reference's (n / d) >= armijo holds iff
         //    n <= armijo*d (up to the rounding of the quotient).  The thresholds step*c_lo / step*c_hi are
@@ -634,7 +603,7 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
         double step = 1.0, st_take = 0.0;
         bool searching = (rc == 0), took = false;
         const bool sane = sdotg < 0.0;
-        const double thr = armijo * sdotg;
+        const double thr = BOXQP_ARMIJO * sdotg;
         const double c_lo = thr * (1.0 + 2e-15), c_hi = thr * (1.0 - 2e-15);
         int k0 = 0;  // number of the trip's first trial; the lanes still searching share it (and `step`)
         if(pf) pf->probe(2);
@@ -646,7 +615,7 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
             bool below[NT], doubt[NT], unsure = false;
             st[0] = step;
 #pragma unroll
-            for(int j = 0; j < NT; j++) st[j + 1] = st[j] * step_dec;
+            for(int j = 0; j < NT; j++) st[j + 1] = st[j] * BOXQP_STEP_DEC;
 #pragma unroll
             for(int j = 0; j < NT; j++) {
                 double xt[M];
@@ -662,7 +631,7 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
             if(unsure) {
 #pragma unroll
                 for(int j = 0; j < NT; j++)
-                    if(doubt[j]) below[j] = armijo_exact(vt[j], oldvalue, st[j], sdotg, armijo);
+                    if(doubt[j]) below[j] = BOXQP_ARMIJO_OK(vt[j], oldvalue, st[j], sdotg);
             }
             // The reference's loop reaches trial k if all before it failed and k <= ARMIJO_LAST: a failed trial k is
             // followed by step * stepDec < minStep -> return 2 exactly for k = ARMIJO_LAST (boxQP.c:222-224; the
@@ -679,13 +648,13 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
             st_take = hit ? st_first : st_take;
             took = took | hit;
             const bool out = searching & !hit & (k0 + NT - 1 >= ARMIJO_LAST);
-            rc = out ? 2 : rc;
+            rc = out ? BOXQP_STEP_LIMIT : rc;
             searching = searching & !hit & !out;
             k0 += NT;
             step = st[NT];
         };
-        if(searching) trip(std::integral_constant<int, ARMIJO_TRIALS>());
-        while(searching) trip(std::integral_constant<int, ARMIJO_TRIALS_LATE>());
+        if(searching) trip(std::integral_constant<int, ARMIJO_TRIP_FIRST>());
+        while(searching) trip(std::integral_constant<int, ARMIJO_TRIP_LATE>());
         double xc[M], vc = value;
 #pragma unroll
         for(int i = 0; i < M; i++) {
@@ -703,116 +672,7 @@ ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const
         value = accepted ? vc : value;
         if(rc != 0) break;
     }
-    return rc ? rc : 1;  // 1: max_iter iterations (boxQP.c:237)
-}
-
-// The same algorithm in the reference's own control flow (early returns, one trial per trip of the Armijo loop):
-// for callers whose lanes all solve the SAME problem (wave mapping: the box QP of a step is evaluated redundantly
-// by every lane), where nothing diverges and the predicated form above would only add work.
-template <int M>
-ILQG_DEV int box_qp_uniform(const double *H, const double *g, const double *lower, const double *upper, double *x,
-                    int *clamp, int &n_free_out, double *invH) {
-    constexpr int T = tri(M);
-    const int max_iter = 100;
-    const double min_grad = 1e-8, min_rel_improve = 1e-8, step_dec = 0.6, min_step = 1e-22, armijo = 0.1;
-    double grad[M], search[M], xc[M];
-    double value, oldvalue = 0.0;
-
-#pragma unroll
-    for(int i = 0; i < M; i++) {
-        if(x[i] > upper[i]) x[i] = upper[i];
-        if(x[i] < lower[i]) x[i] = lower[i];
-        clamp[i] = 0;
-    }
-#pragma unroll
-    for(int i = 0; i < T; i++) invH[i] = 0.0;
-    n_free_out = 0;
-    value = qp_value<M>(H, g, x);
-
-    for(int iter = 0; iter < max_iter; iter++) {
-        if(iter > 0 && (oldvalue - value) < min_rel_improve * fabs(oldvalue)) return 4;
-        oldvalue = value;
-
-        bool all_clamped = true, changed = false;
-        int n_free = 0;
-        double gnorm = 0.0;
-#pragma unroll
-        for(int i = 0; i < M; i++) {
-            double hx = 0.0;
-#pragma unroll
-            for(int j = 0; j < M; j++) hx += H[sy(i, j)] * x[j];
-            grad[i] = g[i] + hx;
-            const int was = clamp[i];
-            if(x[i] <= lower[i] && grad[i] > 0)
-                clamp[i] = 1;
-            else if(x[i] >= upper[i] && grad[i] < 0)
-                clamp[i] = 2;
-            else {
-                clamp[i] = 0;
-                all_clamped = false;
-                gnorm += grad[i] * grad[i];
-                n_free++;
-            }
-            if((!was) != (!clamp[i])) changed = true;
-        }
-        n_free_out = n_free;
-        if(all_clamped) return 6;
-
-        if(iter == 0 || changed) {
-            double Hm[T], U[T];
-#pragma unroll
-            for(int j = 0; j < M; j++)
-#pragma unroll
-                for(int i = 0; i <= j; i++)
-                    Hm[ut(i, j)] = (clamp[i] || clamp[j]) ? ((i == j) ? 1.0 : 0.0) : H[ut(i, j)];
-            if(!chol_factor<M>(Hm, U)) return -1;
-            chol_inverse<M>(U, invH);
-        }
-
-        if(gnorm < min_grad * min_grad) return 5;
-
-        // search(free) = -invH(free,free) * (g + H x_clamped)(free) - x(free); search(clamped) = 0
-        double gc[M];
-#pragma unroll
-        for(int i = 0; i < M; i++) {
-            double hc = 0.0;
-#pragma unroll
-            for(int j = 0; j < M; j++)
-                if(clamp[j]) hc += H[sy(i, j)] * x[j];
-            gc[i] = g[i] + hc;
-        }
-#pragma unroll
-        for(int i = 0; i < M; i++) {
-            double s = -x[i];
-#pragma unroll
-            for(int j = 0; j < M; j++)
-                if(!clamp[j]) s -= invH[sy(i, j)] * gc[j];
-            search[i] = clamp[i] ? 0.0 : s;
-        }
-
-        double sdotg = 0.0;
-#pragma unroll
-        for(int i = 0; i < M; i++) sdotg += search[i] * grad[i];
-        if(sdotg >= 0.0) return -2;
-
-        double step = 1.0, vc;
-        for(;;) {
-#pragma unroll
-            for(int i = 0; i < M; i++) {
-                xc[i] = x[i] + step * search[i];
-                if(xc[i] > upper[i]) xc[i] = upper[i];
-                if(xc[i] < lower[i]) xc[i] = lower[i];
-            }
-            vc = qp_value<M>(H, g, xc);
-            if(((vc - oldvalue) / (step * sdotg)) >= armijo) break;
-            step = step * step_dec;
-            if(step < min_step) return 2;
-        }
-#pragma unroll
-        for(int i = 0; i < M; i++) x[i] = xc[i];
-        value = vc;
-    }
-    return 1;
+    return rc ? rc : BOXQP_ITER_LIMIT;
 }
 
 // ---------------------------------------------------------------------------

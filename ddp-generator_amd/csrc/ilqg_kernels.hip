@@ -601,7 +601,6 @@ typedef traj_t eltraj_t;
 #include "ilqg_quad.hpp"  // 16-lane rows; only the wave mapping uses them
 #endif
 #include "ilqg_shim.h"
-#include "ilqg_rules.h"
 
 namespace {
 

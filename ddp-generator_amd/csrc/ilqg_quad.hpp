@@ -103,8 +103,7 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
     lane &= 63;
     const int me = (lane & 15) % M;
     const unsigned all = (1u << M) - 1u;
-    const int max_iter = 100;
-    const double min_grad = 1e-8, min_rel_improve = 1e-8, step_dec = 0.6, min_step = 1e-22, armijo = 0.1;
+    constexpr int INACTIVE = 99;  // rc of a row that is not `active`
 
     double Ucol[M];
 #pragma unroll
@@ -113,8 +112,7 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
         Ucol[j] = 0.0;
     }
     double xs = x;  // warm start, into the box
-    if(xs > upper) xs = upper;
-    if(xs < lower) xs = lower;
+    BOXQP_CLIP(xs, lower, upper);
     int clamp = 0;
 
     // value(y) = sum_i y_i (g_i + 0.5 (H y)_i), boxQP.c:17-37
@@ -128,9 +126,9 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
     };
 
     double value = qp_value(xs), oldvalue = 0.0;
-    int rc = active ? 0 : 99;  // 0: iterating
-    for(int iter = 0; iter < max_iter; iter++) {
-        if(iter > 0 && rc == 0 && (oldvalue - value) < min_rel_improve * fabs(oldvalue)) rc = 4;  // boxQP.c:85-86
+    int rc = active ? 0 : INACTIVE;  // 0: iterating
+    for(int iter = 0; iter < BOXQP_MAX_ITER; iter++) {
+        if(iter > 0 && rc == 0 && BOXQP_STALL(oldvalue, value)) rc = BOXQP_STALLED;
         if(!any_lane(rc == 0)) break;
         const bool live0 = rc == 0;
         oldvalue = live0 ? value : oldvalue;
@@ -141,14 +139,14 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
         const double grad = g + hx;
         const int was = clamp;
         int now = 0;
-        if(xs <= lower && grad > 0)
+        if(BOXQP_AT_LOWER(xs, lower, grad))
             now = 1;
-        else if(xs >= upper && grad < 0)
+        else if(BOXQP_AT_UPPER(xs, upper, grad))
             now = 2;
         clamp = live0 ? now : was;
         const unsigned cm = row_bits(__builtin_amdgcn_ballot_w64(clamp != 0), lane) & all;  // this row's clamped variables
         const bool changed = (row_bits(__builtin_amdgcn_ballot_w64((!was) != (!clamp)), lane) & all) != 0u;
-        if(live0 && cm == all) rc = 6;  // boxQP.c:124-126
+        if(live0 && cm == all) rc = BOXQP_ALL_CLAMPED;
         double gradm = clamp ? 0.0 : grad;  // (free variables only: the others add zeros)
         double gnorm = 0.0;
         bc_dot2<M>(gnorm, gradm, gradm);
@@ -254,10 +252,10 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
                 invrow[j] = take ? v : invrow[j];
             });
             wave_sync();
-            if(fresh && !pd) rc = -1;
+            if(fresh && !pd) rc = BOXQP_NOT_PD;
         }
 
-        if(rc == 0 && gnorm < min_grad * min_grad) rc = 5;  // boxQP.c:149-150
+        if(rc == 0 && BOXQP_GRAD_SMALL(gnorm)) rc = BOXQP_SMALL_GRAD;
 
         // search(free) = -invH(free,free) (g + H x_clamped)(free) - x(free); search(clamped) = 0 (boxQP.c:170-196)
         double xcl = clamp ? xs : 0.0;
@@ -269,7 +267,7 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
         double search = clamp ? 0.0 : sr;
         double sdotg = 0.0;
         bc_dot2<M>(sdotg, search, grad);
-        if(rc == 0 && sdotg >= 0.0) rc = -2;  // boxQP.c:189-196
+        if(rc == 0 && sdotg >= 0.0) rc = BOXQP_NO_DESCENT;  // boxQP.c:189-196
 
         // Armijo backtracking (boxQP.c:199-227): every row walks the same sequence of step sizes; a row that has passed
         // keeps its candidate, a row still searching when the step falls below minStep leaves with 2
@@ -277,17 +275,16 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
         bool searching = rc == 0;
         while(any_lane(searching)) {
             double xc = xs + step * search;
-            if(xc > upper) xc = upper;
-            if(xc < lower) xc = lower;
+            BOXQP_CLIP(xc, lower, upper);
             const double vc = qp_value(xc);
-            const bool pass = ((vc - oldvalue) / (step * sdotg)) >= armijo;
+            const bool pass = BOXQP_ARMIJO_OK(vc, oldvalue, step, sdotg);
             const bool hit = searching && pass;
             xn = hit ? xc : xn;
             vn = hit ? vc : vn;
             searching = searching && !pass;
-            step = step * step_dec;
-            if(step < min_step) {  // (the same in every lane)
-                rc = searching ? 2 : rc;
+            step = step * BOXQP_STEP_DEC;
+            if(step < BOXQP_MIN_STEP) {  // (the same in every lane)
+                rc = searching ? BOXQP_STEP_LIMIT : rc;
                 searching = false;
             }
         }
@@ -295,8 +292,8 @@ ILQG_DEV int box_qp_quad(const double (&Hrow)[M], const double g, const double l
         xs = accepted ? xn : xs;
         value = accepted ? vn : value;
     }
-    if(rc == 0) rc = 1;  // max_iter iterations (boxQP.c:237)
-    if(rc == 99) rc = 0;
+    if(rc == 0) rc = BOXQP_ITER_LIMIT;
+    if(rc == INACTIVE) rc = 0;
     x = active ? xs : x;
     clamp_out = clamp;
     return rc;
@@ -734,7 +731,7 @@ __device__ __forceinline__ int back_step_quad(const unsigned rb, const unsigned 
     double ih[NU];  // invH[me, .]
     double lsol = lcur;
     const int rc = box_qp_quad<NU>(hrow, qul, lo_k, up_k, lsol, live, rb + Q::inv * 8, mine, ih, rb + Q::basis * 8);
-    const bool ok = live && rc >= 1;
+    const bool ok = live && BOXQP_OK(rc);
     if(pf) pf->probe(5);
     __builtin_amdgcn_sched_barrier(0);
 

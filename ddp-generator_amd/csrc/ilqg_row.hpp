@@ -202,8 +202,6 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
     lane &= 63;
     const int me = (lane & 15) % M;
     const unsigned all = (1u << M) - 1u;
-    const int max_iter = 100;
-    const double min_grad = 1e-8, min_rel_improve = 1e-8, step_dec = 0.6, min_step = 1e-22, armijo = 0.1;
     unsigned inv_at = 0;  // LDS address of the inverse (full-square form)
     if constexpr(LD > 0) inv_at = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr(S_invH));
 
@@ -222,8 +220,7 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
         Ucol[j] = 0.0;
     }
     double x = S_l[me];  // warm start
-    if(x > upper) x = upper;
-    if(x < lower) x = lower;
+    BOXQP_CLIP(x, lower, upper);
     int clamp = 0;
     if constexpr(LD == 0)
         for(int e = lane; e < T; e += 64) S_invH[e] = 0.0;
@@ -242,9 +239,9 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
     };
 
     double value = qp_value(x), oldvalue = 0.0;
-    int rc = 1;  // max_iter iterations (boxQP.c:237)
-    for(int iter = 0; iter < max_iter; iter++) {
-        if(iter > 0 && (oldvalue - value) < min_rel_improve * fabs(oldvalue)) { rc = 4; break; }
+    int rc = BOXQP_ITER_LIMIT;
+    for(int iter = 0; iter < BOXQP_MAX_ITER; iter++) {
+        if(iter > 0 && BOXQP_STALL(oldvalue, value)) { rc = BOXQP_STALLED; break; }
         oldvalue = value;
 
         // gradient and clamped set (boxQP.c:101-124)
@@ -253,9 +250,9 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
         row_dot<M>(hx, x, Hrow);
         double grad = g + hx;
         const int was = clamp;
-        if(x <= lower && grad > 0)
+        if(BOXQP_AT_LOWER(x, lower, grad))
             clamp = 1;
-        else if(x >= upper && grad < 0)
+        else if(BOXQP_AT_UPPER(x, upper, grad))
             clamp = 2;
         else
             clamp = 0;
@@ -263,7 +260,7 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
         const bool changed = ((unsigned)__ballot((!was) != (!clamp)) & all) != 0;
         const int n_free = M - __popc(cm);
         n_free_out = n_free;
-        if(cm == all) { rc = 6; break; }
+        if(cm == all) { rc = BOXQP_ALL_CLAMPED; break; }
         dpp_source(grad);
         double gnorm = 0.0;
         static_for<0, M>([&](auto ic) {
@@ -302,7 +299,7 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
                 Ucol[j] = lane_pick<lanes_of<M>(j, 0)>(dg[j], lane_pick<lanes_of<M>(j, 1)>(rdg[j] * sv, 0.0));
                 dpp_source(Ucol[j]);
             });
-            if(!pd) { rc = -1; break; }
+            if(!pd) { rc = BOXQP_NOT_PD; break; }
             // explicit inverse (cholesky.c:51-74): lane l solves U'U y = e_l; y[k] for k >= l is row l of the inverse
             double y[M];
             auto solve = [&](auto plain_c) {
@@ -359,7 +356,7 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
             }
         }
 
-        if(gnorm < min_grad * min_grad) { rc = 5; break; }
+        if(BOXQP_GRAD_SMALL(gnorm)) { rc = BOXQP_SMALL_GRAD; break; }
 
         // search(free) = -invH(free,free) (g + H x_clamped)(free) - x(free); search(clamped) = 0 (boxQP.c:170-196)
         double hc = 0.0;
@@ -379,21 +376,20 @@ ILQG_DEV int box_qp_row(const double *H /* LDS */, const double g, const double 
 
         double sdotg = 0.0;
         static_for<0, M>([&](auto ic) { row_fma2<decltype(ic)::value>(sdotg, search, grad); });
-        if(sdotg >= 0.0) { rc = -2; break; }
+        if(sdotg >= 0.0) { rc = BOXQP_NO_DESCENT; break; }
 
         // Armijo line search (boxQP.c:203-228)
         double step = 1.0, vc, xc;
         bool tiny = false;
         for(;;) {
             xc = x + step * search;
-            if(xc > upper) xc = upper;
-            if(xc < lower) xc = lower;
+            BOXQP_CLIP(xc, lower, upper);
             vc = qp_value(xc);
-            if(((vc - oldvalue) / (step * sdotg)) >= armijo) break;
-            step = step * step_dec;
-            if(step < min_step) { tiny = true; break; }
+            if(BOXQP_ARMIJO_OK(vc, oldvalue, step, sdotg)) break;
+            step = step * BOXQP_STEP_DEC;
+            if(step < BOXQP_MIN_STEP) { tiny = true; break; }
         }
-        if(tiny) { rc = 2; break; }
+        if(tiny) { rc = BOXQP_STEP_LIMIT; break; }
         x = xc;
         value = vc;
     }
@@ -797,7 +793,7 @@ __device__ __forceinline__ int back_step_row(RowLds<NX, NU> &S, const Source &D,
     // (the gradient of input me: with NU a power of two that is this lane's own Qu[c])
     const int rc = box_qp_row<NU, LDU>(S.QuuF, P2U ? qul : S.Qu[me], lo_k, up_k, S.l, S.clamp, S.invH, nf, &mine, &cm_lo, &cm_hi, ih);
     if(pf) pf->probe(3);
-    if(rc < 1) return rc;
+    if(BOXQP_FAILED(rc)) return rc;
 
     // ---- feedback gains (back_pass.c:175-201): lane (g, i) computes K[i, 4g+j], input i = c, state 4g+j
     double kt[4] = {0.0, 0.0, 0.0, 0.0};

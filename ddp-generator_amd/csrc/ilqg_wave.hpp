@@ -10,8 +10,8 @@
 // a wave reads each array field with consecutive lanes on consecutive doubles (coalesced).
 // x, u, l, L are trajectory-major [trajectory][step][field].
 //
-// The box QP of a step (boxQP.c:39-238, size NU) is evaluated redundantly by all lanes in
-// registers with the same template the lane mapping uses (box_qp_uniform<NU>); its results go through
+// The box QP of a step (boxQP.c:39-238, size NU) is solved cooperatively, one lane per input
+// (box_qp_rows below; box_qp_row of ilqg_row.hpp where ILQG_ROW_STEP holds); its results go through
 // LDS because the gain formula indexes them per lane.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,7 +54,8 @@ struct WaveLds {
 // Every scalar of the reference is computed by ONE expression tree in the reference's own operand order —
 // a row sum runs j = 0..M-1 on the row's lane with x[j] broadcast (v_readlane), a sum over the variables
 // (value, gradient norm, search'grad) runs i = 0..M-1 on broadcast operands, uniformly on all lanes — so
-// the results are those of box_qp_uniform bit for bit (asserted by a unit test on the reference's goldens).
+// the results are those of the lane mapping's box_qp bit for bit in the FMA-free build (asserted by a unit test on
+// the reference's goldens and on random problems).
 // Sums over a subset (free or clamped variables) skip the others through wave-uniform masks, as the
 // reference's loops do; where the reference's loop bounds depend on the row (Cholesky, inverse) the extra
 // terms are exact zeros.
@@ -88,8 +89,6 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
     constexpr int T = tri(M);
     const int lane = threadIdx.x & 63, me = lane % M;
     const unsigned all = (M == 32) ? 0xffffffffu : ((1u << M) - 1u);
-    const int max_iter = 100;
-    const double min_grad = 1e-8, min_rel_improve = 1e-8, step_dec = 0.6, min_step = 1e-22, armijo = 0.1;
 
     double Hrow[M], invrow[M], Ucol[M];
 #pragma unroll
@@ -99,8 +98,7 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
         Ucol[j] = 0.0;
     }
     double x = S_l[me];  // warm start
-    if(x > upper) x = upper;
-    if(x < lower) x = lower;
+    BOXQP_CLIP(x, lower, upper);
     int clamp = 0;
     for(int e = lane; e < T; e += 64) S_invH[e] = 0.0;
     n_free_out = 0;
@@ -118,9 +116,9 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
     };
 
     double value = qp_value_rows(x), oldvalue = 0.0;
-    int rc = 1;  // max_iter iterations (boxQP.c:237)
-    for(int iter = 0; iter < max_iter; iter++) {
-        if(iter > 0 && (oldvalue - value) < min_rel_improve * fabs(oldvalue)) { rc = 4; break; }
+    int rc = BOXQP_ITER_LIMIT;
+    for(int iter = 0; iter < BOXQP_MAX_ITER; iter++) {
+        if(iter > 0 && BOXQP_STALL(oldvalue, value)) { rc = BOXQP_STALLED; break; }
         oldvalue = value;
 
         // gradient and clamped set (boxQP.c:101-124)
@@ -129,9 +127,9 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
         for(int j = 0; j < M; j++) hx += Hrow[j] * lane_bcast(x, j);
         const double grad = g + hx;
         const int was = clamp;
-        if(x <= lower && grad > 0)
+        if(BOXQP_AT_LOWER(x, lower, grad))
             clamp = 1;
-        else if(x >= upper && grad < 0)
+        else if(BOXQP_AT_UPPER(x, upper, grad))
             clamp = 2;
         else
             clamp = 0;
@@ -139,7 +137,7 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
         const bool changed = ((unsigned)__ballot((!was) != (!clamp)) & all) != 0;
         const int n_free = M - __popc(cm);
         n_free_out = n_free;
-        if(cm == all) { rc = 6; break; }
+        if(cm == all) { rc = BOXQP_ALL_CLAMPED; break; }
         double gnorm = 0.0;
 #pragma unroll
         for(int i = 0; i < M; i++) {
@@ -164,7 +162,7 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
                 const double d = sqrt(piv);
                 Ucol[j] = (me == j) ? d : ((me > j) ? 1.0 / d * sv : 0.0);
             }
-            if(!pd) { rc = -1; break; }
+            if(!pd) { rc = BOXQP_NOT_PD; break; }
             // explicit inverse (cholesky.c:51-74): lane l solves U'U y = e_l; y[k] for k >= l is row l of the inverse
             double y[M];
 #pragma unroll
@@ -192,7 +190,7 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
             for(int j = 0; j < M; j++) invrow[j] = S_invH[sy(me, j)];
         }
 
-        if(gnorm < min_grad * min_grad) { rc = 5; break; }
+        if(BOXQP_GRAD_SMALL(gnorm)) { rc = BOXQP_SMALL_GRAD; break; }
 
         // search(free) = -invH(free,free) (g + H x_clamped)(free) - x(free); search(clamped) = 0 (boxQP.c:170-196)
         double hc = 0.0;
@@ -213,21 +211,20 @@ ILQG_DEV int box_qp_rows(const double *Hpacked /* LDS */, const double g, const 
         double sdotg = 0.0;
 #pragma unroll
         for(int i = 0; i < M; i++) sdotg += lane_bcast(search, i) * lane_bcast(grad, i);
-        if(sdotg >= 0.0) { rc = -2; break; }
+        if(sdotg >= 0.0) { rc = BOXQP_NO_DESCENT; break; }
 
         // Armijo line search (boxQP.c:203-228)
         double step = 1.0, vc, xc;
         bool tiny = false;
         for(;;) {
             xc = x + step * search;
-            if(xc > upper) xc = upper;
-            if(xc < lower) xc = lower;
+            BOXQP_CLIP(xc, lower, upper);
             vc = qp_value_rows(xc);
-            if(((vc - oldvalue) / (step * sdotg)) >= armijo) break;
-            step = step * step_dec;
-            if(step < min_step) { tiny = true; break; }
+            if(BOXQP_ARMIJO_OK(vc, oldvalue, step, sdotg)) break;
+            step = step * BOXQP_STEP_DEC;
+            if(step < BOXQP_MIN_STEP) { tiny = true; break; }
         }
-        if(tiny) { rc = 2; break; }
+        if(tiny) { rc = BOXQP_STEP_LIMIT; break; }
         x = xc;
         value = vc;
     }
@@ -478,7 +475,7 @@ __device__ __forceinline__ int back_step_wave(WaveLds<NX, NU> &S, const StepFiel
     int rc, nf;
     rc = box_qp_rows<NU>(S.QuuF, S.Qu[lane % NU], lo_k, up_k, S.l, S.clamp, S.invH, nf);
     if(pf) pf->probe(3);
-    if(rc < 1) return rc;
+    if(BOXQP_FAILED(rc)) return rc;
 
     // feedback gains (back_pass.c:175-201); invH is in full-index form (see box_qp)
     for(int o = lane; o < NXU; o += 64) {

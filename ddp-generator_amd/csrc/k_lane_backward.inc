@@ -205,7 +205,7 @@ __device__ __forceinline__ int backward_sweep(const DevPtrs &P, int b, double la
         // l still holds the solution of step k+1: the warm start (back_pass.c:165-166)
         const int rc = back_step<NX, NU, FULL, HX>(cur, ucur, Vx, Vxx, l, K, lambda, regType, dV0, dV1, gsum);
         store_gains<XSI>(l, K, lo, ko);
-        if(rc < 1) {
+        if(BOXQP_FAILED(rc)) {
             failed = 1;
             break;
         }
@@ -345,7 +345,7 @@ __device__ __forceinline__ int backward_sweep_fused(const DevPtrs &P, Callbacks 
 #pragma unroll
             for(int i = 0; i < NU; i++) rec_k[NOM_U + i] = uk[i];
         }
-        if(rc < 1) {
+        if(BOXQP_FAILED(rc)) {
             result = 1;
             break;
         }

@@ -594,7 +594,7 @@ __device__ __forceinline__ int backward_sweep_wave(StepLds &S, const double *tab
 #ifdef ILQG_PROFILE_SECTIONS
         prof.acc[7]++;  // steps executed (sweeps that are abandoned half way count with the steps they ran)
 #endif
-        if(rc < 1) {
+        if(BOXQP_FAILED(rc)) {
             failed = 1;
             break;
         }
@@ -1009,7 +1009,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
 #endif
             // ---- what the row does next
             if constexpr(SPEC) {
-                const bool failed = busy && rc < 1, finished = busy && rc >= 1 && k == 0;
+                const bool failed = busy && BOXQP_FAILED(rc), finished = busy && BOXQP_OK(rc) && k == 0;
                 bool overtaken = false;
 #ifdef ILQG_COUNT_STEPS
                 if(busy) walked++;
@@ -1104,7 +1104,7 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
 #ifdef ILQG_COUNT_STEPS
                 walked++;
 #endif
-                if(rc < 1) {  // the sweep is abandoned (back_pass.c:168-171): raise lambda and sweep again (iLQG.c:267-275)
+                if(BOXQP_FAILED(rc)) {  // the sweep is abandoned (back_pass.c:168-171): raise lambda and sweep again (iLQG.c:267-275)
                     calls++;
                     bp_rc = 1;
                     done = true;
