@@ -19,20 +19,27 @@ single RCCL gather of the per-trajectory costs at the end of the timed window
 (weak scaling: 65 536 trajectories per GPU).  PyTorch is used only for process
 rendezvous, the RCCL collective and device synchronisation.
 
+A plain run does what its headline needs: it sets up, warms up, times the K steps, writes --dump-outputs, and reports
+what the timed window's own HIP events give.  Whatever takes runs of its own — the live PMC traffic, the CPU baseline,
+the other configurations, the kernels alone, the full solves — is measured only with --full (a few minutes).
+
 Prints ONE compact JSON line (rank 0; < 6 KB, nothing else reaches stdout) and writes the full report to
 bench_detail.json beside this file (and to gpurun_out/ where that exists):
   value / ms_per_step   the timed window (three groups of trajectories on three streams)
   roofline              the dominant kernel's launches IN the timed window (HIP events on the solver's streams): SURVEY
                         8(d)'s algorithmic bytes of the stages it replaces / its average duration against 8 TB/s, the PMC
-                        traffic per launch (collected in this run by two short rocprofv3 child runs), its real HBM
-                        utilisation, the limiter and the issue counters of the committed SQ passes
+                        traffic per launch (the committed profiles/traffic.json; with --full collected in this run by
+                        two short rocprofv3 child runs), its real HBM utilisation, the limiter and the issue counters of
+                        the committed SQ passes
   iteration_roofline    the whole iteration against the HBM roofline with SURVEY 8(d)'s algorithmic bytes
-  cpu_baseline          the CPU checker (the reference's own sources when oracle/_ref was shipped) on a bounded
-                        sample of the same workload on this box's host cores
-  config5, config5_stored, config2, dropin_b1
+  --full                adds, each reduced in the line and whole in bench_detail.json:
+    cpu_baseline        the CPU checker (the reference's own sources when oracle/_ref was shipped) on a bounded
+                        sample of the same workload on the host's cores
+    config5, config5_stored, config2, dropin_b1
                         the other BASELINE configs, each measured in a fresh child process (`--object NAME`), reduced
-                        to value / ms_per_step / fractions; the full objects are in bench_detail.json
-  --full                adds full solves to convergence, the dominant kernel alone and the unfused kernel pair
+                        to value / ms_per_step / fractions
+    full_solve, roofline.alone, unfused_kernels
+                        full solves to convergence, the dominant kernel alone and the unfused kernel pair
   --dump-outputs DIR    writes what the timed window computed (rank 0's shard) to DIR/*.npy: cost, lambda, status,
                         iterations of every trajectory, x / u of a fixed seeded sample of them (64 MB at most)
 """
@@ -753,7 +760,7 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed window, write what it computed to DIR/<name>.npy (dump_outputs(); at most 64 MB)")
     ap.add_argument("--config5-variant", choices=("factored", "stored", "pair"), default=None,
-                    help="only BASELINE config 5 in one of its forms (the object `config5` of the default line), as its own JSON line")
+                    help="only BASELINE config 5 in one of its forms (the object `config5` of the --full line), as its own JSON line")
     ap.add_argument("--workload", choices=("car", "synth"), default="car",
                     help="car: BASELINE metric (CarParking n=4,m=2,N=500, 65 536 per GPU); synth: BASELINE config 5 "
                          "(n=16,m=8,N=1000, FULL_DDP=1, 16 384 per GPU, one wavefront per trajectory) as the headline")
@@ -762,7 +769,7 @@ def main():
     ap.add_argument("--full-ddp", type=int, default=None)
     ap.add_argument("--mapping", choices=("auto", "wave"), default="auto",
                     help="wave: CarParking in the one-wavefront-per-trajectory build (comparison)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, --object config5: without the CPU baseline")
     ap.add_argument("--resweep", type=int, default=-1, help="-1: library default (off without multipliers)")
     ap.add_argument("--fuse-derivs", type=int, default=1)
     ap.add_argument("--ls-split", type=int, default=None, help="default: the library's (4; 1 in the wave mapping)")
@@ -770,11 +777,12 @@ def main():
     ap.add_argument("--ls-keep", type=int, default=None,
                     help="default: the library's (2 in the lane mapping: every roll-out kept, the accepted one relocated; 1 in the wave "
                          "mapping: second stage beside the re-rolled winners); 0: second stage, then winner pass")
-    ap.add_argument("--no-unfused", action="store_true", help="skip the secondary runs (kernels alone, config 5, drop-in)")
-    ap.add_argument("--no-config5", action="store_true")
+    ap.add_argument("--no-unfused", action="store_true",
+                    help="--full: skip the secondary runs (live traffic, kernels alone, full solves, config 5, config 2, drop-in)")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the config 5 objects")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not collect the PMC traffic of the headline's kernels in this run (two short rocprofv3 child runs); the "
-                         "committed, source-stamped profiles/traffic.json is quoted instead")
+                    help="--full: do not collect the PMC traffic of the headline's kernels in this run (two short rocprofv3 child "
+                         "runs); the committed, source-stamped profiles/traffic.json is quoted instead, as in a plain run")
     ap.add_argument("--solve", action="store_true",
                     help="full solves instead of the benchmark window: --batch CarParking starts solved to convergence (max_iter "
                          "--max-iter), with and without retiring finished trajectories; prints its own JSON line")
@@ -794,11 +802,13 @@ def main():
                     help="no solver, no GPU: the ranks run the sharding / barrier / gather / JSON protocol around a stand-in "
                          "(ProtocolShard); the line is marked `rehearsal` and measures nothing")
     ap.add_argument("--object", default=None,
-                    help="(used by the default run) ONE secondary object of the report — config5, config5_stored, config5_pair, "
+                    help="(used by --full) ONE secondary object of the report — config5, config5_stored, config5_pair, "
                          "config2, dropin_b1, alone, unfused — measured in this fresh process, as one JSON line")
     ap.add_argument("--full", action="store_true",
-                    help="also the long secondary objects: full solves to convergence (plain / compacted / streamed), the "
-                         "dominant kernel alone, the two kernels of the unfused path (all go to bench_detail.json)")
+                    help="after the headline, everything that takes runs of its own: the CPU baseline and, for the CarParking "
+                         "headline on one GPU, the live PMC traffic, config 5 / its stored form / config 2 / the drop-in, the "
+                         "dominant kernel alone, the two kernels of the unfused path, full solves to convergence (plain / "
+                         "compacted / streamed); a plain run measures the headline alone")
     ap.add_argument("--groups", type=int, default=0,
                     help="independent sets of trajectories advanced on separate HIP streams (0: library default)")
     args = ap.parse_args()
@@ -812,7 +822,7 @@ def main():
     if args.dump_outputs and (args.object or args.config5_variant or args.solve or args.solve_one is not None or args.solve_stream is not None
                               or args.rehearse_protocol):
         ap.error("--dump-outputs goes with the benchmark window of the solver (the default run or --single-process)")
-    if args.object:  # a child of the default run: no torch, no process group
+    if args.object:  # a child of a --full run: no torch, no process group
         return child_object(args)
 
     import torch
@@ -975,7 +985,9 @@ def main():
             "trajectories_still_active": int(active),
             "cost_mean_after_window": float(cost.mean()),
         }
-        secondary = world == 1 and not args.no_unfused and not wave_mapping and car
+        # --full: the objects that take runs of their own (child processes, profiler passes, the host's cores); a plain
+        # run reports the timed window alone
+        secondary = args.full and world == 1 and not args.no_unfused and not wave_mapping and car
         if not rehearsal and not wave_mapping and car:  # (at N > 1: rank 0's own launches, its shard of the batch)
             # The two dominant launches IN THE TIMED WINDOW (HIP events on the solver's streams around every launch of the
             # K timed iterations; the groups of trajectories overlap, a launch covers one group):
@@ -1062,40 +1074,39 @@ def main():
             # Every secondary object is measured in a fresh child process (run_object): its own HIP context and queues,
             # its buffers allocated into an empty device — this process has released the solver and holds only torch's
             # context.  A failure is reported in place and never costs the headline.
-            if args.full:
-                # the dominant kernel ALONE: one group of trajectories, so a launch covers the whole batch and shares the
-                # GPU with nothing; the SAME K iterations as the headline window (the kernel grows with the iterations)
-                t1 = run_object("alone", local, ["--steps", K, "--batch", B, "--n-hor", n_hor] + (["--ls-split", args.ls_split] if args.ls_split is not None else []))
-                name = "k_backward[fused derivs]"
-                if "error" not in t1 and t1.get(name, [0])[0] and "roofline" in out:
-                    n_launch, total_ms = t1[name]
-                    avg_ms = total_ms / n_launch
-                    flops_launch = backpass_flops(nx, nu, fd) * n_hor * B
-                    out["roofline"]["alone"] = {
-                        "avg_launch_ms": avg_ms, "launches": n_launch, "stream_groups": 1, "trajectories_per_launch": B,
-                        "valu_fp64_TFLOPs": flops_launch / (avg_ms * 1e-3) / 1e12,
-                        "valu_fp64_frac": flops_launch / (avg_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
-                        "hbm_equivalent_GBs": (alg["k_derivs"] + alg["k_backward"]) * n_hor * B / (avg_ms * 1e-3) / 1e9,
-                        "note": "one wavefront per SIMD (65 536 lanes): a chain of dependent fp64 instructions, see DESIGN.md; "
-                                "hbm_equivalent above the 8 TB/s peak means the fused kernel beats what the unfused pair could reach"}
-                    out["kernels_ms_per_iteration_alone"] = {k: v[1] / K for k, v in t1.items() if v[0]}
-                elif "error" in t1:
-                    out["kernels_ms_per_iteration_alone"] = t1
-                # the HBM-bound kernels of the unfused path, each alone
-                t2 = run_object("unfused", local, ["--steps", 5, "--batch", B, "--n-hor", n_hor] + (["--ls-split", args.ls_split] if args.ls_split is not None else []))
-                unfused = {}
-                for kname in ("k_derivs", "k_backward"):
-                    n, ms = t2.get(kname, (0, 0.0)) if "error" not in t2 else (0, 0.0)
-                    if n:
-                        b_alg = alg[kname] * n_hor * B
-                        unfused[kname] = {"bound": "hbm", "avg_launch_ms": ms / n, "algorithmic_bytes_per_launch": b_alg,
-                                          "achieved_GBs": b_alg / (ms / n * 1e-3) / 1e9,
-                                          "frac_of_peak": b_alg / (ms / n * 1e-3) / 1e9 / HBM_PEAK_GBS, "stream_groups": 1}
-                out["unfused_kernels"] = unfused if "error" not in t2 else t2
-                try:
-                    out["full_solve"] = full_solve(local)
-                except Exception as e:
-                    out["full_solve"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            # the dominant kernel ALONE: one group of trajectories, so a launch covers the whole batch and shares the
+            # GPU with nothing; the SAME K iterations as the headline window (the kernel grows with the iterations)
+            t1 = run_object("alone", local, ["--steps", K, "--batch", B, "--n-hor", n_hor] + (["--ls-split", args.ls_split] if args.ls_split is not None else []))
+            name = "k_backward[fused derivs]"
+            if "error" not in t1 and t1.get(name, [0])[0] and "roofline" in out:
+                n_launch, total_ms = t1[name]
+                avg_ms = total_ms / n_launch
+                flops_launch = backpass_flops(nx, nu, fd) * n_hor * B
+                out["roofline"]["alone"] = {
+                    "avg_launch_ms": avg_ms, "launches": n_launch, "stream_groups": 1, "trajectories_per_launch": B,
+                    "valu_fp64_TFLOPs": flops_launch / (avg_ms * 1e-3) / 1e12,
+                    "valu_fp64_frac": flops_launch / (avg_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
+                    "hbm_equivalent_GBs": (alg["k_derivs"] + alg["k_backward"]) * n_hor * B / (avg_ms * 1e-3) / 1e9,
+                    "note": "one wavefront per SIMD (65 536 lanes): a chain of dependent fp64 instructions, see DESIGN.md; "
+                            "hbm_equivalent above the 8 TB/s peak means the fused kernel beats what the unfused pair could reach"}
+                out["kernels_ms_per_iteration_alone"] = {k: v[1] / K for k, v in t1.items() if v[0]}
+            elif "error" in t1:
+                out["kernels_ms_per_iteration_alone"] = t1
+            # the HBM-bound kernels of the unfused path, each alone
+            t2 = run_object("unfused", local, ["--steps", 5, "--batch", B, "--n-hor", n_hor] + (["--ls-split", args.ls_split] if args.ls_split is not None else []))
+            unfused = {}
+            for kname in ("k_derivs", "k_backward"):
+                n, ms = t2.get(kname, (0, 0.0)) if "error" not in t2 else (0, 0.0)
+                if n:
+                    b_alg = alg[kname] * n_hor * B
+                    unfused[kname] = {"bound": "hbm", "avg_launch_ms": ms / n, "algorithmic_bytes_per_launch": b_alg,
+                                      "achieved_GBs": b_alg / (ms / n * 1e-3) / 1e9,
+                                      "frac_of_peak": b_alg / (ms / n * 1e-3) / 1e9 / HBM_PEAK_GBS, "stream_groups": 1}
+            out["unfused_kernels"] = unfused if "error" not in t2 else t2
+            try:
+                out["full_solve"] = full_solve(local)
+            except Exception as e:
+                out["full_solve"] = {"error": "%s: %s" % (type(e).__name__, e)}
             out["dropin_b1"] = run_object("dropin_b1", local)
             out["config2"] = run_object("config2", local, ["--steps", 20, "--warmup", 2])
             if not args.no_config5:
@@ -1111,7 +1122,7 @@ def main():
                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": out["iteration_roofline"]["frac_of_peak"],
                                "traffic": None, "note": "per GPU; algorithmic bytes of SURVEY 8(d) per iteration x "
                                                         "iterations/s."}
-        if not args.no_cpu_baseline:  # rank 0, whatever the world size: the host's cores are the same
+        if args.full and not args.no_cpu_baseline:  # rank 0, whatever the world size: the host's cores are the same
             out["cpu_baseline"] = cpu_baseline(B, K, problem, fd, params, n_hor,
                                                synth.car_batch if car else synth.synth16_batch)
         guard.emit(compact_line(out, write_detail(out)))

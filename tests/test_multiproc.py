@@ -115,10 +115,10 @@ def test_bench_main_with_two_ranks_on_one_gpu():
     """the same branch with the PRODUCT under it: two ranks (gloo, collective through host memory) share device 0, each
     advances its shard; the line is a real (small) measurement and the gathered costs are those of one 2 x 512 batch"""
     port = 29800 + (os.getpid() % 90)
-    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512", "--backend", "gloo", "--all-on-device", "0"],
+    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512", "--backend", "gloo", "--all-on-device", "0", "--full"],
                      nproc=2, port=port)
     assert out["n_gpus"] == 2 and out["value"] > 0 and "rehearsal" not in out
-    # the line of an N > 1 run is complete: the CPU baseline (rank 0's host cores) and a per-kernel roofline of rank 0's
+    # the line of an N > 1 --full run is complete: the CPU baseline (rank 0's host cores) and a per-kernel roofline of rank 0's
     # own launches (its shard), not the iteration-level stand-in
     assert out["cpu_baseline"]["cores"] >= 1 and out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["kind"] in ("reference", "port")
     rf = out["roofline"]
@@ -138,6 +138,21 @@ def test_bench_main_with_two_ranks_on_one_gpu():
     want = float(s.scalar("cost").mean())
     s.close()
     assert abs(out["cost_mean_after_window"] - want) <= 1e-12 * abs(want)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_reports_the_timed_window_alone():
+    """without --full, bench.py measures nothing but its headline: no CPU baseline, no child process — the line and the
+    report hold the timed window and what its own HIP events give"""
+    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "512"])
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    detail = json.load(open(os.path.join(ROOT, out["detail"])))
+    assert detail["value"] == out["value"]
+    for k in ("cpu_baseline", "config5", "config5_stored", "config2", "dropin_b1", "full_solve", "unfused_kernels",
+              "kernels_ms_per_iteration_alone"):
+        assert k not in detail and k not in out, k
+    rf = detail["roofline"]
+    assert rf["kernel"] == "k_backward[fused derivs]" and rf["dominant_launch"]["launches"] >= 2 and "alone" not in rf
 
 
 @pytest.mark.gpu
