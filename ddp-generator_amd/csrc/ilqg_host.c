@@ -505,6 +505,59 @@ int ilqg_batch_init(ilqg_batch_t *c) {
     return 0;
 }
 
+/* Receding horizon (no reference counterpart as a call; it is what the MEX entry's caller does between two calls:
+ * u_nom = [u(:, s+1:end), tail] and a new x0, iLQG_mex.c:113-120).  The plan moves on the device (ilqg_dev_shift); only
+ * x0_new and u_tail go up.  Then exactly ilqg_batch_init: initial roll-out, solver entry state. */
+int ilqg_batch_shift(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail) {
+    int g;
+    if(steps < 0 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift: steps = %d, must be in 0 .. n_hor - 1 = %d", steps, c->N - 1);
+        return 1;
+    }
+    if(push_config(c)) return 1;
+    EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, x0_new == NULL)) return fail(c, "shift");
+    EACH_GROUP(g) {
+        if(x0_new && ilqg_dev_write_steps(c->dev[g], ILQG_F_X, x0_new + (size_t)c->first[g] * N_X, 1)) return fail(c, "shift: x0_new");
+        if(u_tail && steps > 0 && ilqg_dev_write_u_tail(c->dev[g], u_tail + (size_t)c->first[g] * steps * N_U, steps))
+            return fail(c, "shift: u_tail");
+    }
+    EACH_GROUP(g) {
+        if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
+        if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
+    }
+    return 0;
+}
+
+static int iterate_groups(ilqg_batch_t *c, int n);
+int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, double *x_applied, double *u_applied, double *cost) {
+    int g, r, i;
+    if(rounds < 1 || iterations < 0) return fail_msg(c, "ilqg_batch_receding: need rounds >= 1 and iterations >= 0");
+    if(steps < 1 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_receding: steps = %d, must be in 1 .. n_hor - 1 = %d", steps, c->N - 1);
+        return 1;
+    }
+    for(i = 0; i < n_params; i++)
+        if(paramdesc[i]->size == -1) {
+            snprintf(c->err, sizeof(c->err), "ilqg_batch_receding: parameter '%s' has one value per time step and its window must move "
+                     "with the horizon: loop over ilqg_batch_iterate, ilqg_batch_set_param and ilqg_batch_shift instead", paramdesc[i]->name);
+            return 1;
+        }
+    if(push_config(c)) return 1;
+    EACH_GROUP(g) if(ilqg_dev_log_begin(c->dev[g], rounds, steps)) return fail(c, "receding: log");
+    for(r = 0; r < rounds; r++) {
+        if(iterate_groups(c, iterations)) return 1;
+        EACH_GROUP(g) if(ilqg_dev_log_append(c->dev[g], r)) return fail(c, "receding: log");
+        if(ilqg_batch_shift(c, steps, NULL, NULL)) return 1;
+    }
+    EACH_GROUP(g) {
+        const size_t at = (size_t)c->first[g] * rounds * steps;
+        if(ilqg_dev_log_read(c->dev[g], x_applied ? x_applied + at * N_X : NULL, u_applied ? u_applied + at * N_U : NULL,
+                             cost ? cost + (size_t)c->first[g] * rounds : NULL))
+            return fail(c, "receding: log");
+    }
+    return 0;
+}
+
 /* the groups advance alternately, one iteration at a time: their launches interleave on the device */
 static int iterate_groups(ilqg_batch_t *c, int n) {
     int it, g;
@@ -1441,6 +1494,14 @@ int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0) {
 int ilqg_multi_set_u(ilqg_multi_t *m, const double *u) {
     int g;
     EACH_SHARD(g) if(ilqg_batch_set_u(m->shard[g], u + (size_t)m->first[g] * m->N * N_U)) return multi_fail(m, g);
+    return 0;
+}
+int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const double *u_tail) {
+    int g;
+    EACH_SHARD(g)
+        if(ilqg_batch_shift(m->shard[g], steps, x0_new ? x0_new + (size_t)m->first[g] * N_X : NULL,
+                            u_tail ? u_tail + (size_t)m->first[g] * (steps > 0 ? steps : 0) * N_U : NULL))
+            return multi_fail(m, g);
     return 0;
 }
 int ilqg_multi_init(ilqg_multi_t *m) {

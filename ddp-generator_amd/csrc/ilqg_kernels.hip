@@ -1032,6 +1032,8 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 
 #include "k_common.inc"  // k_select, k_adopt, k_update, k_multipliers, unit-test kernels
 
+#include "k_shift.inc"  // k_shift_lane / k_shift_wave, k_put_u_steps, k_log_steps (receding horizon)
+
 }  // namespace
 
 #ifndef ILQG_ONLY_KERNEL

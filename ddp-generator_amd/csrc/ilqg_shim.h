@@ -115,6 +115,8 @@ enum {
     ILQG_K_SEARCH,   /* ls_keep = 2: k_search on all trajectories (first stage) */
     ILQG_K_SEARCH2,  /*             k_search on the pending list (second stage) */
     ILQG_K_ADOPT,    /*             k_adopt_home / k_rejected_home, k_commit */
+    ILQG_K_SHIFT,    /* receding horizon: k_shift_lane / k_shift_wave (ilqg_dev_shift) */
+    ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_log_append) */
     ILQG_K_COUNT
 };
 
@@ -157,6 +159,20 @@ int ilqg_dev_copy_scalar_to(ilqg_dev_t *d, int field, void *dst_device);
 /* stages (all asynchronous on the context's stream) */
 int ilqg_dev_reset(ilqg_dev_t *d);            /* solver entry state (iLQG.c:226-237) */
 int ilqg_dev_rollout_init(ilqg_dev_t *d);     /* forward_pass(alpha = 0) + swap (iLQG_mex.c:113-120) */
+/* Receding horizon: every trajectory's current controls move `steps` time steps towards the start, u'[k] = u[k + steps],
+ * the last one held over the tail; with use_plan_x0 the state the plan reaches after `steps` steps becomes x0.  Read where
+ * the current trajectory lives, written to the arrays X / U (records in the wave mapping); the location indices are
+ * cleared, so the ilqg_dev_rollout_init that follows copies nothing.  0 <= steps < n_hor. */
+int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0);
+/* the caller's tail behind a shift: host [batch][steps][N_U] into the last `steps` time steps of the controls */
+int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps);
+/* A log on the device of the steps a receding-horizon loop applies: begin sizes it for `rounds` rounds of `steps` steps,
+ * append copies (x_k, u_k), k < steps, of every current plan and its cost into round `round`, read brings the whole log to
+ * the host once: x [batch][rounds*steps][N_X], u [batch][rounds*steps][N_U], cost [batch][rounds] (any may be NULL);
+ * synchronises. */
+int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps);
+int ilqg_dev_log_append(ilqg_dev_t *d, int round);
+int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost);
 int ilqg_dev_derivs(ilqg_dev_t *d);           /* calc_derivs for trajectories that need it */
 /* back_pass.  mode 0: records from HBM + lambda retry loop + gradient test; 1: records from HBM, one
  * sweep (drop-in back_pass()); 2: as 0 with the derivatives evaluated on the fly (no k_derivs needed) */

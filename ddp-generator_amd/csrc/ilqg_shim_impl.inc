@@ -79,6 +79,8 @@ struct ilqg_dev {
     struct SharedWork *shared;  // wave mapping: the device's derivative work buffer (see SharedWork)
     int own_chunk;              // trajectories whose records fit the context's private buffer P.work (stage-by-stage calls)
     bool per_step_params;       // some problem parameter has one value per time step
+    double *log_x, *log_u, *log_c;  // receding horizon: the applied steps of every round (ilqg_dev_log_begin), host layout
+    int log_rounds, log_steps;
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
     struct EnvSwitches { bool no_quad, quad_stored, two_pieces, deriv_parts, no_dma, no_rollout_parts, quad_spec; } env;
@@ -343,7 +345,8 @@ const char *ilqg_dev_kernel_name(int k) {
     static const char *names[ILQG_K_COUNT] = {"k_derivs", "k_backward", "k_rollout[search]", "k_select",
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
-                                              "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit"};
+                                              "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
+                                              "k_log_steps"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -599,6 +602,9 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
     if(d->P.upl) hipFree(d->P.upl);
     if(d->P.pending) hipFree(d->P.pending);
     if(d->P.n_pending) hipFree(d->P.n_pending);
+    if(d->log_x) hipFree(d->log_x);
+    if(d->log_u) hipFree(d->log_u);
+    if(d->log_c) hipFree(d->log_c);
     for(double *p : d->param_bufs) hipFree(p);
     if(d->P.p) hipFree(d->P.p);
     if(d->staging) hipFree(d->staging);
@@ -1005,6 +1011,100 @@ int ilqg_dev_rollout_init(ilqg_dev_t *d) {
     launch_rollout(d, ROLL_INIT, ILQG_K_ROLLOUT_INIT, 0, 1, roll_stream(d));
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
+}
+
+// Receding horizon: the plan moves `steps` time steps towards the start where it is (k_shift.inc).  One pass over U in the
+// lane mapping — the controls are read wherever the current trajectory lives and land in the array U, so the all_home()
+// of the initial roll-out that follows has nothing left to copy — and one over the records' u in the wave mapping.
+int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(steps < 0 || steps >= d->N) {
+        g_err = "ilqg_dev_shift: steps must be in 0 .. n_hor - 1";
+        return 1;
+    }
+    {
+        Timed t(d, ILQG_K_SHIFT);
+#if ILQG_WAVE_MAP
+        hipLaunchKernelGGL(k_shift_wave, dim3(d->B), dim3(SHIFT_BLOCK), 0, d->stream, d->P, steps, use_plan_x0);
+#else
+        hipLaunchKernelGGL(k_shift_lane, dim3((unsigned)((size_t)(NX > NU ? NX : NU) * d->Bp / WAVE)), dim3(WAVE * SHIFT_WAVES), 0, d->stream, d->P, steps, use_plan_x0);
+#endif
+    }
+    HIP_TRY(hipGetLastError());
+#if !ILQG_WAVE_MAP
+    if(d->loc_set >= 0) HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
+    d->loc_set = -1;
+#endif
+    return 0;
+}
+
+int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(steps < 1 || steps > d->N) {
+        g_err = "ilqg_dev_write_u_tail: bad step count";
+        return 1;
+    }
+    if(all_home(d)) return 1;
+    const size_t n = (size_t)d->B * steps * NU;
+    void *dev, *pin;
+    if(stage(d, n * sizeof(double), &dev, &pin)) return 1;
+    if(stage_in(d, dev, pin, host, n * sizeof(double))) return 1;
+    {
+        Timed t(d, ILQG_K_TRANSPOSE);
+        hipLaunchKernelGGL(k_put_u_steps, grid1(n, 256), dim3(256), 0, d->stream, d->P, (const double *)dev, d->N - steps, steps);
+    }
+    HIP_TRY(hipGetLastError());
+    return io_done(d);
+}
+
+int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(rounds < 1 || steps < 1 || steps >= d->N) {
+        g_err = "ilqg_dev_log_begin: need rounds >= 1 and 1 <= steps < n_hor";
+        return 1;
+    }
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if(d->log_x) HIP_TRY(hipFree(d->log_x));
+    if(d->log_u) HIP_TRY(hipFree(d->log_u));
+    if(d->log_c) HIP_TRY(hipFree(d->log_c));
+    d->log_x = d->log_u = d->log_c = nullptr;
+    d->log_rounds = d->log_steps = 0;
+    const size_t per = (size_t)d->B * rounds * steps;
+    HIP_TRY(hipMalloc((void **)&d->log_x, per * NX * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&d->log_u, per * NU * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&d->log_c, (size_t)d->B * rounds * sizeof(double)));
+    d->log_rounds = rounds;
+    d->log_steps = steps;
+    return 0;
+}
+
+int ilqg_dev_log_append(ilqg_dev_t *d, int round) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!d->log_x || round < 0 || round >= d->log_rounds) {
+        g_err = "ilqg_dev_log_append: no such round in the log (ilqg_dev_log_begin)";
+        return 1;
+    }
+    {
+        Timed t(d, ILQG_K_LOG);
+        hipLaunchKernelGGL(k_log_steps, grid1((size_t)d->B * d->log_steps * (NX + NU), 256), dim3(256), 0, d->stream, d->P, d->log_x,
+                           d->log_u, d->log_c, round, d->log_rounds, d->log_steps);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!d->log_x) {
+        g_err = "ilqg_dev_log_read: no log (ilqg_dev_log_begin)";
+        return 1;
+    }
+    const size_t per = (size_t)d->B * d->log_rounds * d->log_steps;
+    if(x) HIP_TRY(hipMemcpyAsync(x, d->log_x, per * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(u) HIP_TRY(hipMemcpyAsync(u, d->log_u, per * NU * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(cost) HIP_TRY(hipMemcpyAsync(cost, d->log_c, (size_t)d->B * d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return 0;
 }
 
 #if ILQG_WAVE_MAP

@@ -80,6 +80,23 @@ def _named_list(items):
     return arr, len(items), keep
 
 
+def _optional(a, shape):
+    """an optional array argument: None, or the C-contiguous doubles of that shape"""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(shape)
+
+
+def _address(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _receding_entry(lib, name):
+    """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift of a problem library; one built before they existed (a
+    pair compiled out of tree and not rebuilt since) still loads and solves, and says so when they are asked for"""
+    if not hasattr(lib, name):
+        raise IlqgError("this problem library was built before %s existed: rebuild it (make -C ddp-generator_amd/csrc)" % name)
+    return getattr(lib, name)
+
+
 def load_library(problem="carparking", full_ddp=0, strict=False):
     path = library_path(problem, full_ddp, strict)
     if path in _libs:
@@ -111,6 +128,10 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
     for f in ("init", "solve", "sync", "calc_derivs", "line_search", "update"):
         getattr(lib, "ilqg_batch_" + f).argtypes = [v]
     lib.ilqg_batch_iterate.argtypes = [v, C.c_int]
+    if hasattr(lib, "ilqg_batch_shift"):  # (a library built before the receding-horizon entries: see _receding_entry)
+        lib.ilqg_batch_shift.argtypes = [v, C.c_int, v, v]
+        lib.ilqg_batch_receding.argtypes = [v, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
+        lib.ilqg_multi_shift.argtypes = [v, C.c_int, v, v]
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -236,6 +257,21 @@ class BatchSolver:
 
     def solve(self):
         self._ck(self.lib.ilqg_batch_solve(self.h))
+
+    def shift(self, steps, x0=None, u_tail=None):
+        """receding horizon on the device (ilqg_batch_shift): u'[k] = u[k+steps], tail = u_tail [B,steps,nu] or the last
+        control held, x0' = x0 [B,nx] or the plan's x[steps]; then what init() does.  Problem parameters are left alone."""
+        x0, u_tail = _optional(x0, (self.B, self.problem.nx)), _optional(u_tail, (self.B, max(int(steps), 0), self.problem.nu))
+        self._ck(_receding_entry(self.lib, "ilqg_batch_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
+
+    def receding(self, rounds, steps, iterations):
+        """rounds x { iterate(iterations); record the first `steps` (x, u) of every plan and its cost; shift(steps) }
+        (ilqg_batch_receding): dict(x [B,rounds*steps,nx], u [B,rounds*steps,nu], cost [B,rounds]), copied to the host once"""
+        n = max(int(rounds), 0) * max(int(steps), 0)
+        out = dict(x=np.zeros((self.B, n, self.problem.nx)), u=np.zeros((self.B, n, self.problem.nu)),
+                   cost=np.zeros((self.B, max(int(rounds), 0))))
+        self._ck(_receding_entry(self.lib, "ilqg_batch_receding")(self.h, int(rounds), int(steps), int(iterations), out["x"], out["u"], out["cost"]))
+        return out
 
     def solve_stream(self, x0, u0, with_trajectories=False):
         """a stream of len(x0) starts through this batch's slots (ilqg_batch_solve_stream): dict of cost, status, iterations
@@ -458,6 +494,11 @@ class MultiSolver:
 
     def iterate(self, n=1):
         self._ck(self.lib.ilqg_multi_iterate(self.h, int(n)))
+
+    def shift(self, steps, x0=None, u_tail=None):
+        """BatchSolver.shift on every shard (ilqg_multi_shift)"""
+        x0, u_tail = _optional(x0, (self.B, self.problem.nx)), _optional(u_tail, (self.B, max(int(steps), 0), self.problem.nu))
+        self._ck(_receding_entry(self.lib, "ilqg_multi_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
 
     def solve(self):
         self._ck(self.lib.ilqg_multi_solve(self.h))

@@ -104,6 +104,28 @@ int ilqg_batch_set_u(ilqg_batch_t *c, const double *u /* [B][n_hor][N_U] */);
 int ilqg_batch_set_x(ilqg_batch_t *c, const double *x /* [B][n_hor+1][N_X] */);
 int ilqg_batch_init(ilqg_batch_t *c);
 
+/* Receding horizon, on the device: what the caller of the reference's MEX entry does between two calls — it passes
+ * u_nom = [u(:, s+1:end), tail] and the new x0 (iLQG_mex.c:113-120) — without the trajectories leaving the GPU.  With
+ * (x, u) the current nominal trajectory of every slot, whatever its status:
+ *     u'[k] = u[k + steps] for k < n_hor - steps; the last `steps` controls are u_tail [B][steps][N_U], or u[n_hor-1]
+ *     repeated if u_tail is NULL;  x0' = x0_new [B][N_X], or x[steps] if x0_new is NULL;
+ * then exactly what ilqg_batch_init does: the initial roll-out (clamps u, re-initialises multipliers, may set status 7)
+ * and the solver entry state, so that every trajectory is active again with 0 iterations and lambda = lambdaInit.  Gains
+ * and derivative records are left as ilqg_batch_init leaves them.  0 <= steps < n_hor, anything else is an error;
+ * steps = 0 with both pointers NULL is ilqg_batch_init.  Only x0_new and u_tail cross to the device.
+ * PROBLEM PARAMETERS ARE LEFT ALONE, those with one value per time step (size -1) included: the caller moves their
+ * window with ilqg_batch_set_param before (or after) the shift. */
+int ilqg_batch_shift(ilqg_batch_t *c, int steps, const double *x0_new /* [B][N_X] or NULL */,
+                     const double *u_tail /* [B][steps][N_U] or NULL */);
+/* `rounds` times { ilqg_batch_iterate(c, iterations); record; ilqg_batch_shift(c, steps, NULL, NULL) }: a closed loop on
+ * the model itself.  "record" appends the first `steps` (x_k, u_k) of every plan and its cost to a log on the device,
+ * which reaches the host once, at the end.  1 <= steps < n_hor.  A problem with a per-time-step parameter (size -1) is
+ * refused: its window has to move with the horizon, which is the caller's loop over ilqg_batch_iterate,
+ * ilqg_batch_set_param and ilqg_batch_shift. */
+int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations,
+                        double *x_applied /* [B][rounds*steps][N_X] */, double *u_applied /* [B][rounds*steps][N_U] */,
+                        double *cost /* [B][rounds] */);   /* any output may be NULL */
+
 /* n lock-step iterations of { calc_derivs, back_pass (+ lambda retries),
  * line_search over all alpha, accept/reject } for every still-active trajectory */
 int ilqg_batch_iterate(ilqg_batch_t *c, int n);
@@ -192,6 +214,7 @@ int ilqg_multi_set_param(ilqg_multi_t *m, const char *name, const double *value,
 int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0);
 int ilqg_multi_set_u(ilqg_multi_t *m, const double *u);
 int ilqg_multi_init(ilqg_multi_t *m);
+int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const double *u_tail);  /* ilqg_batch_shift per shard */
 int ilqg_multi_iterate(ilqg_multi_t *m, int n);   /* asynchronous on every device; the devices are served in turn */
 int ilqg_multi_solve(ilqg_multi_t *m);
 int ilqg_multi_sync(ilqg_multi_t *m);
