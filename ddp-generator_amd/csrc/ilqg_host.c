@@ -558,6 +558,96 @@ int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, 
     return 0;
 }
 
+/* The control interval of a caller with its own plant: {iterate; head; the caller's plant step; shift}.  The heads are read
+ * where the plans live (nothing moves home, nothing else changes); the _device forms take and fill device memory of the
+ * caller in the order of ITS stream, by events, and never wait on the host. */
+static int head_steps(ilqg_batch_t *c, const char *who, int steps) {
+    if(steps >= 1 && steps <= c->N) return 0;
+    snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor = %d", who, steps, c->N);
+    return 1;
+}
+#define HEAD_AT(p, w) ((p) ? (p) + (size_t)c->first[g] * steps * (w) : NULL)
+
+int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost) {
+    int g;
+    if(head_steps(c, "ilqg_batch_head", steps)) return 1;
+    EACH_GROUP(g)
+        if(ilqg_dev_head(c->dev[g], steps, HEAD_AT(x, N_X), HEAD_AT(u, N_U), HEAD_AT(l, N_U), HEAD_AT(L, N_U * N_X),
+                         cost ? cost + c->first[g] : NULL))
+            return fail(c, "head");
+    return 0;
+}
+
+int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream) {
+    int g;
+    if(head_steps(c, "ilqg_batch_head_device", steps)) return 1;
+    if((x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) || (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u")) ||
+       (l && ilqg_dev_check_device_ptr(c->dev[0], l, "l")) || (L && ilqg_dev_check_device_ptr(c->dev[0], L, "L")) ||
+       (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")))
+        return fail(c, "ilqg_batch_head_device");
+    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "head: stream");
+    EACH_GROUP(g) {
+        if(ilqg_dev_head_device(c->dev[g], steps, HEAD_AT(x, N_X), HEAD_AT(u, N_U), HEAD_AT(l, N_U), HEAD_AT(L, N_U * N_X),
+                                cost ? cost + c->first[g] : NULL))
+            return fail(c, "head");
+        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "head: stream");
+    }
+    return 0;
+}
+
+int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
+    int g;
+    if(steps < 0 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift_device: steps = %d, must be in 0 .. n_hor - 1 = %d", steps, c->N - 1);
+        return 1;
+    }
+    if((x0_new && ilqg_dev_check_device_ptr(c->dev[0], x0_new, "x0_new")) || (u_tail && ilqg_dev_check_device_ptr(c->dev[0], u_tail, "u_tail")))
+        return fail(c, "ilqg_batch_shift_device");
+    if(push_config(c)) return 1;
+    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "shift: stream");
+    /* the order of ilqg_batch_shift: the shift kernel brings U home and clears the location indices, then the caller's values */
+    EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, x0_new == NULL)) return fail(c, "shift");
+    EACH_GROUP(g) {
+        if(x0_new && ilqg_dev_put_x0_device(c->dev[g], x0_new + (size_t)c->first[g] * N_X)) return fail(c, "shift: x0_new");
+        if(u_tail && steps > 0 && ilqg_dev_put_u_tail_device(c->dev[g], u_tail + (size_t)c->first[g] * steps * N_U, steps))
+            return fail(c, "shift: u_tail");
+        /* behind the last kernel that reads the caller's memory, not behind the roll-out */
+        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift: stream");
+    }
+    EACH_GROUP(g) {
+        if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
+        if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
+    }
+    return 0;
+}
+
+/* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param), and in the host
+ * mirror c->p[i], from which a later ilqg_batch_set_param of another parameter re-pushes the whole table */
+int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const double *tail) {
+    int i, k, g, n;
+    for(i = 0; i < n_params; i++)
+        if(strcmp(paramdesc[i]->name, name) == 0) break;
+    if(i == n_params) {
+        snprintf(c->err, sizeof(c->err), "Parameter name '%s' is not a parameter of this problem.", name);
+        return 1;
+    }
+    if(paramdesc[i]->size != -1) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift_param: parameter name '%s' has a fixed size of %d, not one value per time step "
+                 "(size -1): it has no window to move", name, paramdesc[i]->size);
+        return 1;
+    }
+    if(steps < 0 || steps > c->N) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift_param: steps = %d, must be in 0 .. n_hor = %d", steps, c->N);
+        return 1;
+    }
+    if(steps == 0) return 0;
+    n = c->N + 1;
+    /* the table is on the device (and was pushed from this mirror): move it there, and the mirror with it */
+    if(c->params_pushed) EACH_GROUP(g) if(ilqg_dev_shift_param(c->dev[g], i, steps, tail)) return fail(c, "shift_param");
+    for(k = 0; k < n; k++) c->p[i][k] = k + steps < n ? c->p[i][k + steps] : (tail ? tail[k + steps - n] : c->p[i][n - 1]);
+    return 0;
+}
+
 /* the groups advance alternately, one iteration at a time: their launches interleave on the device */
 static int iterate_groups(ilqg_batch_t *c, int n) {
     int it, g;
@@ -1501,6 +1591,15 @@ int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const dou
     EACH_SHARD(g)
         if(ilqg_batch_shift(m->shard[g], steps, x0_new ? x0_new + (size_t)m->first[g] * N_X : NULL,
                             u_tail ? u_tail + (size_t)m->first[g] * (steps > 0 ? steps : 0) * N_U : NULL))
+            return multi_fail(m, g);
+    return 0;
+}
+int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l, double *L, double *cost) {
+    int g;
+    const size_t s = steps > 0 ? (size_t)steps : 0;
+    EACH_SHARD(g)
+        if(ilqg_batch_head(m->shard[g], steps, x ? x + m->first[g] * s * N_X : NULL, u ? u + m->first[g] * s * N_U : NULL,
+                           l ? l + m->first[g] * s * N_U : NULL, L ? L + m->first[g] * s * N_U * N_X : NULL, cost ? cost + m->first[g] : NULL))
             return multi_fail(m, g);
     return 0;
 }

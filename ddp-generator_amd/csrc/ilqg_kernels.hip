@@ -1034,6 +1034,8 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 
 #include "k_shift.inc"  // k_shift_lane / k_shift_wave, k_put_u_steps, k_log_steps (receding horizon)
 
+#include "k_mpc_io.inc"  // k_head, k_shift_param (the control interval of a caller with its own plant)
+
 }  // namespace
 
 #ifndef ILQG_ONLY_KERNEL

@@ -117,6 +117,8 @@ enum {
     ILQG_K_ADOPT,    /*             k_adopt_home / k_rejected_home, k_commit */
     ILQG_K_SHIFT,    /* receding horizon: k_shift_lane / k_shift_wave (ilqg_dev_shift) */
     ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_log_append) */
+    ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head, ilqg_dev_head_device) */
+    ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
     ILQG_K_COUNT
 };
 
@@ -173,6 +175,28 @@ int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps);
 int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps);
 int ilqg_dev_log_append(ilqg_dev_t *d, int round);
 int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost);
+/* The control interval of a caller with its own plant.  head: the first `steps` steps of every CURRENT plan, read where it
+ * lives (nothing moves home), trajectory-major: x [batch][steps][N_X], u / l [batch][steps][N_U], L [batch][steps][N_U*N_X],
+ * cost [batch]; any pointer may be NULL; 1 <= steps <= n_hor.  ilqg_dev_head fills host arrays (one wait at most),
+ * ilqg_dev_head_device writes device memory of the caller on the context's stream and waits for nothing. */
+int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost);
+int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost);
+/* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) / ilqg_dev_write_u_tail with the source in DEVICE memory: no staging, no wait */
+int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0);
+int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps);
+/* Ordering with a stream of the caller (a hipStream_t, NULL = the null stream), by events made once per context: after
+ * stream_in the context's stream runs behind everything enqueued on `stream` so far; after stream_out `stream` runs behind
+ * everything enqueued on the context's stream so far.  Neither waits on the host. */
+int ilqg_dev_stream_in(ilqg_dev_t *d, void *stream);
+int ilqg_dev_stream_out(ilqg_dev_t *d, void *stream);
+/* 0 if [ptr, ...) is device memory on the context's device, else 1 with a message that names `what` */
+int ilqg_dev_check_device_ptr(ilqg_dev_t *d, const void *ptr, const char *what);
+/* The window of per-time-step parameter `index` (its n_hor + 1 doubles on the device) moves `steps` values on, in place:
+ * p'[k] = p[k + steps], the last `steps` from tail [steps] (host) or p[n_hor] held if tail is NULL; 0 <= steps <= n_hor.
+ * Needs ilqg_dev_set_params before it.  (Wave mapping: the constant record entries are marked stale as
+ * ilqg_dev_set_params marks them; no wave-mapped problem with such a parameter is built in this tree, so that path is
+ * untested.) */
+int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail);
 int ilqg_dev_derivs(ilqg_dev_t *d);           /* calc_derivs for trajectories that need it */
 /* back_pass.  mode 0: records from HBM + lambda retry loop + gradient test; 1: records from HBM, one
  * sweep (drop-in back_pass()); 2: as 0 with the derivatives evaluated on the fly (no k_derivs needed) */

@@ -81,6 +81,7 @@ struct ilqg_dev {
     bool per_step_params;       // some problem parameter has one value per time step
     double *log_x, *log_u, *log_c;  // receding horizon: the applied steps of every round (ilqg_dev_log_begin), host layout
     int log_rounds, log_steps;
+    hipEvent_t ext_in, ext_out;  // ordering with a stream of the caller (ilqg_dev_stream_in / _out), made with the context
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
     struct EnvSwitches { bool no_quad, quad_stored, two_pieces, deriv_parts, no_dma, no_rollout_parts, quad_spec; } env;
@@ -346,7 +347,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
-                                              "k_log_steps"};
+                                              "k_log_steps", "k_head", "k_shift_param"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -398,6 +399,8 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
     d->P.Bp = d->Bp;
     d->P.N = d->N;
     HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&d->ext_in, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&d->ext_out, hipEventDisableTiming));
     d->env.no_quad = getenv("ILQG_NO_QUAD") != nullptr;
     // stored tensors in the quad mapping (ilqg_quad.hpp): measured behind the row mapping at config 5 (1.66-1.71 against 1.82
     // iterations/s, profiles/r6_stored_path.txt — both kernels share the HBM with k_derivs_wave of the other half of the
@@ -617,6 +620,8 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
     if(d->roll_in) hipEventDestroy(d->roll_in);
     if(d->roll_out) hipEventDestroy(d->roll_out);
     if(d->epoch) hipEventDestroy(d->epoch);
+    if(d->ext_in) hipEventDestroy(d->ext_in);
+    if(d->ext_out) hipEventDestroy(d->ext_out);
     delete d;
 }
 
@@ -1105,6 +1110,142 @@ int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost) {
     if(cost) HIP_TRY(hipMemcpyAsync(cost, d->log_c, (size_t)d->B * d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The control interval of a caller with its own plant (k_mpc_io.inc)
+// ---------------------------------------------------------------------------------------------------------------------
+static int launch_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost) {
+    const int tiles = (x ? (steps * NX + 7) / 8 : 0) + ((u ? 1 : 0) + (l ? 1 : 0)) * ((steps * NU + 7) / 8) + (L ? (steps * NXU + 7) / 8 : 0);
+    const int gy = tiles > 0 ? (tiles + HEAD_WAVES - 1) / HEAD_WAVES : 1;
+    {
+        Timed t(d, ILQG_K_HEAD);
+        hipLaunchKernelGGL(k_head, dim3((unsigned)((d->B + 7) / 8), (unsigned)gy), dim3(WAVE * HEAD_WAVES), 0, d->stream, d->P, steps, x, u, l, L, cost);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int head_steps_ok(ilqg_dev_t *d, int steps) {
+    if(steps >= 1 && steps <= d->N) return 1;
+    g_err = "head: steps must be in 1 .. n_hor";
+    return 0;
+}
+
+int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!head_steps_ok(d, steps)) return 1;
+    if(!x && !u && !l && !L && !cost) return 0;
+    return launch_head(d, steps, x, u, l, L, cost);
+}
+
+int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!head_steps_ok(d, steps)) return 1;
+    double *const host[5] = {x, u, l, L, cost};
+    const size_t per[5] = {(size_t)steps * NX, (size_t)steps * NU, (size_t)steps * NU, (size_t)steps * NXU, 1};
+    size_t off[5], total = 0;
+    for(int i = 0; i < 5; i++) {
+        off[i] = total;
+        if(host[i]) total += ((size_t)d->B * per[i] + 31) & ~(size_t)31;  // slices 256 bytes apart
+    }
+    if(total == 0) return 0;
+    void *dev, *pin;
+    if(stage(d, total * sizeof(double), &dev, &pin)) return 1;
+    double *dv[5];
+    for(int i = 0; i < 5; i++) dv[i] = host[i] ? (double *)dev + off[i] : nullptr;
+    if(launch_head(d, steps, dv[0], dv[1], dv[2], dv[3], dv[4])) return 1;
+    for(int i = 0; i < 5; i++) {
+        if(!host[i]) continue;
+        const size_t bytes = (size_t)d->B * per[i] * sizeof(double);
+        void *to = pin ? (void *)((double *)pin + off[i]) : (void *)host[i];
+        HIP_TRY(hipMemcpyAsync(to, dv[i], bytes, hipMemcpyDeviceToHost, d->stream));
+        if(pin) d->pending.push_back({host[i], to, bytes, 0});
+    }
+    if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
+    return 0;
+}
+
+int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(all_home(d)) return 1;  // (behind ilqg_dev_shift nothing is left to move)
+    const size_t n = (size_t)d->B * NX;
+    {
+        Timed t(d, ILQG_K_TRANSPOSE);
+        hipLaunchKernelGGL(k_nom_io, grid1(n, 256), dim3(256), 0, d->stream, d->P.nom, const_cast<double *>(x0), d->B, d->N, 1, NX, NOM_X, 1);
+        if(!WAVE_MAP) hipLaunchKernelGGL(k_to_dev, grid1(n, 256), dim3(256), 0, d->stream, x0, d->P.f[ILQG_F_X], d->B, d->Bp, 1, NX, NX);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(steps < 1 || steps > d->N) {
+        g_err = "ilqg_dev_put_u_tail_device: bad step count";
+        return 1;
+    }
+    if(all_home(d)) return 1;
+    {
+        Timed t(d, ILQG_K_TRANSPOSE);
+        hipLaunchKernelGGL(k_put_u_steps, grid1((size_t)d->B * steps * NU, 256), dim3(256), 0, d->stream, d->P, tail, d->N - steps, steps);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ilqg_dev_stream_in(ilqg_dev_t *d, void *stream) {
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipEventRecord(d->ext_in, (hipStream_t)stream));
+    HIP_TRY(hipStreamWaitEvent(d->stream, d->ext_in, 0));
+    return 0;
+}
+int ilqg_dev_stream_out(ilqg_dev_t *d, void *stream) {
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipEventRecord(d->ext_out, d->stream));
+    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, d->ext_out, 0));
+    return 0;
+}
+
+int ilqg_dev_check_device_ptr(ilqg_dev_t *d, const void *ptr, const char *what) {
+    HIP_TRY(hipSetDevice(d->device));
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    const hipError_t e = hipPointerGetAttributes(&a, ptr);
+    if(e != hipSuccess) (void)hipGetLastError();  // (memory the runtime does not know: plain host memory)
+    if(e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != d->device) {
+        g_err = std::string(what) + " must point to device memory on the context's device";
+        return 1;
+    }
+    return 0;
+}
+
+int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    constexpr int want[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+    if(index < 0 || index >= ILQG_NP || index >= (int)d->param_bufs.size() || want[index] != -1) {
+        g_err = "ilqg_dev_shift_param: not a parameter with one value per time step";
+        return 1;
+    }
+    if(steps < 0 || steps > d->N) {
+        g_err = "ilqg_dev_shift_param: steps must be in 0 .. n_hor";
+        return 1;
+    }
+    if(steps == 0) return 0;
+    const double *tail_dev = nullptr;
+    if(tail) {
+        void *dev, *pin;
+        if(stage(d, (size_t)steps * sizeof(double), &dev, &pin)) return 1;
+        if(stage_in(d, dev, pin, tail, (size_t)steps * sizeof(double))) return 1;
+        tail_dev = (const double *)dev;
+    }
+    {
+        Timed t(d, ILQG_K_SHIFT_PARAM);
+        hipLaunchKernelGGL(k_shift_param, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index], d->N + 1, steps, tail_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
+    return tail ? io_done(d) : 0;
 }
 
 #if ILQG_WAVE_MAP

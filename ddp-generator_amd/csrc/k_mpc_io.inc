@@ -1,0 +1,73 @@
+// The control interval of a caller with its OWN plant (ilqg_dev_head*, ilqg_dev_put_*_device, ilqg_dev_shift_param): the
+// first steps of every plan leave the solver's layouts for trajectory-major arrays, and the window of a per-time-step
+// parameter moves with the horizon, without a field or a table crossing to the host.  No arithmetic.  The device-source
+// forms of the x0 / tail writes are the existing k_nom_io, k_to_dev and k_put_u_steps fed from the caller's pointer.
+
+// k_head: x_k, u_k, l_k, L_k for k < steps and the cost of every CURRENT plan into x [B][steps][NX], u [B][steps][NU],
+// l [B][steps][NU], L [B][steps][NXU] (column-major per step, as the host getter), cost [B]; any pointer may be null.
+// x / u are read where the current trajectory lives (cur_x / cur_u: the tiled X / U or a kept roll-out plane in the lane
+// mapping, the packed records in the wave mapping), l / L from the packed records in both mappings (what the host
+// getters read, has_tiled_scratch).
+//
+// Thread-to-element map.  The two sides want opposite orders: the tiled arrays are contiguous along the TRAJECTORY (one
+// (step, component) of 8 consecutive trajectories is one 64-byte segment), the outputs — and the records — along the
+// COMPONENT (for one trajectory the q = k * w + c, q < steps * w, are consecutive doubles).  Neither is favoured: a
+// wavefront takes a block of 8 trajectories x 8 consecutive q, the trajectory on the low three lane bits.  Every tiled read
+// of the wavefront is then a whole 64-byte segment (8 lanes each), and every write a run of 8 doubles = 64 bytes per
+// trajectory (for steps * w < 8, e.g. CarParking's x with steps = 1, runs of w doubles that are adjacent from one
+// trajectory to the next: the 8 trajectories' 256 bytes are contiguous); reads from the records are runs of up to 64 bytes
+// too.  A map with the trajectory fastest over the whole wavefront (k_log_steps) would write one double per 64-byte
+// segment for the 16 x 8 problem; one with the component fastest would read the tiled arrays that way.  The price is
+// idle lanes where steps * w < 8, on a kernel that moves a few bytes per trajectory.
+// Grid: x = blocks of 8 trajectories, y = groups of HEAD_WAVES tiles of 8 q over the four fields one behind the other.
+constexpr int HEAD_WAVES = 4;
+__global__ void __launch_bounds__(WAVE * HEAD_WAVES) k_head(DevPtrs P, int steps, double *__restrict__ ox, double *__restrict__ ou,
+                                                          double *__restrict__ ol, double *__restrict__ oL, double *__restrict__ oc) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int b = (int)blockIdx.x * 8 + (lane & 7);
+    int tile = (int)blockIdx.y * HEAD_WAVES + (int)(threadIdx.x >> 6);  // wave-uniform
+    if(oc && blockIdx.y == 0 && threadIdx.x < 8 && b < P.B) oc[b] = P.f[ILQG_F_COST][b];
+    if(b >= P.B) return;
+    const int tx = ox ? (steps * NX + 7) / 8 : 0, tu = ou ? (steps * NU + 7) / 8 : 0, tl = ol ? (steps * NU + 7) / 8 : 0,
+              tL = oL ? (steps * NXU + 7) / 8 : 0;
+    if(tile < tx) {
+        const int q = tile * 8 + (lane >> 3);
+        if(q < steps * NX) ox[(size_t)b * steps * NX + q] = cur_x(P, q / NX, b)[(size_t)(q % NX) * XSI];
+        return;
+    }
+    tile -= tx;
+    if(tile < tu) {
+        const int q = tile * 8 + (lane >> 3);
+        if(q < steps * NU) ou[(size_t)b * steps * NU + q] = cur_u(P, q / NU, b)[(size_t)(q % NU) * XSI];
+        return;
+    }
+    tile -= tu;
+    if(tile < tl) {
+        const int q = tile * 8 + (lane >> 3);
+        if(q < steps * NU) ol[(size_t)b * steps * NU + q] = nomp(P, q / NU, b)[NOM_L + q % NU];
+        return;
+    }
+    tile -= tl;
+    if(tile < tL) {
+        const int q = tile * 8 + (lane >> 3);
+        if(q < steps * NXU) oL[(size_t)b * steps * NXU + q] = nomp(P, q / NXU, b)[NOM_K + q % NXU];
+    }
+}
+
+// The window of ONE per-time-step parameter (n = n_hor + 1 doubles in global memory, param_bufs) moves `steps` values
+// on, in place: p'[k] = p[k + steps], the last `steps` values from tail [steps] or, with tail null, p[n - 1] held.  One
+// workgroup, ascending blocks of its size: all loads of a block, a barrier, its stores (the pattern of k_shift_wave: a
+// block reads [k0 + steps, k0 + block + steps) and writes [k0, k0 + block), the blocks before it wrote nothing beyond
+// k0; p[n - 1], which a null tail repeats, is written by the last block alone, behind that block's reads).
+constexpr int PARAM_BLOCK = 256;
+__global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param(double *__restrict__ p, int n, int steps, const double *__restrict__ tail) {
+    const int t = (int)threadIdx.x;
+    if(steps <= 0) return;
+    for(int k0 = 0; k0 < n; k0 += PARAM_BLOCK) {
+        const int k = k0 + t, from = k + steps;
+        double v = 0.0;
+        if(k < n) v = from < n ? p[from] : (tail ? tail[from - n] : p[n - 1]);
+        __syncthreads();
+        if(k < n) p[k] = v;
+    }
+}

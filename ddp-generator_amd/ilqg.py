@@ -12,6 +12,7 @@ error messages (iLQG.c:91-216).
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -89,12 +90,74 @@ def _address(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _is_cuda(a):
+    """a torch tensor in GPU memory (asked of the object: torch is not imported for the question)"""
+    return bool(getattr(a, "is_cuda", False))
+
+
+def _cuda_address(a, shape, device, what):
+    """the device address of an optional CUDA tensor argument, which must be what the library reads as it is: float64,
+    contiguous, of the documented shape, on the solver's device.  Checked here, before any library call."""
+    if a is None:
+        return None
+    if "float64" not in str(a.dtype):
+        raise IlqgError("%s: a tensor on the device must be float64, not %s" % (what, a.dtype))
+    if tuple(a.shape) != tuple(shape):
+        raise IlqgError("%s: shape %s, expected %s" % (what, tuple(a.shape), tuple(shape)))
+    if not a.is_contiguous():
+        raise IlqgError("%s: a tensor on the device must be contiguous" % what)
+    if a.device.index != device:
+        raise IlqgError("%s: on %s, the solver is on GPU %d" % (what, a.device, device))
+    return C.c_void_p(a.data_ptr() or None)
+
+
+def _head_arrays(B, steps, nx, nu, gains):
+    n = max(int(steps), 0)
+    out = dict(x=np.zeros((B, n, nx)), u=np.zeros((B, n, nu)), cost=np.zeros(B))
+    if gains:
+        out.update(l=np.zeros((B, n, nu)), L=np.zeros((B, n, nu * nx)))
+    return out
+
+
 def _receding_entry(lib, name):
-    """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift of a problem library; one built before they existed (a
-    pair compiled out of tree and not rebuilt since) still loads and solves, and says so when they are asked for"""
+    """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift, and ilqg_batch_head / _head_device / _shift_device /
+    _shift_param / ilqg_multi_head, of a problem library; one built before they existed (a pair compiled out of tree and
+    not rebuilt since) still loads and solves, and says so when they are asked for"""
     if not hasattr(lib, name):
         raise IlqgError("this problem library was built before %s existed: rebuild it (make -C ddp-generator_amd/csrc)" % name)
     return getattr(lib, name)
+
+
+def _share_hip_runtime():
+    """Device tensors of torch and the solver's memory and streams must belong to ONE HIP runtime, and a torch wheel may
+    bring a copy of its own beside the one the problem libraries are linked with: two runtimes in one process know nothing
+    of each other's allocations and streams.  Where torch has NOT been imported yet, the runtime the first problem library
+    brought is made visible to everything loaded later (its scope is widened, nothing else is loaded), so a torch
+    imported afterwards — BatchSolver.head(device=True) and shift() with a CUDA tensor import it themselves — runs on the
+    same runtime as the solver.  Where torch was imported first nothing is touched: the loader then serves the problem
+    library with the runtime torch brought where the two carry the same soname (seen with torch 2.10+rocm7.0 beside ROCm
+    7.2), and where it does not, the device entries refuse torch's pointers with a message instead of reading them."""
+    if "torch" in sys.modules:
+        return
+    try:
+        with open("/proc/self/maps") as f:
+            paths = sorted({line.split()[-1] for line in f if "libamdhip64" in line})
+    except OSError:
+        return
+    for p in paths:
+        try:
+            C.CDLL(p, mode=C.RTLD_GLOBAL)
+        except OSError:
+            pass
+
+
+def _torch_on_gpu():
+    """torch, for the device forms of head() / shift(): imported here and nowhere else"""
+    import torch
+    if not torch.cuda.is_available():
+        raise IlqgError("torch sees no GPU in this process: torch and the solver must share one HIP runtime, which they do "
+                        "when torch is first imported after the first solver has been made (see ilqg._share_hip_runtime)")
+    return torch
 
 
 def load_library(problem="carparking", full_ddp=0, strict=False):
@@ -105,6 +168,8 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         raise IlqgError("HIP library %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(make -C ddp-generator_amd/csrc). There is no CPU fallback." % path)
     lib = C.CDLL(path)
+    if not _libs:
+        _share_hip_runtime()
     v = C.c_void_p
     lib.ilqg_problem_dims.argtypes = [_ip]
     lib.ilqg_problem_param_name.restype = C.c_char_p
@@ -132,6 +197,12 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_shift.argtypes = [v, C.c_int, v, v]
         lib.ilqg_batch_receding.argtypes = [v, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
         lib.ilqg_multi_shift.argtypes = [v, C.c_int, v, v]
+    if hasattr(lib, "ilqg_batch_head"):  # (the same for the entries of a caller with its own plant)
+        lib.ilqg_batch_head.argtypes = [v, C.c_int, v, v, v, v, v]
+        lib.ilqg_batch_head_device.argtypes = [v, C.c_int, v, v, v, v, v, v]
+        lib.ilqg_batch_shift_device.argtypes = [v, C.c_int, v, v, v]
+        lib.ilqg_batch_shift_param.argtypes = [v, C.c_char_p, C.c_int, v]
+        lib.ilqg_multi_head.argtypes = [v, C.c_int, v, v, v, v, v]
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -209,7 +280,7 @@ class BatchSolver:
         (0 = the library's choice, see ilqg_batch_create_groups)"""
         self.problem = Problem(problem, full_ddp, strict)
         self.lib = self.problem.lib
-        self.B, self.N = int(batch), int(n_hor)
+        self.B, self.N, self.device = int(batch), int(n_hor), int(device)
         self.h = self.lib.ilqg_batch_create_groups(int(device), self.B, self.N, int(groups))
         if not self.h:
             raise IlqgError(self.lib.ilqg_batch_error(None).decode())
@@ -260,9 +331,55 @@ class BatchSolver:
 
     def shift(self, steps, x0=None, u_tail=None):
         """receding horizon on the device (ilqg_batch_shift): u'[k] = u[k+steps], tail = u_tail [B,steps,nu] or the last
-        control held, x0' = x0 [B,nx] or the plan's x[steps]; then what init() does.  Problem parameters are left alone."""
-        x0, u_tail = _optional(x0, (self.B, self.problem.nx)), _optional(u_tail, (self.B, max(int(steps), 0), self.problem.nu))
+        control held, x0' = x0 [B,nx] or the plan's x[steps]; then what init() does.  Problem parameters are left alone
+        (shift_param moves the window of one with a value per time step).
+        x0 / u_tail as CUDA torch tensors (float64, contiguous, on the solver's GPU) are read where they are, in the order
+        of torch's current stream, without a host copy or a host wait (ilqg_batch_shift_device); both or neither."""
+        nx, nu, n = self.problem.nx, self.problem.nu, max(int(steps), 0)
+        if _is_cuda(x0) or _is_cuda(u_tail):
+            for what, a in (("x0", x0), ("u_tail", u_tail)):
+                if a is not None and not _is_cuda(a):
+                    raise IlqgError("shift: %s is in host memory and the other argument on the device: pass both the same way" % what)
+            px, pt = _cuda_address(x0, (self.B, nx), self.device, "x0"), _cuda_address(u_tail, (self.B, n, nu), self.device, "u_tail")
+            entry = _receding_entry(self.lib, "ilqg_batch_shift_device")
+            torch = _torch_on_gpu()
+            stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+            self._ck(entry(self.h, int(steps), px, pt, C.c_void_p(stream or None)))
+            return
+        x0, u_tail = _optional(x0, (self.B, nx)), _optional(u_tail, (self.B, n, nu))
         self._ck(_receding_entry(self.lib, "ilqg_batch_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
+
+    def head(self, steps, gains=False, device=False):
+        """the first `steps` steps of every current plan, read where it lives (nothing in the batch changes):
+        dict(x [B,steps,nx] = x_0 .. x_{steps-1}, u [B,steps,nu], cost [B]) and, with gains, l [B,steps,nu] and
+        L [B,steps,nu*nx] (each step column-major, as gains()).  numpy arrays (ilqg_batch_head), or with device=True
+        float64 torch tensors on the solver's GPU, filled in the order of torch's current stream without a host wait
+        (ilqg_batch_head_device)."""
+        nx, nu = self.problem.nx, self.problem.nu
+        if not device:
+            out = _head_arrays(self.B, steps, nx, nu, gains)
+            self._ck(_receding_entry(self.lib, "ilqg_batch_head")(self.h, int(steps), *[_address(out.get(k)) for k in ("x", "u", "l", "L", "cost")]))
+            return out
+        entry = _receding_entry(self.lib, "ilqg_batch_head_device")
+        torch = _torch_on_gpu()
+        dev, n = torch.device("cuda", self.device), max(int(steps), 0)
+        shapes = dict(x=(self.B, n, nx), u=(self.B, n, nu), cost=(self.B,))
+        if gains:
+            shapes.update(l=(self.B, n, nu), L=(self.B, n, nu * nx))
+        out = {k: torch.empty(shape, dtype=torch.float64, device=dev) for k, shape in shapes.items()}
+        ptr = [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in ("x", "u", "l", "L", "cost")]
+        self._ck(entry(self.h, int(steps), *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+        return out
+
+    def shift_param(self, name, steps, tail=None):
+        """the window of ONE per-time-step parameter moves `steps` values on (ilqg_batch_shift_param): p'[k] = p[k+steps],
+        the last `steps` values from tail [steps], or the last value held; what set_param(name, [p[steps:], tail]) gives
+        without sending the table again"""
+        if tail is not None:
+            tail = np.ascontiguousarray(tail, dtype=np.float64)
+            if tail.shape != (max(int(steps), 0),):
+                raise IlqgError("shift_param: tail has shape %s, expected (%d,) = (steps,)" % (tail.shape, max(int(steps), 0)))
+        self._ck(_receding_entry(self.lib, "ilqg_batch_shift_param")(self.h, name.encode(), int(steps), _address(tail)))
 
     def receding(self, rounds, steps, iterations):
         """rounds x { iterate(iterations); record the first `steps` (x, u) of every plan and its cost; shift(steps) }
@@ -499,6 +616,12 @@ class MultiSolver:
         """BatchSolver.shift on every shard (ilqg_multi_shift)"""
         x0, u_tail = _optional(x0, (self.B, self.problem.nx)), _optional(u_tail, (self.B, max(int(steps), 0), self.problem.nu))
         self._ck(_receding_entry(self.lib, "ilqg_multi_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
+
+    def head(self, steps, gains=False):
+        """BatchSolver.head of every shard (ilqg_multi_head), numpy arrays"""
+        out = _head_arrays(self.B, steps, self.problem.nx, self.problem.nu, gains)
+        self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *[_address(out.get(k)) for k in ("x", "u", "l", "L", "cost")]))
+        return out
 
     def solve(self):
         self._ck(self.lib.ilqg_multi_solve(self.h))

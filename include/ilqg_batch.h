@@ -126,6 +126,36 @@ int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations,
                         double *x_applied /* [B][rounds*steps][N_X] */, double *u_applied /* [B][rounds*steps][N_U] */,
                         double *cost /* [B][rounds] */);   /* any output may be NULL */
 
+/* A control interval with the caller's OWN plant (a simulator, a learned model, hardware) is
+ *     ilqg_batch_iterate;  ilqg_batch_head*;  the plant's step;  ilqg_batch_shift*  (and ilqg_batch_shift_param)
+ * and none of it needs a whole field on the host.
+ *
+ * The first `steps` steps of every CURRENT plan, wherever it lives (a kept roll-out plane of the line search included),
+ * trajectory-major: x [B][steps][N_X] (x_0 .. x_{steps-1}), u [B][steps][N_U], l [B][steps][N_U],
+ * L [B][steps][N_U*N_X] (each step column-major, as ilqg_batch_get_gains), cost [B].  Any pointer may be NULL.
+ * 1 <= steps <= n_hor.  Changes nothing in the batch (in particular it does not move trajectories home).
+ * ilqg_batch_head fills host memory and waits once per group of trajectories; it moves steps * (N_X + N_U + ...) doubles
+ * per trajectory, not whole fields.  ilqg_batch_head_device fills DEVICE memory of the context's device.
+ *
+ * Stream contract of the two _device entries: `stream` is the caller's hipStream_t (NULL = the null stream, handled like
+ * any other: by events).  Work that produces the inputs has been enqueued on it; the outputs are consumed on it.  On
+ * entry the library records an event on `stream` and lets its own streams wait for it; behind the last kernel that
+ * touches the caller's memory (the gather of the heads; the scatter of x0_new / u_tail, NOT the initial roll-out) it
+ * records an event per group of trajectories and lets `stream` wait for it.  The host waits for nothing, copies nothing
+ * and allocates nothing in steady state.  Pointers that are not device memory on the context's device are refused and
+ * the batch is left untouched. */
+int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost);
+int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream);
+/* ilqg_batch_shift with x0_new / u_tail in DEVICE memory of the context's device (same layouts, same NULL meanings) */
+int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream);
+/* The window of ONE per-time-step parameter (size -1) moves `steps` values on: p'[k] = p[k + steps], the last `steps`
+ * values from tail [steps] (host), or p[n_hor] held if tail is NULL.  0 <= steps <= n_hor.  Exactly what
+ * ilqg_batch_set_param(c, name, [p[steps:], tail], n_hor + 1) gives, without re-allocating or re-sending the table: the
+ * values move in place on the device, and in the host copy a later ilqg_batch_set_param of another parameter re-sends.
+ * (Wave-mapped problems: written as the full re-send implies, but no such problem with a per-time-step parameter is
+ * built in this tree, so that path is untested.) */
+int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const double *tail /* [steps] or NULL */);
+
 /* n lock-step iterations of { calc_derivs, back_pass (+ lambda retries),
  * line_search over all alpha, accept/reject } for every still-active trajectory */
 int ilqg_batch_iterate(ilqg_batch_t *c, int n);
@@ -215,6 +245,7 @@ int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0);
 int ilqg_multi_set_u(ilqg_multi_t *m, const double *u);
 int ilqg_multi_init(ilqg_multi_t *m);
 int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const double *u_tail);  /* ilqg_batch_shift per shard */
+int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l, double *L, double *cost);  /* ilqg_batch_head per shard */
 int ilqg_multi_iterate(ilqg_multi_t *m, int n);   /* asynchronous on every device; the devices are served in turn */
 int ilqg_multi_solve(ilqg_multi_t *m);
 int ilqg_multi_sync(ilqg_multi_t *m);

@@ -2,11 +2,19 @@
 """Receding-horizon re-plan: on the device (BatchSolver.shift) against through the host (x(), u(), a numpy shift, init()).
 
     python tools/receding_profile.py [--config headline|config5|both] [--repeats 10] [--steps 10] [--warmup 20]
+    python tools/receding_profile.py --loop external [--config ...] [--repeats 10] [--steps 1] [--iterations 2]
 
 One process per invocation.  After `--warmup` iterations the two re-plans ALTERNATE; each is timed by the host clock
 between two device synchronisations, and two solver iterations run between re-plans so that every one of them finds the
 batch as a control loop would (lane mapping: current trajectories in the kept roll-out planes of the line search).  The
 new kernels' own times are HIP events (ilqg_batch_get_timing).  Not part of bench.py.
+
+--loop external: one control interval of a caller with its OWN plant, {iterate(k); read what is applied; plant; shift with
+the measured state}, in the forms a caller has — through whole fields on the host (u(), with or without x(), and a host
+x_meas) and with the heads and x_meas staying on the GPU as torch tensors (head(device=True), shift(cuda tensor)).  The
+plant is trivial: x_meas = x[steps] of the plan + noise (a random walk of x_meas where the form does not read x).  The
+forms ALTERNATE in one process.  Per form and repeat two host-clock figures between two device synchronisations: the
+whole interval with nothing waited for inside it, and what comes behind iterate() alone (the overhead).
 """
 import argparse
 import os
@@ -81,11 +89,100 @@ def run(ilqg, synth, config, repeats, steps, warmup, between):
     s.close()
 
 
+def run_external(ilqg, synth, config, repeats, steps, warmup, iterations):
+    import torch
+    if config == "headline":
+        problem, fd, B, N, params = "carparking", 0, 65536, 500, ilqg.CAR_PARAMS
+        x0, u0 = synth.car_batch(B, N)
+    else:
+        problem, fd, B, N, params = "synth16x8", 1, 16384, 1000, synth.SYNTH16_PARAMS
+        x0, u0 = synth.synth16_batch(B, N)
+    s = ilqg.BatchSolver(problem, fd, batch=B, n_hor=N, params=params, opts=dict(max_iter=1 << 20))
+    nx, nu = s.problem.nx, s.problem.nu
+    print("== %s: %s FULL_DDP=%d, %d trajectories, N = %d, %d step(s) applied per interval, %d iteration(s) per interval, %d stream group(s), %s mapping" % (
+        config, problem, fd, B, N, steps, iterations, s.groups(), "wave" if s.problem.wave_mapping else "lane"))
+    rng = np.random.default_rng(1)
+    noise = 1e-3 * rng.standard_normal((B, nx))
+    noise_t = torch.from_numpy(noise).cuda()
+    walk = [np.array(x0, dtype=np.float64)]
+    applied = {}
+
+    def host_u():  # the parent's form without the states: the plant cannot see the plan's x[steps]
+        applied["u"] = s.u()[:, :steps]
+        walk[0] = walk[0] + noise
+        s.shift(steps, walk[0])
+
+    def host_xu():  # the parent's form with the plant of the device form
+        applied["u"] = s.u()[:, :steps]
+        s.shift(steps, s.x()[:, steps] + noise)
+
+    def device():
+        h = s.head(steps + 1, device=True)
+        applied["u"] = h["u"][:, :steps]
+        s.shift(steps, h["x"][:, steps] + noise_t)
+
+    forms = (("host: u(), shift(x_meas on the host)", host_u), ("host: u(), x(), shift(x_meas on the host)", host_xu),
+             ("device: head(device=True), shift(x_meas on the GPU)", device))
+
+    def sync():
+        torch.cuda.synchronize()
+        s.sync()
+
+    s.init(x0, u0)
+    s.iterate(warmup)
+    for _, f in forms:  # once untimed: staging buffers, torch's allocator
+        s.iterate(iterations)
+        f()
+    sync()
+    s.timing(True)
+    whole, over = {n: [] for n, _ in forms}, {n: [] for n, _ in forms}
+    layout, seen = {n: [0, 0.0] for n, _ in forms}, [0, 0.0]  # "layout kernels" per form: read between the timed regions
+    for r in range(repeats):
+        for name, f in forms:
+            sync()
+            t0 = time.perf_counter()
+            s.iterate(iterations)
+            f()
+            sync()
+            whole[name].append(1e3 * (time.perf_counter() - t0))
+            s.iterate(iterations)
+            sync()
+            t0 = time.perf_counter()
+            f()
+            sync()
+            over[name].append(1e3 * (time.perf_counter() - t0))
+            n, ms = s.kernel_times()["layout kernels"]
+            layout[name][0] += n - seen[0]
+            layout[name][1] += ms - seen[1]
+            seen = [n, ms]
+    kt = s.kernel_times()
+    s.timing(False)
+    for name, _ in forms:
+        print("%-52s interval  %s" % (name, spread(whole[name])))
+        print("%-52s overhead  %s" % ("", spread(over[name])))
+    dev = forms[2][0]
+    for name, _ in forms[:2]:
+        print("ratio of medians, %s / device: interval %.2f, overhead %.1f" % (
+            name.split(",")[0] + ("+x()" if "x()" in name else ""), np.median(whole[name]) / np.median(whole[dev]), np.median(over[name]) / np.median(over[dev])))
+    n, ms = kt["k_head"]
+    print("k_head: %d launches, %.4f ms per launch (%d bytes per trajectory out)" % (n, ms / max(n, 1), ((steps + 1) * nx + (steps + 1) * nu + 1) * 8))
+    for name, _ in forms:  # device form: the scatter of x0_new (k_nom_io, k_to_dev); host forms: the transposes of u(), x(), x0_new
+        n, ms = layout[name]
+        print("layout kernels, %-52s %d launches, %.4f ms per control interval (sum over the groups)" % (name + ":", n, ms / (2 * repeats)))
+    n, ms = kt["k_shift"]
+    print("k_shift: %d launches, %.3f ms per launch; k_rollout[init]: %.3f ms per launch (every form)" % (
+        n, ms / max(n, 1), kt["k_rollout[init]"][1] / max(kt["k_rollout[init]"][0], 1)))
+    print("through the host per interval: u() %.2f GB, x() %.2f GB; device form: nothing" % (B * N * nu * 8 / 1e9, B * (N + 1) * nx * 8 / 1e9))
+    s.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both", choices=("headline", "config5", "both"))
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="steps per shift (default 10; 1 with --loop external)")
+    ap.add_argument("--loop", default="replan", choices=("replan", "external"), help="external: the control interval of a caller with its own plant")
+    ap.add_argument("--iterations", type=int, default=2, help="--loop external: solver iterations per control interval")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--between", type=int, default=2, help="solver iterations between two re-plans")
     a = ap.parse_args()
@@ -93,7 +190,10 @@ def main():
     g.load_package()
     from ddp_generator_amd import ilqg, synth
     for config in (("headline", "config5") if a.config == "both" else (a.config,)):
-        run(ilqg, synth, config, a.repeats, a.steps, a.warmup, a.between)
+        if a.loop == "external":
+            run_external(ilqg, synth, config, a.repeats, a.steps or 1, a.warmup, a.iterations)
+        else:
+            run(ilqg, synth, config, a.repeats, a.steps or 10, a.warmup, a.between)
 
 
 if __name__ == "__main__":
