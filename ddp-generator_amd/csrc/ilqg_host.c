@@ -595,6 +595,55 @@ int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, dou
     return 0;
 }
 
+/* Every plan's feedback policy rolled out from n_starts starts per trajectory (k_policy.inc): what a late measurement, a
+ * Monte-Carlo robustness estimate or a comparison of feedback with open-loop replay asks, without x, u, l, L of the batch
+ * crossing to the host.  Reads the policy where ilqg_batch_head reads it and writes nothing of the batch. */
+static int policy_args(ilqg_batch_t *c, const char *who, int n_starts, const double *x0) {
+    if(n_starts < 1) {
+        snprintf(c->err, sizeof(c->err), "%s: n_starts = %d, must be at least 1", who, n_starts);
+        return 1;
+    }
+    if(!x0) {
+        snprintf(c->err, sizeof(c->err), "%s: x0 is NULL (the starts, [B][n_starts][N_X])", who);
+        return 1;
+    }
+    return 0;
+}
+#define POLICY_AT(p, w) ((p) ? (p) + (size_t)c->first[g] * (size_t)n_starts * (w) : NULL)
+
+int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                              double *x_end, double *x, double *u) {
+    int g;
+    if(policy_args(c, "ilqg_batch_policy_rollout", n_starts, x0)) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    if(push_config(c)) return 1;
+    EACH_GROUP(g)
+        if(ilqg_dev_policy_rollout_host(c->dev[g], n_starts, POLICY_AT(x0, N_X), alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1),
+                                        POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
+            return fail(c, "policy_rollout");
+    return 0;
+}
+
+int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                                     double *x_end, double *x, double *u, void *stream) {
+    int g;
+    if(policy_args(c, "ilqg_batch_policy_rollout_device", n_starts, x0)) return 1;
+    if(ilqg_dev_check_device_ptr(c->dev[0], x0, "x0") || (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")) ||
+       (ok && ilqg_dev_check_device_ptr(c->dev[0], ok, "ok")) || (x_end && ilqg_dev_check_device_ptr(c->dev[0], x_end, "x_end")) ||
+       (x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) || (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u")))
+        return fail(c, "ilqg_batch_policy_rollout_device");
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    if(push_config(c)) return 1;
+    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "policy_rollout: stream");
+    EACH_GROUP(g) {
+        if(ilqg_dev_policy_rollout(c->dev[g], n_starts, POLICY_AT(x0, N_X), alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1),
+                                   POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
+            return fail(c, "policy_rollout");
+        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "policy_rollout: stream");
+    }
+    return 0;
+}
+
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
     int g;
     if(steps < 0 || steps >= c->N) {
@@ -1601,6 +1650,19 @@ int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l,
         if(ilqg_batch_head(m->shard[g], steps, x ? x + m->first[g] * s * N_X : NULL, u ? u + m->first[g] * s * N_U : NULL,
                            l ? l + m->first[g] * s * N_U : NULL, L ? L + m->first[g] * s * N_U * N_X : NULL, cost ? cost + m->first[g] : NULL))
             return multi_fail(m, g);
+    return 0;
+}
+int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                              double *x_end, double *x, double *u) {
+    int g;
+    const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
+    EACH_SHARD(g) {
+        const size_t at = (size_t)m->first[g] * r;
+        if(ilqg_batch_policy_rollout(m->shard[g], n_starts, x0 ? x0 + at * N_X : NULL, alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL,
+                                     x_end ? x_end + at * N_X : NULL, x ? x + at * (size_t)(m->N + 1) * N_X : NULL,
+                                     u ? u + at * (size_t)m->N * N_U : NULL))
+            return multi_fail(m, g);
+    }
     return 0;
 }
 int ilqg_multi_init(ilqg_multi_t *m) {

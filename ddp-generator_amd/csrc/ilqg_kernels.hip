@@ -18,6 +18,7 @@
 //   k_rollout    lane = (traj, alpha)  forward_pass           iLQG_func.tem:121-185
 //   k_select     lane = traj           line_search selection  line_search.c:37-75
 //   k_update     lane = traj           accept / reject        iLQG.c:311-361
+//   k_policy     lane = (traj, start)  forward_pass from the caller's starts, nothing stored in the batch
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -1035,6 +1036,8 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 #include "k_shift.inc"  // k_shift_lane / k_shift_wave, k_put_u_steps, k_log_steps (receding horizon)
 
 #include "k_mpc_io.inc"  // k_head, k_shift_param (the control interval of a caller with its own plant)
+
+#include "k_policy.inc"  // k_policy (roll-outs of every plan's feedback policy from the caller's starts)
 
 }  // namespace
 

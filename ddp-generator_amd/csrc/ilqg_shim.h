@@ -119,6 +119,7 @@ enum {
     ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_log_append) */
     ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head, ilqg_dev_head_device) */
     ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
+    ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
     ILQG_K_COUNT
 };
 
@@ -181,6 +182,19 @@ int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost);
  * ilqg_dev_head_device writes device memory of the caller on the context's stream and waits for nothing. */
 int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost);
 int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost);
+/* Every plan's feedback policy rolled out from R starts per trajectory (k_policy.inc): forward_pass with the caller's start
+ * as x0, the nominal = what ilqg_dev_head hands out (current x / u where they live, l / L of the records), the multipliers
+ * and penalty weights the trajectory has, and u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if feedback].
+ * x0 [batch][R][N_X]; outputs, any of them NULL: cost [batch][R], ok [batch][R] (forward_pass's return value; where it is 0
+ * the other outputs of that roll-out are unspecified), x_end [batch][R][N_X], x [batch][R][n_hor+1][N_X],
+ * u [batch][R][n_hor][N_U] (the clamped controls applied).  Writes nothing of the solver's state.  ilqg_dev_policy_rollout
+ * takes DEVICE memory, is asynchronous on the context's stream and waits for nothing; ilqg_dev_policy_rollout_host takes
+ * host memory, stages through the context's staging buffer (which only grows) and waits once.  R >= 1; needs
+ * ilqg_dev_set_params before it. */
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                            double *x_end, double *x, double *u);
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                                 double *x_end, double *x, double *u);
 /* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) / ilqg_dev_write_u_tail with the source in DEVICE memory: no staging, no wait */
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0);
 int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps);

@@ -347,7 +347,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
-                                              "k_log_steps", "k_head", "k_shift_param"};
+                                              "k_log_steps", "k_head", "k_shift_param", "k_policy"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -1160,6 +1160,79 @@ int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, dou
         void *to = pin ? (void *)((double *)pin + off[i]) : (void *)host[i];
         HIP_TRY(hipMemcpyAsync(to, dv[i], bytes, hipMemcpyDeviceToHost, d->stream));
         if(pin) d->pending.push_back({host[i], to, bytes, 0});
+    }
+    if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Roll-outs of the policy from the caller's starts (k_policy.inc).  On the stream of the roll-out family: in the wave
+// mapping the kernel keeps a trajEl_t per lane in scratch memory like every scalar roll-out (see `roll`).
+// ---------------------------------------------------------------------------------------------------------------------
+static int policy_args_ok(ilqg_dev_t *d, int R, const double *x0) {
+    if(R < 1) {
+        g_err = "policy_rollout: n_starts must be at least 1";
+        return 0;
+    }
+    if(!x0) {
+        g_err = "policy_rollout: x0 is NULL";
+        return 0;
+    }
+    if(((size_t)d->B * (size_t)R + ROLL_BLOCK - 1) / ROLL_BLOCK > (size_t)0x7fffffff) {
+        g_err = "policy_rollout: n_starts is too large for one launch";
+        return 0;
+    }
+    return 1;
+}
+static int launch_policy(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok, double *x_end,
+                         double *x, double *u) {
+    if(roll_enter(d)) return 1;
+    {
+        Timed t(d, ILQG_K_POLICY, roll_stream(d));
+        hipLaunchKernelGGL(k_policy, grid1((size_t)d->B * (size_t)R, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha,
+                           feedback ? 1 : 0, cost, ok, x_end, x, u);
+    }
+    HIP_TRY(hipGetLastError());
+    return roll_leave(d);
+}
+
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                            double *x_end, double *x, double *u) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    if(!policy_args_ok(d, R, x0)) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    return launch_policy(d, R, x0, alpha, feedback, cost, ok, x_end, x, u);
+}
+
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                                 double *x_end, double *x, double *u) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    if(!policy_args_ok(d, R, x0)) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    const size_t n = (size_t)d->B * (size_t)R;
+    void *const host[5] = {cost, ok, x_end, x, u};
+    const size_t bytes[5] = {n * sizeof(double), n * sizeof(int), n * NX * sizeof(double), n * (size_t)(d->N + 1) * NX * sizeof(double),
+                             n * (size_t)d->N * NU * sizeof(double)};
+    const size_t in_bytes = n * NX * sizeof(double);
+    size_t off[5], total = (in_bytes + 255) & ~(size_t)255;  // slices 256 bytes apart, the starts first
+    for(int i = 0; i < 5; i++) {
+        off[i] = total;
+        if(host[i]) total += (bytes[i] + 255) & ~(size_t)255;
+    }
+    void *dev, *pin;
+    if(stage(d, total, &dev, &pin)) return 1;
+    if(stage_in(d, dev, pin, x0, in_bytes)) return 1;
+    void *dv[5];
+    for(int i = 0; i < 5; i++) dv[i] = host[i] ? (void *)((char *)dev + off[i]) : nullptr;
+    if(launch_policy(d, R, (const double *)dev, alpha, feedback, (double *)dv[0], (int *)dv[1], (double *)dv[2], (double *)dv[3], (double *)dv[4]))
+        return 1;
+    for(int i = 0; i < 5; i++) {
+        if(!host[i]) continue;
+        void *to = pin ? (void *)((char *)pin + off[i]) : host[i];
+        HIP_TRY(hipMemcpyAsync(to, dv[i], bytes[i], hipMemcpyDeviceToHost, d->stream));
+        if(pin) d->pending.push_back({host[i], to, bytes[i], 0});
     }
     if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
     return 0;

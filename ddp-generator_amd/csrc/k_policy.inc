@@ -1,0 +1,209 @@
+// Roll-outs of every plan's feedback policy from starts of the caller (ilqg_dev_policy_rollout).  Included by
+// ilqg_kernels.hip inside its anonymous namespace, behind k_rollout.inc (NomStep, NomPtrs, ROLL_BLOCK).
+//
+// k_policy: forward_pass (iLQG_func.tem:121-185) with o->x0 = the caller's start, the nominal = the POLICY of slot b —
+// what k_head hands out: the current (x, u) where it lives (cur_x / cur_u: the tiled X / U, a kept roll-out plane of the
+// line search, the records in the wave mapping) and the gains l, L of the packed records — the multipliers and penalty
+// weights slot b has now, the per-time-step parameters as they stand, and
+//     u_k = u_nom_k  [+ alpha l_k  if alpha != 0]  [+ L_k (x_k - x_nom_k)  if feedback, state by state in the template's order]
+// then the step of the template: calcXVariableAux, clampU, calcXUVariableAux, ddpf, ddpL; the final step calcFVariableAux,
+// ddpF.  The step itself, the huge-argument second pass of sin / cos and, in builds with wave-uniform guards, run_guarded
+// are k_rollout's, statement by statement.  NOTHING of the batch is written: no field, scalar, status, location index or
+// multiplier, and no trajectory moves home.
+//
+// Lanes.  One lane per roll-out, roll-out g = b * R + r with r fastest: R consecutive lanes share slot b and so every
+// address of the nominal data.  A load instruction of a wavefront touches the data of at most ceil(64 / R) + 1 slots
+// (lanes with equal addresses are served by one request), for R >= 64 of one or two, for R a multiple of 64 of exactly one.
+// The next step's nominal data are requested while the step computes (k_rollout's scheme: loaded into the variables the
+// step has just consumed); in the wave mapping L is too large to hold a step ahead and is read where it is used, as
+// k_rollout does.  What alpha / feedback do not need is not loaded (l for alpha == 0; x_nom and L without feedback):
+// both are kernel arguments, the branches are scalar ones.
+//
+// Outputs, all optional (null = not wanted): cost [B][R], ok [B][R] (forward_pass's return value: 0 as soon as a guarded
+// value is NaN or Inf; the other outputs of such a roll-out are unspecified), x_end [B][R][NX], and the whole roll-out
+// x [B][R][N+1][NX], u [B][R][N][NU] (u = the CLAMPED control that was applied).  x / u are trajectory-major per
+// roll-out, so a lane's stores of a step are scattered 8-byte pieces, 64 cache lines per store instruction: accepted,
+// because they are optional — the costs-only call does not pay for them (one wave-uniform branch per step, no store).
+// A roll-out whose start is not finite ends at once with ok = 0.  All indices over B * R are size_t.
+__device__ __forceinline__ void load_policy_step(NomStep &s, const NomPtrs &q, bool use_l, bool use_K) {
+#pragma unroll
+    for(int i = 0; i < NU; i++) s.u[i] = q.u[i * XSI];
+    if(use_l) {
+#pragma unroll
+        for(int i = 0; i < NU; i++) s.l[i] = q.l[i];
+    }
+    if(use_K) {
+#pragma unroll
+        for(int i = 0; i < NX; i++) s.x[i] = q.x[i * XSI];
+        if(!WAVE_MAP) {
+#pragma unroll
+            for(int i = 0; i < NXU; i++) s.K[i] = q.K[i];
+        }
+    }
+}
+
+__global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
+                                                                         double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
+                                                                         double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou) {
+    const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
+    if(g >= (size_t)P.B * (size_t)R) return;
+    const int b = (int)(g / (size_t)R);
+    const int N = P.N;
+    const bool use_l = (alpha != 0.0), use_K = (feedback != 0);
+
+    double xc[NX];
+    bool finite = true;
+#pragma unroll
+    for(int i = 0; i < NX; i++) {
+        xc[i] = x0[g * NX + i];  // o->x0 (iLQG_func.tem:141-142)
+        finite &= (__builtin_fabs(xc[i]) < __builtin_inf());
+    }
+    if(!finite) {
+        if(ook) ook[g] = 0;
+        if(ocost) ocost[g] = __builtin_nan("");
+        return;
+    }
+
+    ILQG_CALLBACKS(C, H);
+    load_penalty_weights(C, P, b);
+    el_t ct;
+    multipliersEl_t mk;
+    multipliersEl_t *const mp = HAS_MUL ? &mk : nullptr;
+#if ILQG_DEV_EL
+    ilqgdev::set_mode(ilqgdev::DISCARD);
+    [[clang::always_inline]]  // (see k_rollout)
+#endif
+    init_running(&ct, &C.o1);
+
+    NomPtrs q;
+    q.x = cur_x(P, 0, b);
+    q.u = cur_u(P, 0, b);
+    q.l = nomp(P, 0, b) + NOM_L;
+    q.K = nomp(P, 0, b) + NOM_K;
+    const size_t xs = cur_xstride(P), us = cur_ustride(P);
+    constexpr int ks = RN;
+    size_t xat = g * (size_t)(N + 1) * NX, uat = g * (size_t)N * NU;  // this roll-out's step in x / u
+
+    double csum = 0.0;
+    int okc = 1;
+    NomStep cur = {};
+    load_policy_step(cur, q, use_l, use_K);
+    drain_memory_ops();
+    for(int k = 0; k < N; k++) {
+        NomPtrs qn;
+        qn.x = q.x + xs;
+        qn.u = q.u + us;
+        qn.l = q.l + ks;
+        qn.K = q.K + ks;
+        double xin[NX], uin[NU];
+#pragma unroll
+        for(int i = 0; i < NX; i++) xin[i] = xc[i];
+#pragma unroll
+        for(int j = 0; j < NU; j++) uin[j] = cur.u[j];
+        if(use_l) {
+#pragma unroll
+            for(int j = 0; j < NU; j++) uin[j] = cur.u[j] + cur.l[j] * alpha;
+        }
+        if(use_K) {
+#pragma unroll
+            for(int i = 0; i < NX; i++) {
+                const double dx = xin[i] - cur.x[i];
+                if(WAVE_MAP) {
+                    const double *Kk = q.K + i * NU;
+#pragma unroll
+                    for(int j = 0; j < NU; j++) uin[j] += Kk[j] * dx;
+                } else {
+#pragma unroll
+                    for(int j = 0; j < NU; j++) uin[j] += cur.K[j + i * NU] * dx;
+                }
+            }
+        }
+
+        // the next step's nominal data, in flight while the step computes (the records have a step N; the tiled U has not)
+        if(k + 1 >= N) qn.u = q.u;
+        load_policy_step(cur, qn, use_l, use_K);
+
+        if(HAS_MUL) load_mul(P, k, b, mk);
+        double xnext[NX];
+        const double nf0 = H.nonfinite;
+        H.huge = 0.0;
+        auto step = [&]() {
+#pragma unroll
+            for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
+#pragma unroll
+            for(int j = 0; j < NU; j++) ct.u[j] = uin[j];
+            int r = calcXVariableAux(&ct, mp, k, &C.o);
+            clampU(ct.u, &ct, k, C.o.p, N);
+            r &= calcXUVariableAux(&ct, mp, k, &C.o);
+            r &= ddpf(xnext, &ct, k, C.o.p, N);
+            r &= ddpL(&ct, k, &C.o);
+            return r;
+        };
+        int r = 1;
+#if ILQG_UNIFORM_GUARDS
+        if(okc) r = run_guarded(step);
+#else
+        r = step();
+        if(H.huge != 0.0) {
+            H.nonfinite = nf0;
+            H.slow = 1.0;
+            r = step();
+            H.slow = 0.0;
+        }
+#endif
+        okc &= r;
+        csum += ct.c;
+        if(ox) {
+#pragma unroll
+            for(int i = 0; i < NX; i++) ox[xat + i] = ct.x[i];
+            xat += NX;
+        }
+        if(ou) {
+#pragma unroll
+            for(int i = 0; i < NU; i++) ou[uat + i] = ct.u[i];
+            uat += NU;
+        }
+#pragma unroll
+        for(int i = 0; i < NX; i++) xc[i] = xnext[i];
+        q = qn;
+    }
+    {
+        trajFin_t cf;
+        multipliersFin_t mf;
+        if(HAS_MUL) load_mul_fin(P, b, mf);
+        init_final(&cf, &C.o);
+        const double nf0 = H.nonfinite;
+        H.huge = 0.0;
+        auto fin = [&]() {
+#pragma unroll
+            for(int i = 0; i < NX; i++) cf.x[i] = xc[i];
+            int r = calcFVariableAux(&cf, HAS_MUL ? &mf : nullptr, &C.o);
+            r &= ddpF(&cf, &C.o);
+            return r;
+        };
+        int r = 1;
+#if ILQG_UNIFORM_GUARDS
+        if(okc) r = run_guarded(fin);
+#else
+        r = fin();
+        if(H.huge != 0.0) {
+            H.nonfinite = nf0;
+            H.slow = 1.0;
+            r = fin();
+            H.slow = 0.0;
+        }
+#endif
+        okc &= r;
+        csum += cf.c;
+        if(ox) {
+#pragma unroll
+            for(int i = 0; i < NX; i++) ox[xat + i] = cf.x[i];
+        }
+        if(oxe) {
+#pragma unroll
+            for(int i = 0; i < NX; i++) oxe[g * NX + i] = cf.x[i];
+        }
+    }
+    if(ocost) ocost[g] = csum;
+    if(ook) ook[g] = (okc && H.nonfinite == 0.0) ? 1 : 0;
+}

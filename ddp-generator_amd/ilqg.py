@@ -119,9 +119,19 @@ def _head_arrays(B, steps, nx, nu, gains):
     return out
 
 
+def _policy_starts(x0, B, nx):
+    """the starts of policy_rollout as [B, R, nx] C-contiguous doubles: given so, or as [R, nx] for every trajectory"""
+    a = np.asarray(x0, dtype=np.float64)
+    if a.ndim == 2 and a.shape[1] == nx:
+        a = np.broadcast_to(a, (B,) + a.shape)
+    if a.ndim != 3 or a.shape[0] != B or a.shape[2] != nx or a.shape[1] < 1:
+        raise IlqgError("policy_rollout: x0 has shape %s, expected (%d, R, %d) or (R, %d) with n_starts = R >= 1" % (tuple(a.shape), B, nx, nx))
+    return np.ascontiguousarray(a)
+
+
 def _receding_entry(lib, name):
-    """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift, and ilqg_batch_head / _head_device / _shift_device /
-    _shift_param / ilqg_multi_head, of a problem library; one built before they existed (a pair compiled out of tree and
+    """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift, ilqg_batch_head / _head_device / _shift_device /
+    _shift_param / ilqg_multi_head, and ilqg_batch_policy_rollout / _policy_rollout_device / ilqg_multi_policy_rollout, of a problem library; one built before they existed (a pair compiled out of tree and
     not rebuilt since) still loads and solves, and says so when they are asked for"""
     if not hasattr(lib, name):
         raise IlqgError("this problem library was built before %s existed: rebuild it (make -C ddp-generator_amd/csrc)" % name)
@@ -203,6 +213,10 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_shift_device.argtypes = [v, C.c_int, v, v, v]
         lib.ilqg_batch_shift_param.argtypes = [v, C.c_char_p, C.c_int, v]
         lib.ilqg_multi_head.argtypes = [v, C.c_int, v, v, v, v, v]
+    if hasattr(lib, "ilqg_batch_policy_rollout"):  # (and for the roll-outs of the policy)
+        lib.ilqg_batch_policy_rollout.argtypes = [v, C.c_int, v, C.c_double, C.c_int, v, v, v, v, v]
+        lib.ilqg_batch_policy_rollout_device.argtypes = [v, C.c_int, v, C.c_double, C.c_int, v, v, v, v, v, v]
+        lib.ilqg_multi_policy_rollout.argtypes = [v, C.c_int, v, C.c_double, C.c_int, v, v, v, v, v]
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -369,6 +383,45 @@ class BatchSolver:
         out = {k: torch.empty(shape, dtype=torch.float64, device=dev) for k, shape in shapes.items()}
         ptr = [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in ("x", "u", "l", "L", "cost")]
         self._ck(entry(self.h, int(steps), *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+        return out
+
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False):
+        """every plan's feedback policy rolled out from R starts per trajectory on the GPU (ilqg_batch_policy_rollout):
+        x0 [B,R,nx], or [R,nx] for every trajectory; u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if
+        feedback], clamped, through the problem's dynamics and cost.  The policy is what head(N, gains=True) returns — behind
+        an accepted step its gains were computed about the PREVIOUS nominal trajectory; nothing in the batch changes.
+        dict(cost [B,R], ok [B,R] int32 (0: a value was NaN / Inf, the roll-out's other outputs are unspecified),
+        x_end [B,R,nx]) and with trajectories x [B,R,N+1,nx], u [B,R,N,nu] (the clamped controls applied).
+        numpy arrays, or with device=True a float64 torch tensor [B,R,nx] on the solver's GPU in and torch tensors out, in
+        the order of torch's current stream without a host wait (ilqg_batch_policy_rollout_device)."""
+        nx, nu, B, N = self.problem.nx, self.problem.nu, self.B, self.N
+        order = ("cost", "ok", "x_end", "x", "u")
+        if not device:
+            if _is_cuda(x0):
+                raise IlqgError("policy_rollout: x0 is a tensor on the device: pass device=True")
+            x0 = _policy_starts(x0, B, nx)
+            R = x0.shape[1]
+            out = dict(cost=np.zeros((B, R)), ok=np.zeros((B, R), dtype=np.int32), x_end=np.zeros((B, R, nx)))
+            if trajectories:
+                out.update(x=np.zeros((B, R, N + 1, nx)), u=np.zeros((B, R, N, nu)))
+            self._ck(_receding_entry(self.lib, "ilqg_batch_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
+                                                                            *[_address(out.get(k)) for k in order]))
+            return out
+        if not _is_cuda(x0):
+            raise IlqgError("policy_rollout: device=True and x0 is in host memory: pass a float64 torch tensor on the solver's GPU")
+        if len(x0.shape) != 3 or int(x0.shape[1]) < 1:
+            raise IlqgError("policy_rollout: x0 has shape %s, expected (%d, R, %d) with n_starts = R >= 1" % (tuple(x0.shape), B, nx))
+        R = int(x0.shape[1])
+        px = _cuda_address(x0, (B, R, nx), self.device, "x0")
+        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_device")
+        torch = _torch_on_gpu()
+        dev = torch.device("cuda", self.device)
+        out = dict(cost=torch.empty((B, R), dtype=torch.float64, device=dev), ok=torch.empty((B, R), dtype=torch.int32, device=dev),
+                   x_end=torch.empty((B, R, nx), dtype=torch.float64, device=dev))
+        if trajectories:
+            out.update(x=torch.empty((B, R, N + 1, nx), dtype=torch.float64, device=dev), u=torch.empty((B, R, N, nu), dtype=torch.float64, device=dev))
+        ptr = [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in order]
+        self._ck(entry(self.h, R, px, float(alpha), 1 if feedback else 0, *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
         return out
 
     def shift_param(self, name, steps, tail=None):
@@ -621,6 +674,18 @@ class MultiSolver:
         """BatchSolver.head of every shard (ilqg_multi_head), numpy arrays"""
         out = _head_arrays(self.B, steps, self.problem.nx, self.problem.nu, gains)
         self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *[_address(out.get(k)) for k in ("x", "u", "l", "L", "cost")]))
+        return out
+
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False):
+        """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout), numpy arrays"""
+        nx, nu, B, N = self.problem.nx, self.problem.nu, self.B, self.N
+        x0 = _policy_starts(x0, B, nx)
+        R = x0.shape[1]
+        out = dict(cost=np.zeros((B, R)), ok=np.zeros((B, R), dtype=np.int32), x_end=np.zeros((B, R, nx)))
+        if trajectories:
+            out.update(x=np.zeros((B, R, N + 1, nx)), u=np.zeros((B, R, N, nu)))
+        self._ck(_receding_entry(self.lib, "ilqg_multi_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
+                                                                        *[_address(out.get(k)) for k in ("cost", "ok", "x_end", "x", "u")]))
         return out
 
     def solve(self):

@@ -148,6 +148,35 @@ int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l,
 int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream);
 /* ilqg_batch_shift with x0_new / u_tail in DEVICE memory of the context's device (same layouts, same NULL meanings) */
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream);
+/* Every plan's feedback POLICY rolled out from n_starts starts per trajectory, on the device (one lane per roll-out).
+ *
+ * The policy of trajectory b is what ilqg_batch_head(c, n_hor, x, u, l, L, NULL) returns for it: the current trajectory,
+ * read where it lives, and the gains stored with it.  A trajectory's status does not matter.  BEHIND AN ACCEPTED STEP THE
+ * STORED GAINS WERE COMPUTED ABOUT THE PREVIOUS NOMINAL TRAJECTORY (the backward pass runs before the line search that
+ * moves the trajectory) — this is what a caller applies today from ilqg_batch_head; right after a backward pass
+ * (ilqg_batch_back_pass, or an iteration whose step was rejected) the gains are exact.
+ *
+ * For start s = x0[b][r] the reference's forward_pass (iLQG_func.tem:121-185) runs with o->x0 = s, the nominal = the
+ * policy, the multipliers and penalty weights trajectory b has now, the per-time-step parameters as they stand, and
+ *     u_k = u_nom_k  [+ alpha * l_k  if alpha != 0]  [+ L_k (x_k - x_nom_k)  if feedback]
+ * then calcXVariableAux, clampU, calcXUVariableAux, ddpf, ddpL per step and calcFVariableAux, ddpF at the end:
+ *     feedback = 1, alpha != 0   the reference's forward_pass(alpha)
+ *     feedback = 0, alpha  = 0   the reference's forward_pass(0): open-loop replay from another start
+ *     feedback = 1, alpha  = 0   the pure feedback law u_nom + L dx
+ *     feedback = 0, alpha != 0   the feed-forward step alone
+ * x0 [B][n_starts][N_X].  Outputs, any of them NULL: cost [B][n_starts]; ok [B][n_starts] = forward_pass's return value
+ * (1, or 0 as soon as a guarded value is NaN or Inf — then cost and the trajectory of that roll-out are unspecified);
+ * x_end [B][n_starts][N_X]; the whole roll-out x [B][n_starts][n_hor+1][N_X], u [B][n_starts][n_hor][N_U] (u is the
+ * clamped control that was applied).  NOTHING in the batch changes.  n_starts >= 1 and x0 != NULL, else an error; all
+ * outputs NULL is a no-op.
+ * ilqg_batch_policy_rollout takes host memory, stages through device buffers of the context that only grow, and waits once
+ * per group of trajectories.  ilqg_batch_policy_rollout_device takes DEVICE memory of the context's device under the
+ * stream contract of ilqg_batch_head_device above (event in, one event per group out, no host wait); pointers are checked
+ * before anything is launched. */
+int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                              double *x_end, double *x, double *u);
+int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                                     double *x_end, double *x, double *u, void *stream);
 /* The window of ONE per-time-step parameter (size -1) moves `steps` values on: p'[k] = p[k + steps], the last `steps`
  * values from tail [steps] (host), or p[n_hor] held if tail is NULL.  0 <= steps <= n_hor.  Exactly what
  * ilqg_batch_set_param(c, name, [p[steps:], tail], n_hor + 1) gives, without re-allocating or re-sending the table: the
@@ -246,6 +275,8 @@ int ilqg_multi_set_u(ilqg_multi_t *m, const double *u);
 int ilqg_multi_init(ilqg_multi_t *m);
 int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const double *u_tail);  /* ilqg_batch_shift per shard */
 int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l, double *L, double *cost);  /* ilqg_batch_head per shard */
+int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                              double *x_end, double *x, double *u);  /* ilqg_batch_policy_rollout per shard (host memory) */
 int ilqg_multi_iterate(ilqg_multi_t *m, int n);   /* asynchronous on every device; the devices are served in turn */
 int ilqg_multi_solve(ilqg_multi_t *m);
 int ilqg_multi_sync(ilqg_multi_t *m);

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Roll-outs of the policy from perturbed starts (BatchSolver.policy_rollout, k_policy) against the line search's roll-outs.
+
+    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search]
+
+One process per invocation, one stream group (a launch's HIP-event time is then that launch alone).  The yardstick is the
+line search of the SAME run with ls_keep = 0, ls_split = 0: k_rollout[search] rolls out (active trajectories) x n_alpha
+chains with the same arithmetic per step, one lane per roll-out, and keeps the costs only.  After `--warmup` iterations
+the legs ALTERNATE, `--repeats` times: one solver iteration (its search launch is the yardstick), costs-only roll-outs of
+the policy at every R of --rs, whole roll-outs at R = 8 (device form: the outputs stay on the GPU), and R = 8 costs-only
+through the host form against the device form (host clock between two device synchronisations).  Kernel times are HIP
+events (ilqg_batch_get_timing), read before and after every leg.  Not part of bench.py.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def spread(v, unit="ms"):
+    v = np.asarray(v, dtype=np.float64)
+    return "median %10.4f %s  min %10.4f  max %10.4f  (n = %d)" % (np.median(v), unit, v.min(), v.max(), len(v))
+
+
+def run(ilqg, synth, config, repeats, warmup, rs, scalar_search):
+    import torch
+    if scalar_search:  # (read once, when the context is made)
+        os.environ["ILQG_NO_ROLLOUT_PARTS"] = "1"
+    else:
+        os.environ.pop("ILQG_NO_ROLLOUT_PARTS", None)
+    if config == "headline":
+        problem, fd, B, N, params = "carparking", 0, 65536, 500, ilqg.CAR_PARAMS
+        x0, u0 = synth.car_batch(B, N)
+    else:
+        problem, fd, B, N, params = "synth16x8", 1, 16384, 1000, synth.SYNTH16_PARAMS
+        x0, u0 = synth.synth16_batch(B, N)
+    s = ilqg.BatchSolver(problem, fd, batch=B, n_hor=N, params=params, opts=dict(max_iter=1 << 20, ls_keep=0, ls_split=0), groups=1)
+    nx, nu = s.problem.nx, s.problem.nu
+    print("== %s: %s FULL_DDP=%d, %d trajectories, N = %d, %d stream group(s), %s mapping, ls_keep = 0, ls_split = 0%s" % (
+        config, problem, fd, B, N, s.groups(), "wave" if s.problem.wave_mapping else "lane",
+        ", ILQG_NO_ROLLOUT_PARTS=1 (the search on k_rollout, one lane per roll-out, where the build has the step in parts)" if scalar_search else ""), flush=True)
+    s.init(x0, u0)
+    s.iterate(warmup)
+    s.sync()
+    rng = np.random.default_rng(3)
+    plan_x0 = s.head(1)["x"][:, 0]
+    rmax = max(rs + [8])
+    starts = torch.from_numpy(plan_x0[:, None, :] + 0.1 * rng.standard_normal((B, rmax, nx))).cuda()
+    dev_starts = {R: starts[:, :R].contiguous() for R in set(rs + [8])}
+    host8 = dev_starts[8].cpu().numpy()
+
+    def sync():
+        torch.cuda.synchronize()
+        s.sync()
+
+    def kernel(name):
+        n, ms = s.kernel_times().get(name, (0, 0.0))
+        return n, ms
+
+    legs = [("search", None)] + [("costs R=%d" % R, R) for R in rs] + [("whole R=8", 8), ("host R=8", 8), ("device R=8", 8)]
+
+    def leg(name, R):
+        if name == "search":
+            s.iterate(1)
+        elif name.startswith("costs") or name.startswith("device"):
+            s.policy_rollout(dev_starts[R], device=True)
+        elif name.startswith("whole"):
+            s.policy_rollout(dev_starts[R], trajectories=True, device=True)
+        else:
+            s.policy_rollout(host8)
+
+    for name, R in legs:  # once untimed: staging buffers, torch's allocator, scratch memory
+        t0 = time.perf_counter()
+        leg(name, R)
+        sync()
+        print("   (untimed first call, %-12s %9.1f ms of wall clock)" % (name + ":", 1e3 * (time.perf_counter() - t0)), flush=True)
+    s.timing(True)
+    kern = {name: [] for name, _ in legs}   # ms per launch of the leg's kernel
+    wall = {name: [] for name, _ in legs}   # host clock between two synchronisations
+    per = {name: [] for name, _ in legs}    # ns per roll-out
+    actives = []
+    n_alpha = 8  # standard_parameters (iLQG.c:74): no option of this run changes the list of step sizes
+    for r in range(repeats):
+        for name, R in legs:
+            which = "k_rollout[search]" if name == "search" else "k_policy"
+            active = s.active() if name == "search" else B
+            sync()
+            n0, ms0 = kernel(which)
+            t0 = time.perf_counter()
+            leg(name, R)
+            sync()
+            wall[name].append(1e3 * (time.perf_counter() - t0))
+            n1, ms1 = kernel(which)
+            kern[name].append((ms1 - ms0) / max(n1 - n0, 1))
+            if name == "search":
+                rollouts = active * n_alpha
+                actives.append(active)
+            else:
+                rollouts = B * R
+            per[name].append(1e6 * (ms1 - ms0) / max(rollouts, 1))
+    s.timing(False)
+    print("the searches rolled out %d .. %d active trajectories x %d step sizes" % (min(actives), max(actives), n_alpha))
+    for name, R in legs:
+        which = "k_rollout[search]" if name == "search" else "k_policy"
+        print("%-12s %-18s per launch   %s" % (name, which, spread(kern[name])))
+        print("%-12s %-18s per roll-out %s" % ("", "", spread(per[name], "ns")))
+    base = np.median(per["search"])
+    lo, hi = np.min(per["search"]), np.max(per["search"])
+    for name, R in legs[1:len(rs) + 2]:
+        m = np.median(per[name])
+        print("ratio per roll-out, k_policy %-10s / k_rollout[search]: %.3f  (medians; the search's own repeats span %.3f .. %.3f of its median, k_policy's %.3f .. %.3f of its)" % (
+            name, m / base, lo / base, hi / base, np.min(per[name]) / m, np.max(per[name]) / m))
+    print("host form R=8, host clock:    " + spread(wall["host R=8"]))
+    print("device form R=8, host clock:  " + spread(wall["device R=8"]))
+    print("ratio of medians host / device form: %.2f  (host form: %.1f MB of starts up, %.1f MB of results down per call)" % (
+        np.median(wall["host R=8"]) / np.median(wall["device R=8"]), B * 8 * nx * 8 / 1e6, B * 8 * (8 + 4 + nx * 8) / 1e6))
+    print("whole roll-outs at R=8 write %.2f GB per call (x and u, scattered 8-byte stores per lane)" % (B * 8 * ((N + 1) * nx + N * nu) * 8 / 1e9))
+    s.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="both", choices=("headline", "config5", "both"))
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rs", default="1,8,64")
+    ap.add_argument("--scalar-search", action="store_true", help="wave-mapped builds whose line search rolls out in parts (k_rollout_parts, "
+                    "several wavefronts per 64 trajectories): the search on k_rollout instead, one lane per roll-out like k_policy")
+    a = ap.parse_args()
+    import __graft_entry__ as g
+    g.load_package()
+    from ddp_generator_amd import ilqg, synth
+    for config in (("headline", "config5") if a.config == "both" else (a.config,)):
+        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search)
+
+
+if __name__ == "__main__":
+    main()
