@@ -644,6 +644,96 @@ int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double
     return 0;
 }
 
+/* The same roll-outs, roll-out (b, r) under a parameter set of its own (k_policy<true>): the batch's fixed-size parameters
+ * with those of names[] replaced by row (b, r) of values.  The names are resolved here against paramdesc[] — named[i] = the
+ * index of names[i], *width = W, the sum of their sizes — and everything is refused before anything is launched. */
+#define POLICY_MAX_NAMES 64 /* as many as push_config allows parameters */
+static int policy_names(ilqg_batch_t *c, const char *who, int n_names, const char *const *names, const double *values, int *named, int *width) {
+    int i, j, k;
+    if(n_names < 1) {
+        snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must be at least 1", who, n_names);
+        return 1;
+    }
+    if(!names) {
+        snprintf(c->err, sizeof(c->err), "%s: names is NULL (n_names parameter names)", who);
+        return 1;
+    }
+    if(!values) {
+        snprintf(c->err, sizeof(c->err), "%s: values is NULL (the parameter rows, [B][n_starts][W] or [n_starts][W])", who);
+        return 1;
+    }
+    *width = 0;
+    for(i = 0; i < n_names; i++) {
+        if(i >= POLICY_MAX_NAMES) {  /* (named[]: more names than that repeat one or are unknown, but are not read to find out) */
+            snprintf(c->err, sizeof(c->err), "%s: n_names = %d, more than %d names", who, n_names, POLICY_MAX_NAMES);
+            return 1;
+        }
+        if(!names[i]) {
+            snprintf(c->err, sizeof(c->err), "%s: names[%d] is NULL", who, i);
+            return 1;
+        }
+        for(k = 0; k < n_params; k++)
+            if(strcmp(paramdesc[k]->name, names[i]) == 0) break;
+        if(k == n_params) {
+            snprintf(c->err, sizeof(c->err), "%s: names[%d]: Parameter name '%s' is not member of parameters struct.", who, i, names[i]);
+            return 1;
+        }
+        if(paramdesc[k]->size == -1) {
+            snprintf(c->err, sizeof(c->err), "%s: names[%d]: parameter '%s' has one value per time step (size -1); per-time-step parameters "
+                     "stay shared by all roll-outs", who, i, names[i]);
+            return 1;
+        }
+        for(j = 0; j < i; j++)
+            if(named[j] == k) {
+                snprintf(c->err, sizeof(c->err), "%s: names[%d]: parameter '%s' is named twice (a duplicate of names[%d])", who, i, names[i], j);
+                return 1;
+            }
+        named[i] = k;
+        *width += paramdesc[k]->size;
+    }
+    return 0;
+}
+#define POLICY_VALUES_AT(w) (shared ? values : values + (size_t)c->first[g] * (size_t)n_starts * (size_t)(w))
+
+int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    int g, named[POLICY_MAX_NAMES], W;
+    if(policy_args(c, "ilqg_batch_policy_rollout_params", n_starts, x0)) return 1;
+    if(policy_names(c, "ilqg_batch_policy_rollout_params", n_names, names, values, named, &W)) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    if(push_config(c)) return 1;
+    EACH_GROUP(g)
+        if(ilqg_dev_policy_rollout_params_host(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, POLICY_VALUES_AT(W), shared, alpha, feedback,
+                                               POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X),
+                                               POLICY_AT(u, (size_t)c->N * N_U)))
+            return fail(c, "policy_rollout_params");
+    return 0;
+}
+
+int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
+                                            const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
+                                            double *x, double *u, void *stream) {
+    int g, named[POLICY_MAX_NAMES], W;
+    if(policy_args(c, "ilqg_batch_policy_rollout_params_device", n_starts, x0)) return 1;
+    if(policy_names(c, "ilqg_batch_policy_rollout_params_device", n_names, names, values, named, &W)) return 1;
+    if(ilqg_dev_check_device_ptr(c->dev[0], x0, "x0") || ilqg_dev_check_device_ptr(c->dev[0], values, "values") ||
+       (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")) || (ok && ilqg_dev_check_device_ptr(c->dev[0], ok, "ok")) ||
+       (x_end && ilqg_dev_check_device_ptr(c->dev[0], x_end, "x_end")) || (x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) ||
+       (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u")))
+        return fail(c, "ilqg_batch_policy_rollout_params_device");
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    if(push_config(c)) return 1;
+    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "policy_rollout_params: stream");
+    EACH_GROUP(g) {
+        if(ilqg_dev_policy_rollout_params(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, POLICY_VALUES_AT(W), shared, alpha, feedback,
+                                          POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X),
+                                          POLICY_AT(u, (size_t)c->N * N_U)))
+            return fail(c, "policy_rollout_params");
+        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "policy_rollout_params: stream");
+    }
+    return 0;
+}
+
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
     int g;
     if(steps < 0 || steps >= c->N) {
@@ -1661,6 +1751,24 @@ int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, d
         if(ilqg_batch_policy_rollout(m->shard[g], n_starts, x0 ? x0 + at * N_X : NULL, alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL,
                                      x_end ? x_end + at * N_X : NULL, x ? x + at * (size_t)(m->N + 1) * N_X : NULL,
                                      u ? u + at * (size_t)m->N * N_U : NULL))
+            return multi_fail(m, g);
+    }
+    return 0;
+}
+int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    int g, i, k;
+    size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
+    const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
+    if(names && values && !shared)
+        for(i = 0; i < n_names; i++)
+            for(k = 0; names[i] && k < n_params; k++)
+                if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    EACH_SHARD(g) {
+        const size_t at = (size_t)m->first[g] * r;
+        if(ilqg_batch_policy_rollout_params(m->shard[g], n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
+                                            alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
+                                            x ? x + at * (size_t)(m->N + 1) * N_X : NULL, u ? u + at * (size_t)m->N * N_U : NULL))
             return multi_fail(m, g);
     }
     return 0;

@@ -120,6 +120,7 @@ enum {
     ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head, ilqg_dev_head_device) */
     ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
+    ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout_params) */
     ILQG_K_COUNT
 };
 
@@ -195,6 +196,16 @@ int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, double alpha
                             double *x_end, double *x, double *u);
 int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
                                  double *x_end, double *x, double *u);
+/* The same roll-outs, each under problem parameters of its own (k_policy<true>): roll-out (b, r) evaluates every callback
+ * with the context's fixed-size parameters, those of the n_named parameters named[] (indices into paramdesc[], each of
+ * fixed size, no index twice — the caller has checked names; sizes and range are checked here) replaced by row (b, r) of
+ * values: [batch][R][W], or with shared != 0 [R][W] for every trajectory, W = the sum of the named sizes, the named
+ * parameters one behind the other in the order of named[].  The policy, multipliers, penalty weights and per-time-step
+ * parameters are the context's.  Memory and stream rules as for the pair above; values lives where x0 lives. */
+int ilqg_dev_policy_rollout_params(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                   double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+int ilqg_dev_policy_rollout_params_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                        double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
 /* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) / ilqg_dev_write_u_tail with the source in DEVICE memory: no staging, no wait */
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0);
 int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps);

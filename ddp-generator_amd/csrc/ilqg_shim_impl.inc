@@ -347,7 +347,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
-                                              "k_log_steps", "k_head", "k_shift_param", "k_policy"};
+                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -1184,13 +1184,54 @@ static int policy_args_ok(ilqg_dev_t *d, int R, const double *x0) {
     }
     return 1;
 }
+// the map of the ParamValues slots for the named parameters (k_policy.inc), or nullptr with g_err set
+static const PolicyParamMap *policy_param_map(int n_named, const int *named, const double *values, PolicyParamMap &map) {
+    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+    constexpr int offs[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_POFFSETS;
+    if(n_named < 1 || !named) {
+        g_err = "policy_rollout_params: n_names must be at least 1 and names not NULL";
+        return nullptr;
+    }
+    if(!values) {
+        g_err = "policy_rollout_params: values is NULL";
+        return nullptr;
+    }
+    for(int j = 0; j < ILQG_PTOTAL; j++) map.src[j] = -1;
+    map.W = 0;
+    for(int n = 0; n < n_named; n++) {
+        const int i = named[n];
+        if(i < 0 || i >= ILQG_NP || sizes[i] < 1) {
+            g_err = "policy_rollout_params: names must be fixed-size parameters of the problem (per-time-step parameters stay shared)";
+            return nullptr;
+        }
+        if(map.src[offs[i]] >= 0) {
+            g_err = "policy_rollout_params: a parameter is named twice";
+            return nullptr;
+        }
+        for(int j = 0; j < sizes[i]; j++) map.src[offs[i] + j] = (short)(map.W + j);
+        map.W += sizes[i];
+    }
+    return &map;
+}
 static int launch_policy(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok, double *x_end,
                          double *x, double *u) {
     if(roll_enter(d)) return 1;
     {
         Timed t(d, ILQG_K_POLICY, roll_stream(d));
-        hipLaunchKernelGGL(k_policy, grid1((size_t)d->B * (size_t)R, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha,
+        hipLaunchKernelGGL(k_policy<false>, grid1((size_t)d->B * (size_t)R, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha,
                            feedback ? 1 : 0, cost, ok, x_end, x, u);
+    }
+    HIP_TRY(hipGetLastError());
+    return roll_leave(d);
+}
+// the same under the rows of `values` (device memory): k_policy<true>
+static int launch_policy_params(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap &map, const double *values, int shared, double alpha,
+                                int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    if(roll_enter(d)) return 1;
+    {
+        Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
+        hipLaunchKernelGGL((k_policy<true, const double *, int, PolicyParamMap>), grid1((size_t)d->B * (size_t)R, ROLL_BLOCK), dim3(ROLL_BLOCK), 0,
+                           roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, values, shared ? 1 : 0, map);
     }
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
@@ -1205,18 +1246,27 @@ int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, double alpha
     return launch_policy(d, R, x0, alpha, feedback, cost, ok, x_end, x, u);
 }
 
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                                 double *x_end, double *x, double *u) {
+int ilqg_dev_policy_rollout_params(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                   double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     HIP_TRY(hipSetDevice(d->device));
     NEED_PARAMS(d);
-    if(!policy_args_ok(d, R, x0)) return 1;
+    PolicyParamMap map;
+    if(!policy_args_ok(d, R, x0) || !policy_param_map(n_named, named, values, map)) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
+    return launch_policy_params(d, R, x0, map, values, shared, alpha, feedback, cost, ok, x_end, x, u);
+}
+
+// the host forms: the starts, then with a map the table of values, then the outputs, in one piece of the staging buffer
+static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, double alpha,
+                                 int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     const size_t n = (size_t)d->B * (size_t)R;
     void *const host[5] = {cost, ok, x_end, x, u};
     const size_t bytes[5] = {n * sizeof(double), n * sizeof(int), n * NX * sizeof(double), n * (size_t)(d->N + 1) * NX * sizeof(double),
                              n * (size_t)d->N * NU * sizeof(double)};
     const size_t in_bytes = n * NX * sizeof(double);
-    size_t off[5], total = (in_bytes + 255) & ~(size_t)255;  // slices 256 bytes apart, the starts first
+    const size_t val_bytes = map ? (shared ? (size_t)R : n) * (size_t)map->W * sizeof(double) : 0;
+    const size_t val_off = (in_bytes + 255) & ~(size_t)255;  // slices 256 bytes apart, the starts first
+    size_t off[5], total = val_off + ((val_bytes + 255) & ~(size_t)255);
     for(int i = 0; i < 5; i++) {
         off[i] = total;
         if(host[i]) total += (bytes[i] + 255) & ~(size_t)255;
@@ -1224,9 +1274,12 @@ int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double 
     void *dev, *pin;
     if(stage(d, total, &dev, &pin)) return 1;
     if(stage_in(d, dev, pin, x0, in_bytes)) return 1;
+    if(map && stage_in(d, (char *)dev + val_off, pin ? (char *)pin + val_off : nullptr, values, val_bytes)) return 1;
     void *dv[5];
     for(int i = 0; i < 5; i++) dv[i] = host[i] ? (void *)((char *)dev + off[i]) : nullptr;
-    if(launch_policy(d, R, (const double *)dev, alpha, feedback, (double *)dv[0], (int *)dv[1], (double *)dv[2], (double *)dv[3], (double *)dv[4]))
+    if(map ? launch_policy_params(d, R, (const double *)dev, *map, (const double *)((char *)dev + val_off), shared, alpha, feedback, (double *)dv[0],
+                                  (int *)dv[1], (double *)dv[2], (double *)dv[3], (double *)dv[4])
+           : launch_policy(d, R, (const double *)dev, alpha, feedback, (double *)dv[0], (int *)dv[1], (double *)dv[2], (double *)dv[3], (double *)dv[4]))
         return 1;
     for(int i = 0; i < 5; i++) {
         if(!host[i]) continue;
@@ -1236,6 +1289,25 @@ int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double 
     }
     if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
     return 0;
+}
+
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                                 double *x_end, double *x, double *u) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    if(!policy_args_ok(d, R, x0)) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    return policy_rollout_staged(d, R, x0, nullptr, nullptr, 0, alpha, feedback, cost, ok, x_end, x, u);
+}
+
+int ilqg_dev_policy_rollout_params_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                        double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    PolicyParamMap map;
+    if(!policy_args_ok(d, R, x0) || !policy_param_map(n_named, named, values, map)) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    return policy_rollout_staged(d, R, x0, &map, values, shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {

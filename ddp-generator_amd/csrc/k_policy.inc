@@ -42,9 +42,52 @@ __device__ __forceinline__ void load_policy_step(NomStep &s, const NomPtrs &q, b
     }
 }
 
+// Per-roll-out problem parameters (ilqg_dev_policy_rollout_params).  k_policy<true> is the same roll-out with three more
+// arguments — the caller's table `values`, [B][R][W] or with `shared` [R][W], and a by-value map of the ParamValues slots:
+// src[j] = the column of a row that replaces slot j, or -1 for a slot that keeps the batch's value.  Behind ILQG_CALLBACKS
+// every lane overrides the mapped slots of its PRIVATE ParamValues with row (shared ? r : g) of the table; the callbacks
+// then read them through the same ParamTable as ever.  The map is a kernel argument, so the test of a slot is a scalar
+// branch; an overridden slot lives in two vector registers instead of two scalar ones.  The policy (x, u, l, L of slot b),
+// the multipliers, the penalty weights and the per-time-step parameters are the batch's.  k_policy<false> has no further
+// argument (the pack is empty) and not one statement more than before.
+struct PolicyParamMap {
+    short src[ILQG_PTOTAL];
+    int W;
+};
+// Register-resident overrides cost two vector registers per parameter double, 90 for the n = 16 problem.  Its FMA-free
+// builds (tests only) have none to give — their k_policy<false> already takes 448 of 512 — and would pay in scratch memory;
+// there the callbacks read EVERY fixed-size parameter from global memory instead: a named one in the lane's row of the
+// caller's table, the others in the context's own parameter buffers (P.p, which hold the fixed-size parameters too).  No
+// private copy, no register, and a reload behind every store the compiler cannot tell apart.
+#ifndef ILQG_POLICY_PARAMS_IN_MEMORY
+#if defined(ILQG_STRICT_FP)
+#define ILQG_POLICY_PARAMS_IN_MEMORY (2 * ILQG_PTOTAL > 64)
+#else
+#define ILQG_POLICY_PARAMS_IN_MEMORY 0
+#endif
+#endif
+__device__ __forceinline__ void override_params(ParamValues &V, ParamTable &T, const DevPtrs &P, size_t g, int r, const double *__restrict__ values,
+                                                int shared, const PolicyParamMap &map) {
+    const double *row = values + (shared ? (size_t)r : g) * (size_t)map.W;
+    if(ILQG_POLICY_PARAMS_IN_MEMORY) {
+        constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+        constexpr int offs[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_POFFSETS;
+#pragma unroll
+        for(int i = 0; i < ILQG_NP; i++)
+            if(sizes[i] > 0) T.ptr[i] = map.src[offs[i]] >= 0 ? const_cast<double *>(row + map.src[offs[i]]) : P.p[i];
+    } else {
+#pragma unroll
+        for(int j = 0; j < ILQG_PTOTAL; j++)
+            if(map.src[j] >= 0) V.v[j] = row[map.src[j]];
+    }
+}
+
+template <bool PER_ROLLOUT_PARAMS, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
                                                                          double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
-                                                                         double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou) {
+                                                                         double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
+                                                                         Rows... rows) {
+    static_assert(sizeof...(Rows) == (PER_ROLLOUT_PARAMS ? 3 : 0), "k_policy<true>(..., values, shared, map); k_policy<false>(...)");
     const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
     if(g >= (size_t)P.B * (size_t)R) return;
     const int b = (int)(g / (size_t)R);
@@ -65,6 +108,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
     }
 
     ILQG_CALLBACKS(C, H);
+    if constexpr(PER_ROLLOUT_PARAMS) override_params(C_values, C_table, P, g, (int)(g - (size_t)b * (size_t)R), rows...);
     load_penalty_weights(C, P, b);
     el_t ct;
     multipliersEl_t mk;

@@ -129,9 +129,76 @@ def _policy_starts(x0, B, nx):
     return np.ascontiguousarray(a)
 
 
+def _policy_param_sizes(problem, params):
+    """the sizes of the parameters a policy_rollout(params=...) names, in dict order; refused here as the library refuses
+    them: a name that is no parameter, and one with a value per time step"""
+    if not isinstance(params, dict) or not params:
+        raise IlqgError("policy_rollout: params must be a non-empty dict of parameter name -> array ([B, R, size], or [R, size] for every trajectory)")
+    known = dict(problem.params)
+    sizes = []
+    for name in params:
+        if name not in known:
+            raise IlqgError("policy_rollout: params: Parameter name '%s' is not member of parameters struct." % name)
+        if known[name] < 1:
+            raise IlqgError("policy_rollout: params: '%s' has one value per time step; per-time-step parameters stay shared by all roll-outs" % name)
+        sizes.append(known[name])
+    return sizes
+
+
+def _policy_param_form(name, shape, size, B, R):
+    """True for a [R, size] array (one table for every trajectory), False for [B, R, size]; the last axis may be left out
+    for size 1"""
+    shape = tuple(int(n) for n in shape)
+    if shape == (B, R, size) or (size == 1 and shape == (B, R) and shape != (R, size)):
+        return False
+    if shape == (R, size) or (size == 1 and shape == (R,)):
+        return True
+    raise IlqgError("policy_rollout: params['%s'] has shape %s, expected (%d, %d, %d) or (%d, %d)%s, with R = %d as in x0"
+                    % (name, shape, B, R, size, R, size, " (the last axis may be left out)" if size == 1 else "", R))
+
+
+def _policy_param_names(params):
+    return (C.c_char_p * len(params))(*[name.encode() for name in params])
+
+
+def _policy_param_rows(problem, params, B, R):
+    """(names, values, shared) for ilqg_batch_policy_rollout_params from host arrays: values [B, R, W] or, where every
+    array is [R, size], [R, W], C-contiguous doubles, the named parameters one behind the other in dict order"""
+    sizes = _policy_param_sizes(problem, params)
+    cols, forms = [], []
+    for (name, a), size in zip(params.items(), sizes):
+        if _is_cuda(a):
+            raise IlqgError("policy_rollout: params['%s'] is a tensor on the device: pass device=True" % name)
+        a = np.asarray(a, dtype=np.float64)
+        forms.append(_policy_param_form(name, a.shape, size, B, R))
+        cols.append(a.reshape((R, size) if forms[-1] else (B, R, size)))
+    if len(set(forms)) != 1:
+        raise IlqgError("policy_rollout: params mixes [R, size] arrays (%s) with [B, R, size] arrays (%s): every array in one form"
+                        % (", ".join(n for n, f in zip(params, forms) if f), ", ".join(n for n, f in zip(params, forms) if not f)))
+    return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1)), 1 if forms[0] else 0
+
+
+def _policy_param_tensors(problem, params, B, R, device):
+    """the same checks for float64 torch tensors on the solver's GPU: [(tensor, its shape with the last axis)], shared"""
+    sizes = _policy_param_sizes(problem, params)
+    cols, forms = [], []
+    for (name, a), size in zip(params.items(), sizes):
+        what = "policy_rollout: params['%s']" % name
+        if not _is_cuda(a):
+            raise IlqgError("%s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % what)
+        forms.append(_policy_param_form(name, a.shape, size, B, R))
+        _cuda_address(a, a.shape, device, what)
+        cols.append((a, (R, size) if forms[-1] else (B, R, size)))
+    if len(set(forms)) != 1:
+        raise IlqgError("policy_rollout: params mixes [R, size] tensors (%s) with [B, R, size] tensors (%s): every tensor in one form"
+                        % (", ".join(n for n, f in zip(params, forms) if f), ", ".join(n for n, f in zip(params, forms) if not f)))
+    return cols, 1 if forms[0] else 0
+
+
 def _receding_entry(lib, name):
     """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift, ilqg_batch_head / _head_device / _shift_device /
-    _shift_param / ilqg_multi_head, and ilqg_batch_policy_rollout / _policy_rollout_device / ilqg_multi_policy_rollout, of a problem library; one built before they existed (a pair compiled out of tree and
+    _shift_param / ilqg_multi_head, ilqg_batch_policy_rollout / _policy_rollout_device / ilqg_multi_policy_rollout and their
+    _params forms, of a problem library; one built before they existed (a pair compiled out of tree and
     not rebuilt since) still loads and solves, and says so when they are asked for"""
     if not hasattr(lib, name):
         raise IlqgError("this problem library was built before %s existed: rebuild it (make -C ddp-generator_amd/csrc)" % name)
@@ -217,6 +284,11 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_policy_rollout.argtypes = [v, C.c_int, v, C.c_double, C.c_int, v, v, v, v, v]
         lib.ilqg_batch_policy_rollout_device.argtypes = [v, C.c_int, v, C.c_double, C.c_int, v, v, v, v, v, v]
         lib.ilqg_multi_policy_rollout.argtypes = [v, C.c_int, v, C.c_double, C.c_int, v, v, v, v, v]
+    if hasattr(lib, "ilqg_batch_policy_rollout_params"):  # (and under parameters per roll-out)
+        named = [v, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, C.c_int, C.c_double, C.c_int, v, v, v, v, v]
+        lib.ilqg_batch_policy_rollout_params.argtypes = named
+        lib.ilqg_batch_policy_rollout_params_device.argtypes = named + [v]
+        lib.ilqg_multi_policy_rollout_params.argtypes = named
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -385,7 +457,7 @@ class BatchSolver:
         self._ck(entry(self.h, int(steps), *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
         return out
 
-    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False):
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False, params=None):
         """every plan's feedback policy rolled out from R starts per trajectory on the GPU (ilqg_batch_policy_rollout):
         x0 [B,R,nx], or [R,nx] for every trajectory; u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if
         feedback], clamped, through the problem's dynamics and cost.  The policy is what head(N, gains=True) returns — behind
@@ -393,7 +465,13 @@ class BatchSolver:
         dict(cost [B,R], ok [B,R] int32 (0: a value was NaN / Inf, the roll-out's other outputs are unspecified),
         x_end [B,R,nx]) and with trajectories x [B,R,N+1,nx], u [B,R,N,nu] (the clamped controls applied).
         numpy arrays, or with device=True a float64 torch tensor [B,R,nx] on the solver's GPU in and torch tensors out, in
-        the order of torch's current stream without a host wait (ilqg_batch_policy_rollout_device)."""
+        the order of torch's current stream without a host wait (ilqg_batch_policy_rollout_device).
+        params = {name: array}: roll-out (b, r) runs under problem parameters of its own (ilqg_batch_policy_rollout_params) —
+        the batch's, with every named fixed-size parameter replaced by array[b, r]: every array [B,R,size], or every array
+        [R,size] for all trajectories (the last axis may be left out for size 1), R as in x0.  The policy stays the plan's:
+        its gains were computed under the batch's parameters.  Per-time-step parameters stay shared and cannot be named;
+        the batch's parameters do not change.  With device=True contiguous float64 torch tensors on the solver's GPU,
+        packed with torch.cat on torch's current stream (a single tensor is read where it is)."""
         nx, nu, B, N = self.problem.nx, self.problem.nu, self.B, self.N
         order = ("cost", "ok", "x_end", "x", "u")
         if not device:
@@ -404,6 +482,11 @@ class BatchSolver:
             out = dict(cost=np.zeros((B, R)), ok=np.zeros((B, R), dtype=np.int32), x_end=np.zeros((B, R, nx)))
             if trajectories:
                 out.update(x=np.zeros((B, R, N + 1, nx)), u=np.zeros((B, R, N, nu)))
+            if params is not None:
+                names, values, shared = _policy_param_rows(self.problem, params, B, R)
+                self._ck(_receding_entry(self.lib, "ilqg_batch_policy_rollout_params")(self.h, R, _address(x0), len(names), names, _address(values), shared,
+                                                                                       float(alpha), 1 if feedback else 0, *[_address(out.get(k)) for k in order]))
+                return out
             self._ck(_receding_entry(self.lib, "ilqg_batch_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
                                                                             *[_address(out.get(k)) for k in order]))
             return out
@@ -413,7 +496,9 @@ class BatchSolver:
             raise IlqgError("policy_rollout: x0 has shape %s, expected (%d, R, %d) with n_starts = R >= 1" % (tuple(x0.shape), B, nx))
         R = int(x0.shape[1])
         px = _cuda_address(x0, (B, R, nx), self.device, "x0")
-        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_device")
+        if params is not None:
+            cols, shared = _policy_param_tensors(self.problem, params, B, R, self.device)
+        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_device" if params is None else "ilqg_batch_policy_rollout_params_device")
         torch = _torch_on_gpu()
         dev = torch.device("cuda", self.device)
         out = dict(cost=torch.empty((B, R), dtype=torch.float64, device=dev), ok=torch.empty((B, R), dtype=torch.int32, device=dev),
@@ -421,6 +506,13 @@ class BatchSolver:
         if trajectories:
             out.update(x=torch.empty((B, R, N + 1, nx), dtype=torch.float64, device=dev), u=torch.empty((B, R, N, nu), dtype=torch.float64, device=dev))
         ptr = [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in order]
+        if params is not None:
+            with torch.cuda.device(dev):  # (a single tensor is the table as it lies: [B, R] and [B, R, 1] are the same memory)
+                values = cols[0][0] if len(cols) == 1 else torch.cat([a.reshape(shape) for a, shape in cols], dim=-1)
+            names = _policy_param_names(params)
+            self._ck(entry(self.h, R, px, len(names), names, C.c_void_p(values.data_ptr() or None), shared, float(alpha), 1 if feedback else 0, *ptr,
+                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+            return out
         self._ck(entry(self.h, R, px, float(alpha), 1 if feedback else 0, *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
         return out
 
@@ -676,14 +768,21 @@ class MultiSolver:
         self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *[_address(out.get(k)) for k in ("x", "u", "l", "L", "cost")]))
         return out
 
-    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False):
-        """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout), numpy arrays"""
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, params=None):
+        """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout, with params ilqg_multi_policy_rollout_params),
+        numpy arrays"""
         nx, nu, B, N = self.problem.nx, self.problem.nu, self.B, self.N
         x0 = _policy_starts(x0, B, nx)
         R = x0.shape[1]
         out = dict(cost=np.zeros((B, R)), ok=np.zeros((B, R), dtype=np.int32), x_end=np.zeros((B, R, nx)))
         if trajectories:
             out.update(x=np.zeros((B, R, N + 1, nx)), u=np.zeros((B, R, N, nu)))
+        if params is not None:
+            names, values, shared = _policy_param_rows(self.problem, params, B, R)
+            self._ck(_receding_entry(self.lib, "ilqg_multi_policy_rollout_params")(self.h, R, _address(x0), len(names), names, _address(values), shared,
+                                                                                   float(alpha), 1 if feedback else 0,
+                                                                                   *[_address(out.get(k)) for k in ("cost", "ok", "x_end", "x", "u")]))
+            return out
         self._ck(_receding_entry(self.lib, "ilqg_multi_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
                                                                         *[_address(out.get(k)) for k in ("cost", "ok", "x_end", "x", "u")]))
         return out

@@ -177,6 +177,35 @@ int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, d
                               double *x_end, double *x, double *u);
 int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                                      double *x_end, double *x, double *u, void *stream);
+/* The same roll-outs, EACH UNDER PROBLEM PARAMETERS OF ITS OWN: what a plan does on a plant whose wheelbase, time step,
+ * limits or cost weights differ from the model it was planned with (a Monte-Carlo estimate over model error).
+ *
+ * Everything is as in ilqg_batch_policy_rollout — the nominal data, the four (alpha, feedback) kinds, the clamp, the
+ * multipliers and penalty weights of trajectory b, the outputs, their layouts and the per-roll-out ok, and NOTHING in the
+ * batch changes, its parameters included — with one difference: roll-out (b, r) evaluates every generated callback
+ * (init_running, calcXVariableAux, clampU, calcXUVariableAux, ddpf, ddpL, calcFVariableAux, ddpF) with a parameter set of
+ * its own: the batch's current fixed-size parameters, in which the values of the NAMED PARAMETERS REPLACE THE BATCH'S by
+ * the caller's row for that roll-out.  The policy itself stays the plan's: x, u, l, L, THE GAINS HAVING BEEN COMPUTED UNDER
+ * THE BATCH'S PARAMETERS — applying a policy planned for one model to another is the purpose.  PER-TIME-STEP PARAMETERS
+ * (size -1) STAY SHARED, as they stand; naming one is refused.
+ *
+ * names: n_names >= 1 host strings, each a fixed-size parameter of paramdesc[], in any order (not necessarily that of
+ * paramdesc[]), none twice.  W = the sum of the named parameters' sizes.  values: [B][n_starts][W], or with shared != 0
+ * [n_starts][W], used for every trajectory; within a row the named parameters follow each other in the order of names,
+ * each contiguous.  Refused before anything is launched, with the argument and the parameter named in the error text and
+ * the batch untouched: a name that is no parameter ("Parameter name '%s' is not member of parameters struct."), a
+ * per-time-step parameter, a name given twice, n_names < 1, names or values NULL, n_starts < 1, x0 NULL and, in the device
+ * form, x0 / values / an output that is not device memory of the context's device.  All outputs NULL is a no-op after these
+ * checks.
+ * ilqg_batch_policy_rollout_params takes host memory for x0 and values, stages them through the context's buffers, which
+ * only grow, and waits once per group.  ilqg_batch_policy_rollout_params_device takes DEVICE memory for x0, values and the
+ * outputs under the stream contract of ilqg_batch_head_device (event in, one event per group out, no host wait, no
+ * allocation in steady state); names are host strings in both. */
+int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
+                                            const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
+                                            double *x, double *u, void *stream);
 /* The window of ONE per-time-step parameter (size -1) moves `steps` values on: p'[k] = p[k + steps], the last `steps`
  * values from tail [steps] (host), or p[n_hor] held if tail is NULL.  0 <= steps <= n_hor.  Exactly what
  * ilqg_batch_set_param(c, name, [p[steps:], tail], n_hor + 1) gives, without re-allocating or re-sending the table: the
@@ -277,6 +306,9 @@ int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const dou
 int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l, double *L, double *cost);  /* ilqg_batch_head per shard */
 int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                               double *x_end, double *x, double *u);  /* ilqg_batch_policy_rollout per shard (host memory) */
+/* ilqg_batch_policy_rollout_params per shard (host memory): values is offset by the shard's first trajectory unless shared */
+int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
 int ilqg_multi_iterate(ilqg_multi_t *m, int n);   /* asynchronous on every device; the devices are served in turn */
 int ilqg_multi_solve(ilqg_multi_t *m);
 int ilqg_multi_sync(ilqg_multi_t *m);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Roll-outs of the policy from perturbed starts (BatchSolver.policy_rollout, k_policy) against the line search's roll-outs.
 
-    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search]
+    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search] [--params]
 
 One process per invocation, one stream group (a launch's HIP-event time is then that launch alone).  The yardstick is the
 line search of the SAME run with ls_keep = 0, ls_split = 0: k_rollout[search] rolls out (active trajectories) x n_alpha
@@ -10,6 +10,12 @@ the legs ALTERNATE, `--repeats` times: one solver iteration (its search launch i
 the policy at every R of --rs, whole roll-outs at R = 8 (device form: the outputs stay on the GPU), and R = 8 costs-only
 through the host form against the device form (host clock between two device synchronisations).  Kernel times are HIP
 events (ilqg_batch_get_timing), read before and after every leg.  Not part of bench.py.
+
+--params adds the roll-outs under parameters per roll-out (policy_rollout(params=...), k_policy<true>, timing slot
+"k_policy_params") to the same alternation: costs only at every R of --rs with ALL fixed-size parameters named and with a
+SINGLE parameter named, each roll-out with a row of its own ([B, R, W], nominal * (1 + 0.05 N(0, 1))), and at R = 8 one
+[R, W] table shared by every trajectory against the per-trajectory table.  Each is reported as a ratio to the plain k_policy
+launch of the same R in the same run.
 """
 import argparse
 import os
@@ -27,7 +33,7 @@ def spread(v, unit="ms"):
     return "median %10.4f %s  min %10.4f  max %10.4f  (n = %d)" % (np.median(v), unit, v.min(), v.max(), len(v))
 
 
-def run(ilqg, synth, config, repeats, warmup, rs, scalar_search):
+def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=False):
     import torch
     if scalar_search:  # (read once, when the context is made)
         os.environ["ILQG_NO_ROLLOUT_PARTS"] = "1"
@@ -63,9 +69,31 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search):
         return n, ms
 
     legs = [("search", None)] + [("costs R=%d" % R, R) for R in rs] + [("whole R=8", 8), ("host R=8", 8), ("device R=8", 8)]
+    tables = {}
+    if with_params:
+        fixed = [(n, size) for n, size in s.problem.params if size > 0]
+        single = fixed[0][0]
+        gen = torch.Generator(device="cuda").manual_seed(5)
+
+        def table(names, shape):
+            return {n: torch.tensor(np.asarray(params[n], dtype=np.float64).reshape(-1), device="cuda") *
+                    (1.0 + 0.05 * torch.randn(shape + (size,), dtype=torch.float64, device="cuda", generator=gen)) for n, size in fixed if n in names}
+        for R in rs:
+            tables["all R=%d" % R] = table([n for n, _ in fixed], (B, R))
+            tables["one R=%d" % R] = table([single], (B, R))
+            legs += [("all R=%d" % R, R), ("one R=%d" % R, R)]
+        if 8 not in rs:
+            tables["all R=8"] = table([n for n, _ in fixed], (B, 8))
+            legs.append(("all R=8", 8))
+        tables["shared R=8"] = table([n for n, _ in fixed], (8,))
+        legs.append(("shared R=8", 8))
+        print("   --params: %d fixed-size parameters, %d doubles per row when all are named (%s); the single one is %s" % (
+            len(fixed), sum(size for _, size in fixed), ", ".join(n for n, _ in fixed), single), flush=True)
 
     def leg(name, R):
-        if name == "search":
+        if name in tables:
+            s.policy_rollout(dev_starts[R], device=True, params=tables[name])
+        elif name == "search":
             s.iterate(1)
         elif name.startswith("costs") or name.startswith("device"):
             s.policy_rollout(dev_starts[R], device=True)
@@ -87,7 +115,7 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search):
     n_alpha = 8  # standard_parameters (iLQG.c:74): no option of this run changes the list of step sizes
     for r in range(repeats):
         for name, R in legs:
-            which = "k_rollout[search]" if name == "search" else "k_policy"
+            which = "k_rollout[search]" if name == "search" else "k_policy_params" if name in tables else "k_policy"
             active = s.active() if name == "search" else B
             sync()
             n0, ms0 = kernel(which)
@@ -106,7 +134,7 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search):
     s.timing(False)
     print("the searches rolled out %d .. %d active trajectories x %d step sizes" % (min(actives), max(actives), n_alpha))
     for name, R in legs:
-        which = "k_rollout[search]" if name == "search" else "k_policy"
+        which = "k_rollout[search]" if name == "search" else "k_policy_params" if name in tables else "k_policy"
         print("%-12s %-18s per launch   %s" % (name, which, spread(kern[name])))
         print("%-12s %-18s per roll-out %s" % ("", "", spread(per[name], "ns")))
     base = np.median(per["search"])
@@ -115,6 +143,16 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search):
         m = np.median(per[name])
         print("ratio per roll-out, k_policy %-10s / k_rollout[search]: %.3f  (medians; the search's own repeats span %.3f .. %.3f of its median, k_policy's %.3f .. %.3f of its)" % (
             name, m / base, lo / base, hi / base, np.min(per[name]) / m, np.max(per[name]) / m))
+    for name, R in legs:
+        if name not in tables:
+            continue
+        plain = "costs R=%d" % R if R in rs else "device R=8"
+        m, p0 = np.median(kern[name]), np.median(kern[plain])
+        print("ratio per launch, k_policy_params %-11s / k_policy %-11s: %.3f  (medians; its repeats span %.3f .. %.3f of its median, the plain launch's %.3f .. %.3f of its)" % (
+            name, plain, m / p0, np.min(kern[name]) / m, np.max(kern[name]) / m, np.min(kern[plain]) / p0, np.max(kern[plain]) / p0))
+    if with_params:
+        print("ratio per launch, shared [R, W] table / per-trajectory [B, R, W] table at R = 8, all parameters named: %.3f" % (
+            np.median(kern["shared R=8"]) / np.median(kern["all R=8"])))
     print("host form R=8, host clock:    " + spread(wall["host R=8"]))
     print("device form R=8, host clock:  " + spread(wall["device R=8"]))
     print("ratio of medians host / device form: %.2f  (host form: %.1f MB of starts up, %.1f MB of results down per call)" % (
@@ -131,12 +169,14 @@ def main():
     ap.add_argument("--rs", default="1,8,64")
     ap.add_argument("--scalar-search", action="store_true", help="wave-mapped builds whose line search rolls out in parts (k_rollout_parts, "
                     "several wavefronts per 64 trajectories): the search on k_rollout instead, one lane per roll-out like k_policy")
+    ap.add_argument("--params", action="store_true", help="also the roll-outs under parameters per roll-out (k_policy_params): all fixed-size "
+                    "parameters named, a single one named, and a shared against a per-trajectory table at R = 8")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.load_package()
     from ddp_generator_amd import ilqg, synth
     for config in (("headline", "config5") if a.config == "both" else (a.config,)):
-        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search)
+        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search, a.params)
 
 
 if __name__ == "__main__":
