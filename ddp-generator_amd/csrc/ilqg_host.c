@@ -760,6 +760,70 @@ int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, co
     return 0;
 }
 
+/* The closed loop of planner and plant, resident on the device (k_plant.inc): per round { iterate; the plants advance
+ * `steps` steps from their own states under the plans' policies and the plants' parameters; the plans shift and start again
+ * from the plants' states }.  Everything is refused before anything is launched or allocated; values, disturbance and
+ * x_plant go up once (ilqg_dev_plant_begin), the logs come down once (ilqg_dev_plant_read), and nothing waits in between. */
+int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
+                              double *cost_applied, double *plan_cost, int *ok) {
+    static const char who[] = "ilqg_batch_receding_plant";
+    int g, r, i, named[POLICY_MAX_NAMES], W = 0;
+    if(rounds < 1) {
+        snprintf(c->err, sizeof(c->err), "%s: rounds = %d, must be at least 1", who, rounds);
+        return 1;
+    }
+    if(iterations < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: iterations = %d, must not be negative", who, iterations);
+        return 1;
+    }
+    if(steps < 1 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", who, steps, c->N - 1);
+        return 1;
+    }
+    for(i = 0; i < n_params; i++)
+        if(paramdesc[i]->size == -1) {
+            snprintf(c->err, sizeof(c->err), "%s: parameter '%s' has one value per time step and its window must move "
+                     "with the horizon: loop over ilqg_batch_iterate, ilqg_batch_set_param and ilqg_batch_shift instead", who, paramdesc[i]->name);
+            return 1;
+        }
+    if(n_names < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0: the plant is the model)", who, n_names);
+        return 1;
+    }
+    if(n_names > 0 && policy_names(c, who, n_names, names, values, named, &W)) return 1;
+    if(push_config(c)) return 1;
+    {
+        const size_t per = (size_t)rounds * (size_t)steps;
+        EACH_GROUP(g) {
+            const size_t first = (size_t)c->first[g];
+            if(ilqg_dev_plant_begin(c->dev[g], rounds, steps, x_plant ? x_plant + first * N_X : NULL, n_names, named,
+                                    n_names > 0 ? values + first * (size_t)W : NULL, disturbance ? disturbance + first * per * N_X : NULL))
+                return fail(c, "receding_plant");
+        }
+        for(r = 0; r < rounds; r++) {
+            if(iterate_groups(c, iterations)) return 1;
+            /* the plants read the plans the shift moves: k_plant is enqueued in front of k_shift_* on every group's stream */
+            EACH_GROUP(g) if(ilqg_dev_plant_advance(c->dev[g], r, feedback)) return fail(c, "receding_plant: plant");
+            /* ilqg_batch_shift(c, steps, x0_new = the plants' states, NULL), the states being on the device already */
+            EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, 0)) return fail(c, "shift");
+            EACH_GROUP(g) if(ilqg_dev_plant_put_x0(c->dev[g])) return fail(c, "shift: x0_new");
+            EACH_GROUP(g) {
+                if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
+                if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
+            }
+        }
+        EACH_GROUP(g) {
+            const size_t first = (size_t)c->first[g];
+            if(ilqg_dev_plant_read(c->dev[g], x_plant ? x_plant + first * N_X : NULL, x_applied ? x_applied + first * per * N_X : NULL,
+                                   u_applied ? u_applied + first * per * N_U : NULL, cost_applied ? cost_applied + first * rounds : NULL,
+                                   plan_cost ? plan_cost + first * rounds : NULL, ok ? ok + first : NULL))
+                return fail(c, "receding_plant: log");
+        }
+    }
+    return 0;
+}
+
 /* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param), and in the host
  * mirror c->p[i], from which a later ilqg_batch_set_param of another parameter re-pushes the whole table */
 int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const double *tail) {
@@ -1769,6 +1833,26 @@ int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double
         if(ilqg_batch_policy_rollout_params(m->shard[g], n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
                                             alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
                                             x ? x + at * (size_t)(m->N + 1) * N_X : NULL, u ? u + at * (size_t)m->N * N_U : NULL))
+            return multi_fail(m, g);
+    }
+    return 0;
+}
+int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
+                              double *cost_applied, double *plan_cost, int *ok) {
+    int g, i, k;
+    size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
+    const size_t rn = rounds > 0 ? (size_t)rounds : 0, per = rn * (steps > 0 ? (size_t)steps : 0);
+    if(names && values)
+        for(i = 0; i < n_names; i++)
+            for(k = 0; names[i] && k < n_params; k++)
+                if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    EACH_SHARD(g) {
+        const size_t at = (size_t)m->first[g];
+        if(ilqg_batch_receding_plant(m->shard[g], rounds, steps, iterations, feedback, x_plant ? x_plant + at * N_X : NULL, n_names, names,
+                                     values ? values + at * W : NULL, disturbance ? disturbance + at * per * N_X : NULL,
+                                     x_applied ? x_applied + at * per * N_X : NULL, u_applied ? u_applied + at * per * N_U : NULL,
+                                     cost_applied ? cost_applied + at * rn : NULL, plan_cost ? plan_cost + at * rn : NULL, ok ? ok + at : NULL))
             return multi_fail(m, g);
     }
     return 0;

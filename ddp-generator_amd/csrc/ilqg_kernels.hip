@@ -1039,6 +1039,8 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 
 #include "k_policy.inc"  // k_policy (roll-outs of every plan's feedback policy from the caller's starts)
 
+#include "k_plant.inc"  // k_plant (the plant of a closed loop: `steps` steps per round from a state of its own)
+
 }  // namespace
 
 #ifndef ILQG_ONLY_KERNEL

@@ -121,6 +121,7 @@ enum {
     ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
     ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout_params) */
+    ILQG_K_PLANT,    /* k_plant (ilqg_dev_plant_advance) */
     ILQG_K_COUNT
 };
 
@@ -206,6 +207,28 @@ int ilqg_dev_policy_rollout_params(ilqg_dev_t *d, int R, const double *x0, int n
                                    double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
 int ilqg_dev_policy_rollout_params_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
                                         double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+/* The plant of a closed loop that stays on the device (k_plant.inc): `rounds` times { ilqg_dev_iterate; ilqg_dev_plant_advance;
+ * ilqg_dev_shift(d, steps, 0); ilqg_dev_plant_put_x0; ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_plant_begin
+ * and one ilqg_dev_plant_read — the caller's loop; nothing in it waits or copies.
+ * begin (HOST memory in, all of it sent once; waits once): the plants' states x_plant [batch][N_X], or NULL = every plan's
+ * x_0; the plants' parameters — the context's fixed-size ones with the n_named parameters named[] replaced by row b of
+ * values [batch][W], names and W as in ilqg_dev_policy_rollout_params with R = 1 and shared = 0; n_named = 0: the
+ * context's own —; disturbance [batch][rounds*steps][N_X], added to the state behind each step, or NULL = none.  It also
+ * sizes the logs (the rules of ilqg_dev_log_begin, whose log it takes) and clears the plants' failure flags.
+ * rounds >= 1, 1 <= steps < n_hor.
+ * advance: every plant that has not failed advances `steps` steps from its own state under the CURRENT plan's policy,
+ * u = u_nom_k [+ L_k (xp - x_nom_k) if feedback], through the step of forward_pass under the plant's parameters and the
+ * multipliers and penalty weights its slot has, then xp <- x_next + disturbance; the state each control was applied at, the
+ * clamped control, the sum of the running costs and the plan's cost go to the logs of round `round`.  A plant fails — for
+ * the rest of the loop, staying at its last finite state — when a step's guards fail or its state is not finite.  Writes
+ * nothing of the solver's state.  put_x0: the plants' states become x_0 of the plans (ilqg_dev_put_x0_device).
+ * read (waits once): x_plant [batch][N_X] the plants' states now, x [batch][rounds*steps][N_X], u [..][N_U],
+ * cost_applied / plan_cost [batch][rounds], ok [batch] (0 = failed); any may be NULL. */
+int ilqg_dev_plant_begin(ilqg_dev_t *d, int rounds, int steps, const double *x_plant, int n_named, const int *named, const double *values,
+                         const double *disturbance);
+int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback);
+int ilqg_dev_plant_put_x0(ilqg_dev_t *d);
+int ilqg_dev_plant_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok);
 /* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) / ilqg_dev_write_u_tail with the source in DEVICE memory: no staging, no wait */
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0);
 int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps);

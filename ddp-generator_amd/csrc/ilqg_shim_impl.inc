@@ -81,6 +81,13 @@ struct ilqg_dev {
     bool per_step_params;       // some problem parameter has one value per time step
     double *log_x, *log_u, *log_c;  // receding horizon: the applied steps of every round (ilqg_dev_log_begin), host layout
     int log_rounds, log_steps;
+    // the plants of a closed loop (ilqg_dev_plant_begin): their states [B][NX], failure flags [B], the sums of the applied
+    // running costs [B][rounds] (the applied steps and the plans' costs go to the log above), and what the caller sent:
+    // the parameter rows [B][W] with their map, the disturbances [B][rounds * steps][NX]
+    double *plant_xp, *plant_cost, *plant_values, *plant_dist;
+    int *plant_failed;
+    bool plant_named;
+    PolicyParamMap plant_map;
     hipEvent_t ext_in, ext_out;  // ordering with a stream of the caller (ilqg_dev_stream_in / _out), made with the context
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
@@ -285,6 +292,18 @@ int drain_spans(ilqg_dev *d) {
 
 inline dim3 grid1(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 
+// the plants' buffers (ilqg_dev_plant_begin makes them anew for every loop; the caller has synchronised)
+void plant_release(ilqg_dev *d) {
+    if(d->plant_xp) hipFree(d->plant_xp);
+    if(d->plant_cost) hipFree(d->plant_cost);
+    if(d->plant_values) hipFree(d->plant_values);
+    if(d->plant_dist) hipFree(d->plant_dist);
+    if(d->plant_failed) hipFree(d->plant_failed);
+    d->plant_xp = d->plant_cost = d->plant_values = d->plant_dist = nullptr;
+    d->plant_failed = nullptr;
+    d->plant_named = false;
+}
+
 }  // namespace
 
 // Kernels with scratch memory (spills, the frames of called generated functions) all go to that shared stream too.  The
@@ -347,7 +366,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
-                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params"};
+                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -608,6 +627,7 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
     if(d->log_x) hipFree(d->log_x);
     if(d->log_u) hipFree(d->log_u);
     if(d->log_c) hipFree(d->log_c);
+    plant_release(d);
     for(double *p : d->param_bufs) hipFree(p);
     if(d->P.p) hipFree(d->P.p);
     if(d->staging) hipFree(d->staging);
@@ -1320,6 +1340,100 @@ int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {
         if(!WAVE_MAP) hipLaunchKernelGGL(k_to_dev, grid1(n, 256), dim3(256), 0, d->stream, x0, d->P.f[ILQG_F_X], d->B, d->Bp, 1, NX, NX);
     }
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The plants of a closed loop (k_plant.inc).  k_plant runs where k_policy runs: on the stream of the roll-out family,
+// between the two hand-overs with the context's stream, so behind the iteration that made the plan and in front of the
+// k_shift_* that moves it.
+// ---------------------------------------------------------------------------------------------------------------------
+int ilqg_dev_plant_begin(ilqg_dev_t *d, int rounds, int steps, const double *x_plant, int n_named, const int *named, const double *values,
+                         const double *disturbance) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    if(rounds < 1 || steps < 1 || steps >= d->N) {
+        g_err = "ilqg_dev_plant_begin: need rounds >= 1 and 1 <= steps < n_hor";
+        return 1;
+    }
+    PolicyParamMap map;
+    if(n_named < 0 || (n_named > 0 && !policy_param_map(n_named, named, values, map))) {
+        if(n_named < 0) g_err = "ilqg_dev_plant_begin: n_names must not be negative";
+        return 1;
+    }
+    if(ilqg_dev_log_begin(d, rounds, steps)) return 1;  // (synchronises the context's stream)
+    if(d->roll) HIP_TRY(hipStreamSynchronize(d->roll));
+    plant_release(d);
+    const size_t B = (size_t)d->B, per = B * (size_t)rounds * (size_t)steps;
+    HIP_TRY(hipMalloc((void **)&d->plant_xp, B * NX * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&d->plant_failed, B * sizeof(int)));
+    HIP_TRY(hipMalloc((void **)&d->plant_cost, B * (size_t)rounds * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(d->plant_failed, 0, B * sizeof(int), d->stream));
+    // (what a failed plant leaves unwritten reaches the host as zeros)
+    HIP_TRY(hipMemsetAsync(d->log_x, 0, per * NX * sizeof(double), d->stream));
+    HIP_TRY(hipMemsetAsync(d->log_u, 0, per * NU * sizeof(double), d->stream));
+    HIP_TRY(hipMemsetAsync(d->plant_cost, 0, B * (size_t)rounds * sizeof(double), d->stream));
+    if(n_named > 0) {
+        d->plant_map = map;
+        d->plant_named = true;
+        HIP_TRY(hipMalloc((void **)&d->plant_values, B * (size_t)map.W * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(d->plant_values, values, B * (size_t)map.W * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    }
+    if(disturbance) {
+        HIP_TRY(hipMalloc((void **)&d->plant_dist, per * NX * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(d->plant_dist, disturbance, per * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    }
+    if(x_plant) HIP_TRY(hipMemcpyAsync(d->plant_xp, x_plant, B * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    else if(launch_head(d, 1, d->plant_xp, nullptr, nullptr, nullptr, nullptr)) return 1;  // x_0 of every plan, where it lives
+    HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
+    return 0;
+}
+
+int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    if(!d->plant_xp || !d->log_x || round < 0 || round >= d->log_rounds) {
+        g_err = "ilqg_dev_plant_advance: no such round (ilqg_dev_plant_begin)";
+        return 1;
+    }
+    const int steps = d->log_steps, rounds = d->log_rounds;
+    if(roll_enter(d)) return 1;
+    {
+        Timed t(d, ILQG_K_PLANT, roll_stream(d));
+        if(d->plant_named)
+            hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
+                               d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps, rounds * steps,
+                               round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c, (const double *)d->plant_values, d->plant_map);
+        else
+            hipLaunchKernelGGL(k_plant<false>, grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps,
+                               feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps, rounds * steps, round, rounds,
+                               d->log_x, d->log_u, d->plant_cost, d->log_c);
+    }
+    HIP_TRY(hipGetLastError());
+    return roll_leave(d);
+}
+
+int ilqg_dev_plant_put_x0(ilqg_dev_t *d) {
+    if(!d->plant_xp) {
+        g_err = "ilqg_dev_plant_put_x0: no plants (ilqg_dev_plant_begin)";
+        return 1;
+    }
+    return ilqg_dev_put_x0_device(d, d->plant_xp);
+}
+
+int ilqg_dev_plant_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!d->plant_xp || !d->log_x) {
+        g_err = "ilqg_dev_plant_read: no plants (ilqg_dev_plant_begin)";
+        return 1;
+    }
+    const size_t B = (size_t)d->B;
+    if(x_plant) HIP_TRY(hipMemcpyAsync(x_plant, d->plant_xp, B * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(cost_applied) HIP_TRY(hipMemcpyAsync(cost_applied, d->plant_cost, B * (size_t)d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(ok) HIP_TRY(hipMemcpyAsync(ok, d->plant_failed, B * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    if(ilqg_dev_log_read(d, x, u, plan_cost)) return 1;  // (waits for the context's stream)
+    if(ok)
+        for(size_t b = 0; b < B; b++) ok[b] = ok[b] ? 0 : 1;  // the device keeps failure flags
     return 0;
 }
 

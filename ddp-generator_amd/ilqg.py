@@ -195,10 +195,61 @@ def _policy_param_tensors(problem, params, B, R, device):
     return cols, 1 if forms[0] else 0
 
 
+def _plant_array(a, shape, what):
+    """a host array argument of receding_plant as C-contiguous doubles of that shape; refused: a tensor on the device, a
+    dtype that is no real number, another shape"""
+    if _is_cuda(a):
+        raise IlqgError("receding_plant: %s is a tensor on the device: the loop takes host memory (numpy arrays)" % what)
+    a = np.asarray(a)
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise IlqgError("receding_plant: %s has dtype %s, expected real numbers (float64)" % (what, a.dtype))
+    if tuple(a.shape) != tuple(shape):
+        raise IlqgError("receding_plant: %s has shape %s, expected %s" % (what, tuple(a.shape), tuple(shape)))
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _plant_param_rows(problem, params, B):
+    """(names, values [B, W]) for ilqg_batch_receding_plant: the named parameters one behind the other in dict order, each
+    array [B, size] (the last axis may be left out for size 1); refused here as the library refuses them: a name that is
+    no parameter, and one with a value per time step"""
+    if not isinstance(params, dict) or not params:
+        raise IlqgError("receding_plant: params must be a non-empty dict of parameter name -> array [B, size], or None for a plant that is the model")
+    known = dict(problem.params)
+    cols = []
+    for name, a in params.items():
+        if name not in known:
+            raise IlqgError("receding_plant: params: Parameter name '%s' is not member of parameters struct." % name)
+        if known[name] < 1:
+            raise IlqgError("receding_plant: params: '%s' has one value per time step; per-time-step parameters stay shared by planner and plant" % name)
+        size, what = known[name], "params['%s']" % name
+        if size == 1 and not _is_cuda(a) and np.ndim(a) == 1:
+            a = np.asarray(a)[:, None]
+        cols.append(_plant_array(a, (B, size), what))
+    return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1))
+
+
+def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant, params, disturbance):
+    """BatchSolver.receding_plant / MultiSolver.receding_plant: the checks, the arrays and the one library call"""
+    B, nx, nu = solver.B, solver.problem.nx, solver.problem.nu
+    for what, v in (("rounds", rounds), ("steps", steps), ("iterations", iterations)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise IlqgError("receding_plant: %s must be an integer, not %r" % (what, v))
+    r, n = max(int(rounds), 0), max(int(rounds), 0) * max(int(steps), 0)
+    xp = None if x_plant is None else _plant_array(x_plant, (B, nx), "x_plant").copy()
+    dist = None if disturbance is None else _plant_array(disturbance, (B, n, nx), "disturbance")
+    names, values = (None, None) if params is None else _plant_param_rows(solver.problem, params, B)
+    out = dict(x=np.zeros((B, n, nx)), u=np.zeros((B, n, nu)), cost=np.zeros((B, r)), plan_cost=np.zeros((B, r)), ok=np.zeros(B, dtype=np.int32),
+               x_plant=xp)
+    solver._ck(_receding_entry(solver.lib, entry)(solver.h, int(rounds), int(steps), int(iterations), 1 if feedback else 0, _address(xp),
+                                                  0 if names is None else len(names), names, _address(values), _address(dist),
+                                                  *[_address(out[k]) for k in ("x", "u", "cost", "plan_cost", "ok")]))
+    return out
+
+
 def _receding_entry(lib, name):
     """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift, ilqg_batch_head / _head_device / _shift_device /
     _shift_param / ilqg_multi_head, ilqg_batch_policy_rollout / _policy_rollout_device / ilqg_multi_policy_rollout and their
-    _params forms, of a problem library; one built before they existed (a pair compiled out of tree and
+    _params forms, ilqg_batch_receding_plant / ilqg_multi_receding_plant, of a problem library; one built before they existed (a pair compiled out of tree and
     not rebuilt since) still loads and solves, and says so when they are asked for"""
     if not hasattr(lib, name):
         raise IlqgError("this problem library was built before %s existed: rebuild it (make -C ddp-generator_amd/csrc)" % name)
@@ -289,6 +340,9 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_policy_rollout_params.argtypes = named
         lib.ilqg_batch_policy_rollout_params_device.argtypes = named + [v]
         lib.ilqg_multi_policy_rollout_params.argtypes = named
+    if hasattr(lib, "ilqg_batch_receding_plant"):  # (and for the closed loop of planner and plant)
+        lib.ilqg_batch_receding_plant.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, v, v, v, v, v, v]
+        lib.ilqg_multi_receding_plant.argtypes = lib.ilqg_batch_receding_plant.argtypes
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -534,6 +588,24 @@ class BatchSolver:
                    cost=np.zeros((self.B, max(int(rounds), 0))))
         self._ck(_receding_entry(self.lib, "ilqg_batch_receding")(self.h, int(rounds), int(steps), int(iterations), out["x"], out["u"], out["cost"]))
         return out
+
+    def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None):
+        """the closed loop of planner and plant on the GPU for `rounds` control intervals (ilqg_batch_receding_plant):
+        rounds x { iterate(iterations); every trajectory's plant advances `steps` steps from ITS OWN state under the plan's
+        policy, u = u_nom_k [+ L_k (x_plant - x_nom_k) if feedback], clamped, through the problem's dynamics and cost under
+        the PLANT's parameters, and behind each step disturbance[b, round*steps + k] is added to its state;
+        shift(steps, x0 = the plants' states) }.
+        x_plant [B,nx]: the plants' states at the start (None: every plan's x_0).  params = {name: array [B,size]} (the last
+        axis may be left out for size 1): the plant of trajectory b runs under the batch's parameters with every named
+        fixed-size parameter replaced by array[b] (None: the plant is the model); the planner keeps the batch's parameters,
+        which do not change.  disturbance [B,rounds*steps,nx] or None.  Everything is host memory, sent once; the logs come
+        back once: dict(x [B,rounds*steps,nx] the plant's state each control was applied at, u [B,rounds*steps,nu] the
+        clamped control applied, cost [B,rounds] the sum of the round's running costs under the plant's parameters,
+        plan_cost [B,rounds] the cost of the plan the round applied, ok [B] int32 (0: a step of that plant met NaN / Inf; it
+        stayed at its last finite state and its later entries are unspecified), x_plant [B,nx] the plants' states behind
+        the last round, or None where x_plant was None).  The gains behind an accepted step are those about the previous
+        nominal trajectory (see policy_rollout)."""
+        return _receding_plant(self, "ilqg_batch_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance)
 
     def solve_stream(self, x0, u0, with_trajectories=False):
         """a stream of len(x0) starts through this batch's slots (ilqg_batch_solve_stream): dict of cost, status, iterations
@@ -786,6 +858,10 @@ class MultiSolver:
         self._ck(_receding_entry(self.lib, "ilqg_multi_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
                                                                         *[_address(out.get(k)) for k in ("cost", "ok", "x_end", "x", "u")]))
         return out
+
+    def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None):
+        """BatchSolver.receding_plant of every shard, one shard after the other (ilqg_multi_receding_plant), numpy arrays"""
+        return _receding_plant(self, "ilqg_multi_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance)
 
     def solve(self):
         self._ck(self.lib.ilqg_multi_solve(self.h))

@@ -206,6 +206,45 @@ int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double
 int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
                                             const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
                                             double *x, double *u, void *stream);
+/* THE CLOSED LOOP OF PLANNER AND PLANT, resident on the device for `rounds` control intervals — ilqg_batch_receding with a
+ * plant that has a state of its own, may differ from the model and may be disturbed: what closed-loop cost the controllers
+ * reach when the wheelbase is 5 % off and the state is pushed at every step.  Each of the `rounds` rounds is
+ *   (1) ilqg_batch_iterate(c, iterations);
+ *   (2) the plant of every trajectory b advances `steps` steps from ITS OWN state xp: for k = 0 .. steps-1
+ *           u = u_nom_k  [+ L_k (xp - x_nom_k)  if feedback],
+ *       the policy being the one ilqg_batch_head hands out (the current plan where it lives and the gains stored with it;
+ *       BEHIND AN ACCEPTED STEP THE GAINS ARE THOSE ABOUT THE PREVIOUS NOMINAL TRAJECTORY, see ilqg_batch_policy_rollout;
+ *       alpha = 0: l is not used), then the step of the reference's forward_pass (iLQG_func.tem:121-185: calcXVariableAux,
+ *       clampU, calcXUVariableAux, ddpf, ddpL, time index k) with the multipliers and penalty weights trajectory b has,
+ *       evaluated under THE PLANT'S PARAMETERS, then  xp <- x_next + disturbance[b][round*steps + k];
+ *   (3) ilqg_batch_shift(c, steps, x0_new = xp, u_tail = NULL), the states never leaving the device.
+ * The planner stays under the batch's parameters throughout, and they are unchanged afterwards.
+ * The plant's parameters are the batch's fixed-size parameters with the named ones replaced by row b of values [B][W]:
+ * names, their order, W and the refusals are those of ilqg_batch_policy_rollout_params with n_starts = 1 and shared = 0.
+ * n_names = 0 (names and values are then not read): the plant is the model.  disturbance [B][rounds*steps][N_X], or NULL:
+ * none (nothing is added, not even a zero).
+ * x_plant [B][N_X]: the plants' states on entry and, on return, behind the last round; NULL: every plant starts from its
+ * plan's x_0 and no final state is returned.
+ * Logs (host memory, any of them NULL): x_applied [B][rounds*steps][N_X] the plant's state each control was applied at,
+ * u_applied [B][rounds*steps][N_U] the CLAMPED control that was applied, cost_applied [B][rounds] the sum of the round's
+ * running costs (ct.c of ddpL, from 0.0 in step order, under the plant's parameters, multipliers and penalty weights as
+ * above), plan_cost [B][rounds] the cost of the plan the round applied (what ilqg_batch_receding logs as cost), ok [B].
+ * FAILURE IS PER TRAJECTORY: a step whose guards fail (forward_pass would return 0: a guarded value is NaN or Inf) or
+ * behind which the disturbed state is not finite sets ok[b] = 0 for the rest of the call.  That plant no longer advances:
+ * it stays at its last finite state, the planner goes on re-planning from it, and its later log entries and cost_applied
+ * are unspecified.  A start that is not finite fails at once.  No other trajectory's results change by a bit.
+ * Refused with the argument named in the error text, before anything is launched, allocated or changed: rounds < 1,
+ * iterations < 0, steps outside 1 .. n_hor-1, a problem with a per-time-step parameter (as ilqg_batch_receding), n_names < 0,
+ * n_names > 0 with names or values NULL, a name that is no parameter, a per-time-step parameter, a name given twice.
+ * All outputs NULL is NOT a no-op: the batch advances.
+ * Memory: everything is host memory.  values, disturbance and x_plant go up once before the first round; the logs, ok and
+ * the final states come down once behind the last; between rounds the host waits for nothing and copies nothing. */
+int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback,
+                              double *x_plant /* [B][N_X] in/out, or NULL */,
+                              int n_names, const char *const *names, const double *values /* [B][W] */,
+                              const double *disturbance /* [B][rounds*steps][N_X] or NULL */,
+                              double *x_applied, double *u_applied /* [B][rounds*steps][N_X] / [N_U] */,
+                              double *cost_applied, double *plan_cost /* [B][rounds] each */, int *ok /* [B] */);
 /* The window of ONE per-time-step parameter (size -1) moves `steps` values on: p'[k] = p[k + steps], the last `steps`
  * values from tail [steps] (host), or p[n_hor] held if tail is NULL.  0 <= steps <= n_hor.  Exactly what
  * ilqg_batch_set_param(c, name, [p[steps:], tail], n_hor + 1) gives, without re-allocating or re-sending the table: the
@@ -309,6 +348,10 @@ int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, d
 /* ilqg_batch_policy_rollout_params per shard (host memory): values is offset by the shard's first trajectory unless shared */
 int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                      int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+/* ilqg_batch_receding_plant per shard, one shard after the other (host memory): every [B]... array is offset by the shard's first trajectory */
+int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
+                              double *cost_applied, double *plan_cost, int *ok);
 int ilqg_multi_iterate(ilqg_multi_t *m, int n);   /* asynchronous on every device; the devices are served in turn */
 int ilqg_multi_solve(ilqg_multi_t *m);
 int ilqg_multi_sync(ilqg_multi_t *m);

@@ -3,6 +3,7 @@
 
     python tools/receding_profile.py [--config headline|config5|both] [--repeats 10] [--steps 10] [--warmup 20]
     python tools/receding_profile.py --loop external [--config ...] [--repeats 10] [--steps 1] [--iterations 2]
+    python tools/receding_profile.py --loop plant [--config ...] [--repeats 10] [--steps 1] [--iterations 2] [--rounds 5]
 
 One process per invocation.  After `--warmup` iterations the two re-plans ALTERNATE; each is timed by the host clock
 between two device synchronisations, and two solver iterations run between re-plans so that every one of them finds the
@@ -15,6 +16,17 @@ x_meas) and with the heads and x_meas staying on the GPU as torch tensors (head(
 plant is trivial: x_meas = x[steps] of the plan + noise (a random walk of x_meas where the form does not read x).  The
 forms ALTERNATE in one process.  Per form and repeat two host-clock figures between two device synchronisations: the
 whole interval with nothing waited for inside it, and what comes behind iterate() alone (the overhead).
+
+--loop plant: the closed loop of planner and plant under a plant whose parameters are 5 % off and whose state is disturbed
+at every step, `--rounds` control intervals per loop, in three forms that ALTERNATE in one process:
+    receding_plant   BatchSolver.receding_plant: one call, the loop on the device (k_plant)
+    composed         the same loop driven from Python out of the public device entries: policy_rollout(device=True, params=...)
+                     with one start per trajectory and whole roll-outs, a torch add for the disturbance, shift(cuda tensors)
+    receding         BatchSolver.receding: the model loop, which has no plant (nothing is measured, no gain is used)
+Per form and repeat two host-clock figures between two device synchronisations, both divided by the rounds: the whole loop
+with `--iterations` solver iterations per round, and the loop with 0 iterations per round behind one iterate() — what a
+round costs behind its iterations (the overhead).  receding_plant's figures include its one upload of the tables and its one
+download of the logs, receding's its one download.  k_plant's own time is HIP events.
 """
 import argparse
 import os
@@ -176,13 +188,99 @@ def run_external(ilqg, synth, config, repeats, steps, warmup, iterations):
     s.close()
 
 
+def run_plant(ilqg, synth, config, repeats, steps, warmup, iterations, rounds):
+    import torch
+    if config == "headline":
+        problem, fd, B, N, params, names = "carparking", 0, 65536, 500, ilqg.CAR_PARAMS, ("limA", "d", "cf", "cx")
+        x0, u0 = synth.car_batch(B, N)
+    else:
+        problem, fd, B, N, params, names = "synth16x8", 1, 16384, 1000, synth.SYNTH16_PARAMS, ("qf", "c", "lim")
+        x0, u0 = synth.synth16_batch(B, N)
+    s = ilqg.BatchSolver(problem, fd, batch=B, n_hor=N, params=params, opts=dict(max_iter=1 << 20))
+    nx, nu = s.problem.nx, s.problem.nu
+    print("== %s: %s FULL_DDP=%d, %d trajectories, N = %d, %d round(s) per loop, %d step(s) applied and %d iteration(s) per round, %d stream group(s), %s mapping" % (
+        config, problem, fd, B, N, rounds, steps, iterations, s.groups(), "wave" if s.problem.wave_mapping else "lane"))
+    rng = np.random.default_rng(1)
+    rows = {n: np.asarray(params[n], dtype=np.float64).reshape(-1) * (1.0 + 0.05 * rng.standard_normal((B, np.size(params[n])))) for n in names}
+    W = sum(t.shape[1] for t in rows.values())
+    w = 1e-3 * rng.standard_normal((B, rounds * steps, nx))
+    rows_t = {n: torch.from_numpy(t[:, None].copy()).cuda() for n, t in rows.items()}
+    w_t = torch.from_numpy(np.ascontiguousarray(w.transpose(1, 0, 2))).cuda()  # [rounds * steps][B][nx]
+    state = {}
+
+    def start():  # every loop begins with plants at their plans' x_0
+        state["xp"] = s.head(1)["x"][:, 0].copy()
+
+    def plant(k):
+        s.receding_plant(rounds, steps, k, True, state["xp"], rows, w)
+
+    def composed(k):
+        xp = torch.from_numpy(state["xp"]).cuda()
+        for r in range(rounds):
+            s.iterate(k)
+            o = s.policy_rollout(xp[:, None].contiguous(), alpha=0.0, feedback=True, trajectories=True, device=True, params=rows_t)
+            xp = o["x"][:, 0, steps] + w_t[r * steps + steps - 1]  # (steps > 1: the disturbances inside a roll-out are left out)
+            state["logs"] = (o["x"][:, 0, :steps], o["u"][:, 0, :steps])
+            s.shift(steps, xp.contiguous())
+
+    def model(k):
+        s.receding(rounds, steps, k)
+
+    forms = (("receding_plant (k_plant, one call)", plant), ("composed from policy_rollout / torch / shift", composed), ("receding (no plant)", model))
+
+    def sync():
+        torch.cuda.synchronize()
+        s.sync()
+
+    s.init(x0, u0)
+    s.iterate(warmup)
+    for _, f in forms:  # once untimed: the logs' and staging buffers, torch's allocator
+        start()
+        f(iterations)
+    sync()
+    s.timing(True)
+    whole, over = {n: [] for n, _ in forms}, {n: [] for n, _ in forms}
+    for r in range(repeats):
+        for name, f in forms:
+            start()
+            sync()
+            t0 = time.perf_counter()
+            f(iterations)
+            sync()
+            whole[name].append(1e3 * (time.perf_counter() - t0) / rounds)
+            s.iterate(iterations)  # the first round of the overhead loop finds the batch as a round behind its iterations does
+            start()
+            sync()
+            t0 = time.perf_counter()
+            f(0)
+            sync()
+            over[name].append(1e3 * (time.perf_counter() - t0) / rounds)
+    kt = s.kernel_times()
+    s.timing(False)
+    for name, _ in forms:
+        print("%-48s per round  %s" % (name, spread(whole[name])))
+        print("%-48s overhead   %s" % ("", spread(over[name])))
+    new, comp, base = (np.median(over[n]) for n, _ in forms)
+    n, ms = kt["k_plant"]
+    per_launch = ms / max(n, 1)
+    print("k_plant: %d launches, %.4f ms per launch (%d per round: one per stream group); the table is %d doubles per trajectory" % (n, per_launch, s.groups(), W))
+    print("overhead per round, medians: receding_plant %.3f ms, composed %.3f ms (%.1f x), receding %.3f ms; receding_plant - receding = %.3f ms against "
+          "%.3f ms of k_plant launches per round" % (new, comp, comp / new, base, new - base, per_launch * s.groups()))
+    n, ms = kt["k_policy_params"]
+    print("k_policy_params (composed form): %d launches, %.3f ms per launch; k_shift %.3f ms, k_rollout[init] %.3f ms per launch (every form)" % (
+        n, ms / max(n, 1), kt["k_shift"][1] / max(kt["k_shift"][0], 1), kt["k_rollout[init]"][1] / max(kt["k_rollout[init]"][0], 1)))
+    s.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both", choices=("headline", "config5", "both"))
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--steps", type=int, default=None, help="steps per shift (default 10; 1 with --loop external)")
-    ap.add_argument("--loop", default="replan", choices=("replan", "external"), help="external: the control interval of a caller with its own plant")
-    ap.add_argument("--iterations", type=int, default=2, help="--loop external: solver iterations per control interval")
+    ap.add_argument("--steps", type=int, default=None, help="steps per shift (default 10; 1 with --loop external / plant)")
+    ap.add_argument("--loop", default="replan", choices=("replan", "external", "plant"),
+                    help="external: the control interval of a caller with its own plant; plant: the closed loop of planner and plant on the device")
+    ap.add_argument("--iterations", type=int, default=2, help="--loop external / plant: solver iterations per control interval")
+    ap.add_argument("--rounds", type=int, default=5, help="--loop plant: control intervals per timed loop")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--between", type=int, default=2, help="solver iterations between two re-plans")
     a = ap.parse_args()
@@ -192,6 +290,8 @@ def main():
     for config in (("headline", "config5") if a.config == "both" else (a.config,)):
         if a.loop == "external":
             run_external(ilqg, synth, config, a.repeats, a.steps or 1, a.warmup, a.iterations)
+        elif a.loop == "plant":
+            run_plant(ilqg, synth, config, a.repeats, a.steps or 1, a.warmup, a.iterations, a.rounds)
         else:
             run(ilqg, synth, config, a.repeats, a.steps or 10, a.warmup, a.between)
 
