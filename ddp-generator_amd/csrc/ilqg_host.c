@@ -611,39 +611,6 @@ static int policy_args(ilqg_batch_t *c, const char *who, int n_starts, const dou
 }
 #define POLICY_AT(p, w) ((p) ? (p) + (size_t)c->first[g] * (size_t)n_starts * (w) : NULL)
 
-int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                              double *x_end, double *x, double *u) {
-    int g;
-    if(policy_args(c, "ilqg_batch_policy_rollout", n_starts, x0)) return 1;
-    if(!cost && !ok && !x_end && !x && !u) return 0;
-    if(push_config(c)) return 1;
-    EACH_GROUP(g)
-        if(ilqg_dev_policy_rollout_host(c->dev[g], n_starts, POLICY_AT(x0, N_X), alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1),
-                                        POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
-            return fail(c, "policy_rollout");
-    return 0;
-}
-
-int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                                     double *x_end, double *x, double *u, void *stream) {
-    int g;
-    if(policy_args(c, "ilqg_batch_policy_rollout_device", n_starts, x0)) return 1;
-    if(ilqg_dev_check_device_ptr(c->dev[0], x0, "x0") || (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")) ||
-       (ok && ilqg_dev_check_device_ptr(c->dev[0], ok, "ok")) || (x_end && ilqg_dev_check_device_ptr(c->dev[0], x_end, "x_end")) ||
-       (x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) || (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u")))
-        return fail(c, "ilqg_batch_policy_rollout_device");
-    if(!cost && !ok && !x_end && !x && !u) return 0;
-    if(push_config(c)) return 1;
-    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "policy_rollout: stream");
-    EACH_GROUP(g) {
-        if(ilqg_dev_policy_rollout(c->dev[g], n_starts, POLICY_AT(x0, N_X), alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1),
-                                   POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
-            return fail(c, "policy_rollout");
-        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "policy_rollout: stream");
-    }
-    return 0;
-}
-
 /* The same roll-outs, roll-out (b, r) under a parameter set of its own (k_policy<true>): the batch's fixed-size parameters
  * with those of names[] replaced by row (b, r) of values.  The names are resolved here against paramdesc[] — named[i] = the
  * index of names[i], *width = W, the sum of their sizes — and everything is refused before anything is launched. */
@@ -695,43 +662,58 @@ static int policy_names(ilqg_batch_t *c, const char *who, int n_names, const cha
 }
 #define POLICY_VALUES_AT(w) (shared ? values : values + (size_t)c->first[g] * (size_t)n_starts * (size_t)(w))
 
-int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
-                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    int g, named[POLICY_MAX_NAMES], W;
-    if(policy_args(c, "ilqg_batch_policy_rollout_params", n_starts, x0)) return 1;
-    if(policy_names(c, "ilqg_batch_policy_rollout_params", n_names, names, values, named, &W)) return 1;
+/* The four entries below.  params: the _params forms (names resolved, at least one; else n_names is 0 here and names, values
+ * and shared are not read); on_device: the _device forms (device memory of the caller, in the order of its stream, no wait). */
+static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_device, int n_starts, const double *x0, int n_names,
+                          const char *const *names, const double *values, int shared, double alpha, int feedback, double *cost, int *ok,
+                          double *x_end, double *x, double *u, void *stream) {
+    const char *const what = params ? "policy_rollout_params" : "policy_rollout";
+    const char *const what_stream = params ? "policy_rollout_params: stream" : "policy_rollout: stream";
+    int g, named[POLICY_MAX_NAMES], W = 0;
+    if(policy_args(c, who, n_starts, x0)) return 1;
+    if(params && policy_names(c, who, n_names, names, values, named, &W)) return 1;
+    if(on_device &&
+       (ilqg_dev_check_device_ptr(c->dev[0], x0, "x0") || (params && ilqg_dev_check_device_ptr(c->dev[0], values, "values")) ||
+        (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")) || (ok && ilqg_dev_check_device_ptr(c->dev[0], ok, "ok")) ||
+        (x_end && ilqg_dev_check_device_ptr(c->dev[0], x_end, "x_end")) || (x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) ||
+        (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u"))))
+        return fail(c, who);
     if(!cost && !ok && !x_end && !x && !u) return 0;
     if(push_config(c)) return 1;
-    EACH_GROUP(g)
-        if(ilqg_dev_policy_rollout_params_host(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, POLICY_VALUES_AT(W), shared, alpha, feedback,
-                                               POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X),
-                                               POLICY_AT(u, (size_t)c->N * N_U)))
-            return fail(c, "policy_rollout_params");
+    if(on_device) {
+        EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, what_stream);
+    }
+    EACH_GROUP(g) {
+        if((on_device ? ilqg_dev_policy_rollout : ilqg_dev_policy_rollout_host)(
+               c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared, alpha, feedback,
+               POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
+            return fail(c, what);
+        if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, what_stream);
+    }
     return 0;
+}
+
+int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                              double *x_end, double *x, double *u) {
+    return policy_rollout(c, "ilqg_batch_policy_rollout", 0, 0, n_starts, x0, 0, NULL, NULL, 0, alpha, feedback, cost, ok, x_end, x, u, NULL);
+}
+
+int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                                     double *x_end, double *x, double *u, void *stream) {
+    return policy_rollout(c, "ilqg_batch_policy_rollout_device", 0, 1, n_starts, x0, 0, NULL, NULL, 0, alpha, feedback, cost, ok, x_end, x, u, stream);
+}
+
+int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    return policy_rollout(c, "ilqg_batch_policy_rollout_params", 1, 0, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok, x_end,
+                          x, u, NULL);
 }
 
 int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
                                             const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
                                             double *x, double *u, void *stream) {
-    int g, named[POLICY_MAX_NAMES], W;
-    if(policy_args(c, "ilqg_batch_policy_rollout_params_device", n_starts, x0)) return 1;
-    if(policy_names(c, "ilqg_batch_policy_rollout_params_device", n_names, names, values, named, &W)) return 1;
-    if(ilqg_dev_check_device_ptr(c->dev[0], x0, "x0") || ilqg_dev_check_device_ptr(c->dev[0], values, "values") ||
-       (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")) || (ok && ilqg_dev_check_device_ptr(c->dev[0], ok, "ok")) ||
-       (x_end && ilqg_dev_check_device_ptr(c->dev[0], x_end, "x_end")) || (x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) ||
-       (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u")))
-        return fail(c, "ilqg_batch_policy_rollout_params_device");
-    if(!cost && !ok && !x_end && !x && !u) return 0;
-    if(push_config(c)) return 1;
-    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "policy_rollout_params: stream");
-    EACH_GROUP(g) {
-        if(ilqg_dev_policy_rollout_params(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, POLICY_VALUES_AT(W), shared, alpha, feedback,
-                                          POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X),
-                                          POLICY_AT(u, (size_t)c->N * N_U)))
-            return fail(c, "policy_rollout_params");
-        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "policy_rollout_params: stream");
-    }
-    return 0;
+    return policy_rollout(c, "ilqg_batch_policy_rollout_params_device", 1, 1, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok,
+                          x_end, x, u, stream);
 }
 
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
@@ -1806,36 +1788,34 @@ int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l,
             return multi_fail(m, g);
     return 0;
 }
-int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                              double *x_end, double *x, double *u) {
-    int g;
-    const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
-    EACH_SHARD(g) {
-        const size_t at = (size_t)m->first[g] * r;
-        if(ilqg_batch_policy_rollout(m->shard[g], n_starts, x0 ? x0 + at * N_X : NULL, alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL,
-                                     x_end ? x_end + at * N_X : NULL, x ? x + at * (size_t)(m->N + 1) * N_X : NULL,
-                                     u ? u + at * (size_t)m->N * N_U : NULL))
-            return multi_fail(m, g);
-    }
-    return 0;
-}
-int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
-                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+/* both entries below: every shard's part through the worker of ilqg_batch_policy_rollout / ilqg_batch_policy_rollout_params */
+static int multi_policy_rollout(ilqg_multi_t *m, const char *who, int params, int n_starts, const double *x0, int n_names, const char *const *names,
+                                const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
+                                double *u) {
     int g, i, k;
     size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
     const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
-    if(names && values && !shared)
+    if(params && names && values && !shared)
         for(i = 0; i < n_names; i++)
             for(k = 0; names[i] && k < n_params; k++)
                 if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
     EACH_SHARD(g) {
         const size_t at = (size_t)m->first[g] * r;
-        if(ilqg_batch_policy_rollout_params(m->shard[g], n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
-                                            alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
-                                            x ? x + at * (size_t)(m->N + 1) * N_X : NULL, u ? u + at * (size_t)m->N * N_U : NULL))
+        if(policy_rollout(m->shard[g], who, params, 0, n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
+                          alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
+                          x ? x + at * (size_t)(m->N + 1) * N_X : NULL, u ? u + at * (size_t)m->N * N_U : NULL, NULL))
             return multi_fail(m, g);
     }
     return 0;
+}
+int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
+                              double *x_end, double *x, double *u) {
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout", 0, n_starts, x0, 0, NULL, NULL, 0, alpha, feedback, cost, ok, x_end, x, u);
+}
+int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                     int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_params", 1, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok,
+                                x_end, x, u);
 }
 int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,

@@ -776,6 +776,38 @@ __device__ __forceinline__ int run_guarded(Fn &&f, double *alone = nullptr) {
     return r;
 }
 
+// One guarded evaluation of a piece of the generated forward pass — the step or the final cost of a roll-out, f() = the
+// AND of its callbacks' return values — for every kernel of the forward-pass family.  The piece itself is straight-line
+// code: the callbacks' NaN / Inf guards and the huge-argument case of sin / cos are hooks (ilqg_hooks), tested once here.
+//   plain builds         f(); if an argument was beyond the fast sin / cos reduction (H.huge), once more through the
+//                        library (H.slow), with `nonfinite` put back to what it was BEFORE the second pass: what the fast
+//                        reduction made of such an argument is no finding of the guards.
+//   wave-uniform guards  run_guarded(f); sin / cos are calls there, `huge` is never read.  A lane that has failed
+//                        (okc == 0) stays out: its guards would fail the wavefront again.
+// f is the lambda AT the call site: the step's body moved into a function of its own changes what the inliner does in
+// the hot kernels (profiles/README.md).  The kernels' bit-for-bit identities (k_plant = k_policy = k_rollout in the
+// FMA-free builds) rest on this being the one text of the retry.
+template <class Fn>
+__device__ __forceinline__ int run_step(ilqg_hooks &H, int okc, Fn &&f) {
+    // (both in front of the #if, as k_rollout always had them: inside the plain branch, k_rollout<0> / <1> of the
+    // uniform-guard builds lose the store of `huge` — three instructions in the n = 16 pair library — and are other code)
+    const double nf0 = H.nonfinite;
+    H.huge = 0.0;
+    int r = 1;
+#if ILQG_UNIFORM_GUARDS
+    if(okc) r = run_guarded(f);
+#else
+    r = f();
+    if(H.huge != 0.0) {
+        H.nonfinite = nf0;
+        H.slow = 1.0;
+        r = f();
+        H.slow = 0.0;
+    }
+#endif
+    return r;
+}
+
 // Layout of the derivative-record fields (DER, FIN) of width W (doubles per step and trajectory):
 //   lane mapping: [step][tile of 64 trajectories][component][trajectory in tile] — k_derivs, lane = (trajectory,
 //                 step), writes and the backward kernel, lane = trajectory, reads one component as 512 contiguous

@@ -120,7 +120,7 @@ enum {
     ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head, ilqg_dev_head_device) */
     ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
-    ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout_params) */
+    ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout with a table) */
     ILQG_K_PLANT,    /* k_plant (ilqg_dev_plant_advance) */
     ILQG_K_COUNT
 };
@@ -189,30 +189,26 @@ int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double 
  * and penalty weights the trajectory has, and u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if feedback].
  * x0 [batch][R][N_X]; outputs, any of them NULL: cost [batch][R], ok [batch][R] (forward_pass's return value; where it is 0
  * the other outputs of that roll-out are unspecified), x_end [batch][R][N_X], x [batch][R][n_hor+1][N_X],
- * u [batch][R][n_hor][N_U] (the clamped controls applied).  Writes nothing of the solver's state.  ilqg_dev_policy_rollout
- * takes DEVICE memory, is asynchronous on the context's stream and waits for nothing; ilqg_dev_policy_rollout_host takes
- * host memory, stages through the context's staging buffer (which only grows) and waits once.  R >= 1; needs
- * ilqg_dev_set_params before it. */
-int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                            double *x_end, double *x, double *u);
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                                 double *x_end, double *x, double *u);
-/* The same roll-outs, each under problem parameters of its own (k_policy<true>): roll-out (b, r) evaluates every callback
- * with the context's fixed-size parameters, those of the n_named parameters named[] (indices into paramdesc[], each of
- * fixed size, no index twice — the caller has checked names; sizes and range are checked here) replaced by row (b, r) of
- * values: [batch][R][W], or with shared != 0 [R][W] for every trajectory, W = the sum of the named sizes, the named
- * parameters one behind the other in the order of named[].  The policy, multipliers, penalty weights and per-time-step
- * parameters are the context's.  Memory and stream rules as for the pair above; values lives where x0 lives. */
-int ilqg_dev_policy_rollout_params(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                                   double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
-int ilqg_dev_policy_rollout_params_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                                        double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+ * u [batch][R][n_hor][N_U] (the clamped controls applied).  Writes nothing of the solver's state.
+ * n_named = 0: under the context's parameters (k_policy<false>; named, values, shared are not read).  n_named > 0: each
+ * roll-out under problem parameters of its own (k_policy<true>): roll-out (b, r) evaluates every callback with the context's
+ * fixed-size parameters, those of the n_named parameters named[] (indices into paramdesc[], each of fixed size, no index
+ * twice — the caller has checked names; sizes and range are checked here) replaced by row (b, r) of values:
+ * [batch][R][W], or with shared != 0 [R][W] for every trajectory, W = the sum of the named sizes, the named parameters one
+ * behind the other in the order of named[].  The policy, multipliers, penalty weights and per-time-step parameters are the
+ * context's.  ilqg_dev_policy_rollout takes DEVICE memory (values lives where x0 lives), is asynchronous on the context's
+ * stream and waits for nothing; ilqg_dev_policy_rollout_host takes host memory, stages through the context's staging buffer
+ * (which only grows) and waits once.  R >= 1; needs ilqg_dev_set_params before it. */
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
+                            int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
+                                 int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
 /* The plant of a closed loop that stays on the device (k_plant.inc): `rounds` times { ilqg_dev_iterate; ilqg_dev_plant_advance;
  * ilqg_dev_shift(d, steps, 0); ilqg_dev_plant_put_x0; ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_plant_begin
  * and one ilqg_dev_plant_read — the caller's loop; nothing in it waits or copies.
  * begin (HOST memory in, all of it sent once; waits once): the plants' states x_plant [batch][N_X], or NULL = every plan's
  * x_0; the plants' parameters — the context's fixed-size ones with the n_named parameters named[] replaced by row b of
- * values [batch][W], names and W as in ilqg_dev_policy_rollout_params with R = 1 and shared = 0; n_named = 0: the
+ * values [batch][W], names and W as in ilqg_dev_policy_rollout with R = 1 and shared = 0; n_named = 0: the
  * context's own —; disturbance [batch][rounds*steps][N_X], added to the state behind each step, or NULL = none.  It also
  * sizes the logs (the rules of ilqg_dev_log_begin, whose log it takes) and clears the plants' failure flags.
  * rounds >= 1, 1 <= steps < n_hor.

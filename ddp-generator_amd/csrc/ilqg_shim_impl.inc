@@ -1233,50 +1233,26 @@ static const PolicyParamMap *policy_param_map(int n_named, const int *named, con
     }
     return &map;
 }
-static int launch_policy(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok, double *x_end,
-                         double *x, double *u) {
+// map == nullptr: k_policy<false>; else the same under the rows of `values` (device memory), k_policy<true>.  Each has its
+// own timing slot.
+static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, double alpha,
+                         int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     if(roll_enter(d)) return 1;
-    {
+    const dim3 grid = grid1((size_t)d->B * (size_t)R, ROLL_BLOCK);
+    if(!map) {
         Timed t(d, ILQG_K_POLICY, roll_stream(d));
-        hipLaunchKernelGGL(k_policy<false>, grid1((size_t)d->B * (size_t)R, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha,
-                           feedback ? 1 : 0, cost, ok, x_end, x, u);
-    }
-    HIP_TRY(hipGetLastError());
-    return roll_leave(d);
-}
-// the same under the rows of `values` (device memory): k_policy<true>
-static int launch_policy_params(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap &map, const double *values, int shared, double alpha,
-                                int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    if(roll_enter(d)) return 1;
-    {
+        hipLaunchKernelGGL(k_policy<false>, grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok,
+                           x_end, x, u);
+    } else {
         Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
-        hipLaunchKernelGGL((k_policy<true, const double *, int, PolicyParamMap>), grid1((size_t)d->B * (size_t)R, ROLL_BLOCK), dim3(ROLL_BLOCK), 0,
-                           roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, values, shared ? 1 : 0, map);
+        hipLaunchKernelGGL((k_policy<true, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0,
+                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, values, shared ? 1 : 0, *map);
     }
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
 }
 
-int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                            double *x_end, double *x, double *u) {
-    HIP_TRY(hipSetDevice(d->device));
-    NEED_PARAMS(d);
-    if(!policy_args_ok(d, R, x0)) return 1;
-    if(!cost && !ok && !x_end && !x && !u) return 0;
-    return launch_policy(d, R, x0, alpha, feedback, cost, ok, x_end, x, u);
-}
-
-int ilqg_dev_policy_rollout_params(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                                   double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    HIP_TRY(hipSetDevice(d->device));
-    NEED_PARAMS(d);
-    PolicyParamMap map;
-    if(!policy_args_ok(d, R, x0) || !policy_param_map(n_named, named, values, map)) return 1;
-    if(!cost && !ok && !x_end && !x && !u) return 0;
-    return launch_policy_params(d, R, x0, map, values, shared, alpha, feedback, cost, ok, x_end, x, u);
-}
-
-// the host forms: the starts, then with a map the table of values, then the outputs, in one piece of the staging buffer
+// the host form: the starts, then with a map the table of values, then the outputs, in one piece of the staging buffer
 static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, double alpha,
                                  int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     const size_t n = (size_t)d->B * (size_t)R;
@@ -1297,9 +1273,8 @@ static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const P
     if(map && stage_in(d, (char *)dev + val_off, pin ? (char *)pin + val_off : nullptr, values, val_bytes)) return 1;
     void *dv[5];
     for(int i = 0; i < 5; i++) dv[i] = host[i] ? (void *)((char *)dev + off[i]) : nullptr;
-    if(map ? launch_policy_params(d, R, (const double *)dev, *map, (const double *)((char *)dev + val_off), shared, alpha, feedback, (double *)dv[0],
-                                  (int *)dv[1], (double *)dv[2], (double *)dv[3], (double *)dv[4])
-           : launch_policy(d, R, (const double *)dev, alpha, feedback, (double *)dv[0], (int *)dv[1], (double *)dv[2], (double *)dv[3], (double *)dv[4]))
+    if(launch_policy(d, R, (const double *)dev, map, (const double *)((char *)dev + val_off), shared, alpha, feedback, (double *)dv[0], (int *)dv[1],
+                     (double *)dv[2], (double *)dv[3], (double *)dv[4]))
         return 1;
     for(int i = 0; i < 5; i++) {
         if(!host[i]) continue;
@@ -1311,23 +1286,27 @@ static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const P
     return 0;
 }
 
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, double alpha, int feedback, double *cost, int *ok,
-                                 double *x_end, double *x, double *u) {
+// both entries: n_named == 0 = no table (k_policy<false>), else roll-out (b, r) under its row of `values`
+static int policy_rollout(ilqg_dev_t *d, bool on_host, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                          double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     HIP_TRY(hipSetDevice(d->device));
     NEED_PARAMS(d);
-    if(!policy_args_ok(d, R, x0)) return 1;
+    PolicyParamMap table;
+    const PolicyParamMap *map = nullptr;
+    if(!policy_args_ok(d, R, x0) || (n_named != 0 && !(map = policy_param_map(n_named, named, values, table)))) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
-    return policy_rollout_staged(d, R, x0, nullptr, nullptr, 0, alpha, feedback, cost, ok, x_end, x, u);
+    return on_host ? policy_rollout_staged(d, R, x0, map, values, shared, alpha, feedback, cost, ok, x_end, x, u)
+                   : launch_policy(d, R, x0, map, values, shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 
-int ilqg_dev_policy_rollout_params_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                                        double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    HIP_TRY(hipSetDevice(d->device));
-    NEED_PARAMS(d);
-    PolicyParamMap map;
-    if(!policy_args_ok(d, R, x0) || !policy_param_map(n_named, named, values, map)) return 1;
-    if(!cost && !ok && !x_end && !x && !u) return 0;
-    return policy_rollout_staged(d, R, x0, &map, values, shared, alpha, feedback, cost, ok, x_end, x, u);
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
+                            int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    return policy_rollout(d, false, R, x0, n_named, named, values, shared, alpha, feedback, cost, ok, x_end, x, u);
+}
+
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
+                                 int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    return policy_rollout(d, true, R, x0, n_named, named, values, shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {

@@ -163,8 +163,6 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
         if(!DMA) load_nominal<true, 1>(cur, qn);  // the next step's record is in flight while this one computes
         if(HAS_MUL) load_mul(P, k, b, mk);
         double xnext[NX];
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto step = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
@@ -177,13 +175,7 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
             r &= ddpL(&ct, k, &C.o);
             return r;
         };
-        int r = step();
-        if(H.huge != 0.0) {  // an argument beyond the fast sin/cos reduction: once more through the library
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = step();
-            H.slow = 0.0;
-        }
+        const int r = run_step(H, okc, step);
         okc &= r;
         csum += ct.c;
         if(DMA) {
@@ -209,8 +201,6 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
         multipliersFin_t mf;
         if(HAS_MUL) load_mul_fin(P, b, mf);
         init_final(&cf, &C.o);
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto fin = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) cf.x[i] = xc[i];
@@ -218,13 +208,7 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
             r &= ddpF(&cf, &C.o);
             return r;
         };
-        int r = fin();
-        if(H.huge != 0.0) {
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = fin();
-            H.slow = 0.0;
-        }
+        const int r = run_step(H, okc, fin);
         okc &= r;
         csum += cf.c;
         if(live) {

@@ -1,15 +1,14 @@
 // The plant of a closed loop on the device (ilqg_dev_plant_*, ilqg_batch_receding_plant).  Included by ilqg_kernels.hip
-// inside its anonymous namespace, behind k_policy.inc (load_policy_step, override_params, PolicyParamMap).
+// inside its anonymous namespace, behind k_policy.inc (load_policy_step, policy_control, override_params, PolicyParamMap).
 //
 // k_plant: the plant of trajectory b advances `steps` steps from ITS OWN state xp[b] under the policy of slot b — what
 // k_policy rolls out with alpha = 0: the current (x, u) where it lives (cur_x / cur_u) and the gains L of the packed
 // records —
 //     u_k = u_nom_k  [+ L_k (xp - x_nom_k)  if feedback, state by state in the template's order]
 // then the step of the template (iLQG_func.tem:121-185): calcXVariableAux, clampU, calcXUVariableAux, ddpf, ddpL, with the
-// multipliers and penalty weights slot b has now, and  xp <- x_next [+ w_k  if there is a disturbance table].  The step, the
-// huge-argument second pass of sin / cos and, in builds with wave-uniform guards, run_guarded are k_policy's, statement by
-// statement: in the FMA-free builds a step here has the bits of the same step of ilqg_dev_policy_rollout from the same
-// state.  k_plant<true> evaluates the callbacks under the PLANT's parameters: the context's fixed-size parameters with the
+// multipliers and penalty weights slot b has now, and  xp <- x_next [+ w_k  if there is a disturbance table].  The control
+// and the guarded step go through policy_control / run_step, which k_policy goes through: in the FMA-free builds a step
+// here has the bits of the same step of ilqg_dev_policy_rollout from the same state.  k_plant<true> evaluates the callbacks under the PLANT's parameters: the context's fixed-size parameters with the
 // mapped slots replaced by row b of `values` [B][W] (override_params with g = b; the n = 16 FMA-free builds read them from
 // memory, ILQG_POLICY_PARAMS_IN_MEMORY).  k_plant<false> has no table argument and no code for one.
 //
@@ -94,22 +93,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
         double xin[NX], uin[NU];
 #pragma unroll
         for(int i = 0; i < NX; i++) xin[i] = xc[i];
-#pragma unroll
-        for(int j = 0; j < NU; j++) uin[j] = cur.u[j];
-        if(use_K) {
-#pragma unroll
-            for(int i = 0; i < NX; i++) {
-                const double dx = xin[i] - cur.x[i];
-                if(WAVE_MAP) {
-                    const double *Kk = q.K + i * NU;
-#pragma unroll
-                    for(int j = 0; j < NU; j++) uin[j] += Kk[j] * dx;
-                } else {
-#pragma unroll
-                    for(int j = 0; j < NU; j++) uin[j] += cur.K[j + i * NU] * dx;
-                }
-            }
-        }
+        policy_control(uin, cur, q.K, xin, 0.0, false, use_K);
 
         // the next step's nominal data, in flight while the step computes (steps < N: step k + 1 <= N - 1 exists everywhere)
         load_policy_step(cur, qn, false, use_K);
@@ -121,8 +105,6 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
 
         if(HAS_MUL) load_mul(P, k, b, mk);
         double xnext[NX];
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto step = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
@@ -135,18 +117,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
             r &= ddpL(&ct, k, &C.o);
             return r;
         };
-        int r = 1;
-#if ILQG_UNIFORM_GUARDS
-        if(okc) r = run_guarded(step);
-#else
-        r = step();
-        if(H.huge != 0.0) {
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = step();
-            H.slow = 0.0;
-        }
-#endif
+        const int r = run_step(H, okc, step);
         csum += ct.c;
 #pragma unroll
         for(int i = 0; i < NX; i++) lx[at * NX + i] = ct.x[i];

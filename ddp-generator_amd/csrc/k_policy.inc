@@ -7,9 +7,9 @@
 // weights slot b has now, the per-time-step parameters as they stand, and
 //     u_k = u_nom_k  [+ alpha l_k  if alpha != 0]  [+ L_k (x_k - x_nom_k)  if feedback, state by state in the template's order]
 // then the step of the template: calcXVariableAux, clampU, calcXUVariableAux, ddpf, ddpL; the final step calcFVariableAux,
-// ddpF.  The step itself, the huge-argument second pass of sin / cos and, in builds with wave-uniform guards, run_guarded
-// are k_rollout's, statement by statement.  NOTHING of the batch is written: no field, scalar, status, location index or
-// multiplier, and no trajectory moves home.
+// ddpF.  Each is evaluated through run_step, as in k_rollout: the huge-argument second pass of sin / cos or, in builds with
+// wave-uniform guards, run_guarded.  The control law is policy_control (below).  NOTHING of the batch is written: no field,
+// scalar, status, location index or multiplier, and no trajectory moves home.
 //
 // Lanes.  One lane per roll-out, roll-out g = b * R + r with r fastest: R consecutive lanes share slot b and so every
 // address of the nominal data.  A load instruction of a wavefront touches the data of at most ceil(64 / R) + 1 slots
@@ -42,7 +42,35 @@ __device__ __forceinline__ void load_policy_step(NomStep &s, const NomPtrs &q, b
     }
 }
 
-// Per-roll-out problem parameters (ilqg_dev_policy_rollout_params).  k_policy<true> is the same roll-out with three more
+// The control law of a policy at state x (iLQG_func.tem:146-155), for k_policy and k_plant (alpha = 0, use_l = false):
+//     u = u_nom  [+ alpha l  if use_l]  [+ L (x - x_nom)  if use_K, state by state in the template's order]
+// K_here: L of this step where it is read in the wave mapping (too large to hold a step ahead); the lane mapping has it in
+// cur.  k_rollout and the fused search keep their own form (uf, selected on `feedback`): other arithmetic, and hot.
+__device__ __forceinline__ void policy_control(double (&uin)[NU], const NomStep &cur, const double *K_here, const double (&x)[NX], double alpha,
+                                               bool use_l, bool use_K) {
+#pragma unroll
+    for(int j = 0; j < NU; j++) uin[j] = cur.u[j];
+    if(use_l) {
+#pragma unroll
+        for(int j = 0; j < NU; j++) uin[j] = cur.u[j] + cur.l[j] * alpha;
+    }
+    if(use_K) {
+#pragma unroll
+        for(int i = 0; i < NX; i++) {
+            const double dx = x[i] - cur.x[i];
+            if(WAVE_MAP) {
+                const double *Kk = K_here + i * NU;
+#pragma unroll
+                for(int j = 0; j < NU; j++) uin[j] += Kk[j] * dx;
+            } else {
+#pragma unroll
+                for(int j = 0; j < NU; j++) uin[j] += cur.K[j + i * NU] * dx;
+            }
+        }
+    }
+}
+
+// Per-roll-out problem parameters (ilqg_batch_policy_rollout_params).  k_policy<true> is the same roll-out with three more
 // arguments — the caller's table `values`, [B][R][W] or with `shared` [R][W], and a by-value map of the ParamValues slots:
 // src[j] = the column of a row that replaces slot j, or -1 for a slot that keeps the batch's value.  Behind ILQG_CALLBACKS
 // every lane overrides the mapped slots of its PRIVATE ParamValues with row (shared ? r : g) of the table; the callbacks
@@ -142,26 +170,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
         double xin[NX], uin[NU];
 #pragma unroll
         for(int i = 0; i < NX; i++) xin[i] = xc[i];
-#pragma unroll
-        for(int j = 0; j < NU; j++) uin[j] = cur.u[j];
-        if(use_l) {
-#pragma unroll
-            for(int j = 0; j < NU; j++) uin[j] = cur.u[j] + cur.l[j] * alpha;
-        }
-        if(use_K) {
-#pragma unroll
-            for(int i = 0; i < NX; i++) {
-                const double dx = xin[i] - cur.x[i];
-                if(WAVE_MAP) {
-                    const double *Kk = q.K + i * NU;
-#pragma unroll
-                    for(int j = 0; j < NU; j++) uin[j] += Kk[j] * dx;
-                } else {
-#pragma unroll
-                    for(int j = 0; j < NU; j++) uin[j] += cur.K[j + i * NU] * dx;
-                }
-            }
-        }
+        policy_control(uin, cur, q.K, xin, alpha, use_l, use_K);
 
         // the next step's nominal data, in flight while the step computes (the records have a step N; the tiled U has not)
         if(k + 1 >= N) qn.u = q.u;
@@ -169,8 +178,6 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
 
         if(HAS_MUL) load_mul(P, k, b, mk);
         double xnext[NX];
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto step = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
@@ -183,18 +190,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
             r &= ddpL(&ct, k, &C.o);
             return r;
         };
-        int r = 1;
-#if ILQG_UNIFORM_GUARDS
-        if(okc) r = run_guarded(step);
-#else
-        r = step();
-        if(H.huge != 0.0) {
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = step();
-            H.slow = 0.0;
-        }
-#endif
+        const int r = run_step(H, okc, step);
         okc &= r;
         csum += ct.c;
         if(ox) {
@@ -216,8 +212,6 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
         multipliersFin_t mf;
         if(HAS_MUL) load_mul_fin(P, b, mf);
         init_final(&cf, &C.o);
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto fin = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) cf.x[i] = xc[i];
@@ -225,18 +219,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
             r &= ddpF(&cf, &C.o);
             return r;
         };
-        int r = 1;
-#if ILQG_UNIFORM_GUARDS
-        if(okc) r = run_guarded(fin);
-#else
-        r = fin();
-        if(H.huge != 0.0) {
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = fin();
-            H.slow = 0.0;
-        }
-#endif
+        const int r = run_step(H, okc, fin);
         okc &= r;
         csum += cf.c;
         if(ox) {

@@ -58,7 +58,7 @@ __device__ __forceinline__ void load_nominal(NomStep &s, const NomPtrs &q) {
 // of X and U per step size costs more HBM write time than the winner pass, and candidates of the compacted second
 // stage can only be written or copied back as scattered 8-byte pieces (DESIGN.md).
 // The time step itself is straight-line code: the generated callbacks' NaN/Inf guards and the
-// huge-argument case of sin/cos are hooks (see ilqg_hooks), tested once per step.
+// huge-argument case of sin/cos are hooks (see ilqg_hooks), tested once per step (run_step).
 enum { RK_GENERAL = 0, RK_INIT = 1, RK_COST = 2 };
 #ifdef ILQG_ROLLOUT_WAVES  // experiments: force that many wavefronts of the roll-out kernels per SIMD (register cap)
 #define ILQG_ROLLOUT_ATTR __attribute__((amdgpu_waves_per_eu(ILQG_ROLLOUT_WAVES)))
@@ -223,8 +223,6 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
         }
         // the step (iLQG_func.tem:160-176)
         double xnext[NX];
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto step = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
@@ -237,18 +235,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
             r &= ddpL(&ct, k, &C.o);
             return r;
         };
-        int r = 1;
-#if ILQG_UNIFORM_GUARDS
-        if(okc) r = run_guarded(step);  // a lane that has failed stays out: its guards would fail the wavefront again
-#else
-        r = step();
-        if(H.huge != 0.0) {  // an argument beyond the fast sin/cos reduction: once more through the library
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = step();
-            H.slow = 0.0;
-        }
-#endif
+        const int r = run_step(H, okc, step);
         okc &= r;
         csum += ct.c;
         // The step's results are stored right away, i.e. BEHIND the prefetch of the next step in issue order: the
@@ -298,8 +285,6 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
         double xin[NX];
 #pragma unroll
         for(int i = 0; i < NX; i++) xin[i] = cost_only ? q.x[i * CS] : xc[i];
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
         auto fin = [&]() {
 #pragma unroll
             for(int i = 0; i < NX; i++) cf.x[i] = xin[i];
@@ -307,18 +292,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
             r &= ddpF(&cf, &C.o);
             return r;
         };
-        int r = 1;
-#if ILQG_UNIFORM_GUARDS
-        if(okc) r = run_guarded(fin);
-#else
-        r = fin();
-        if(H.huge != 0.0) {
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = fin();
-            H.slow = 0.0;
-        }
-#endif
+        const int r = run_step(H, okc, fin);
         okc &= r;
         csum += cf.c;
         if(store) {

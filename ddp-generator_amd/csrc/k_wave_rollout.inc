@@ -201,6 +201,7 @@ __global__ __launch_bounds__(WAVE *RW) void k_rollout_parts(DevPtrs P, ilqg_dev_
             for(int q = 0; q < PPW; q++)
                 if(part + q * RW < RP) ilqg_step_part(part + q * RW, &s_x[lane][0], &s_t[lane][0], &bad_step, x, u, k, C.o.p, N);
         };
+        // (not run_step: no return value and no `nonfinite` to put back — the parts report through bad_step, which the retry clears)
 #if ILQG_UNIFORM_GUARDS
         parts();
 #else
@@ -264,20 +265,7 @@ __global__ __launch_bounds__(WAVE *RW) void k_rollout_parts(DevPtrs P, ilqg_dev_
             r &= ddpF(&cf, &C.o);
             return r;
         };
-        int r = 1;
-#if ILQG_UNIFORM_GUARDS
-        if(okc) r = run_guarded(fin);
-#else
-        const double nf0 = H.nonfinite;
-        H.huge = 0.0;
-        r = fin();
-        if(H.huge != 0.0) {
-            H.nonfinite = nf0;
-            H.slow = 1.0;
-            r = fin();
-            H.slow = 0.0;
-        }
-#endif
+        const int r = run_step(H, okc, fin);
         okc &= r;
         csum += cf.c;
         if(store) {
