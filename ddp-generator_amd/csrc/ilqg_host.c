@@ -73,6 +73,9 @@ struct ilqg_batch {
     double **p;                      /* owned copies of the problem parameters */
     char *p_given;                   /* which of them the caller has set */
     int params_pushed;
+    /* per-trajectory problem parameters (ilqg_batch_set_params_batch): the indices of the named parameters in the order of
+     * the caller's names, and W, the width of a row; pb_n = 0: none, the batch is shared-only */
+    int pb_n, pb_W, pb_named[64];
     /* full solves: finished trajectories are retired (ilqg_batch_solve) */
     int compact;                     /* 0: never; else the smallest number of live trajectories still worth a smaller context */
     int trace_n;                     /* the last solve, poll by poll: iterations done, trajectories active, slots iterated */
@@ -445,6 +448,16 @@ int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value,
             snprintf(c->err, sizeof(c->err), "Parameter name '%s' must be a vector length %d.", name, param_len(c, i));
             return 1;
         }
+        {
+            int j;
+            for(j = 0; j < c->pb_n; j++)
+                if(c->pb_named[j] == i) {
+                    snprintf(c->err, sizeof(c->err), "ilqg_batch_set_param: name: parameter '%s' currently has a value per trajectory "
+                             "(ilqg_batch_set_params_batch); a shared value would be read by no trajectory.  Clear the per-trajectory set "
+                             "first: ilqg_batch_set_params_batch(c, 0, NULL, NULL)", name);
+                    return 1;
+                }
+        }
         memcpy(c->p[i], value, sizeof(double) * n);
         c->p_given[i] = 1;
         c->params_pushed = 0;
@@ -714,6 +727,97 @@ int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const
                                             double *x, double *u, void *stream) {
     return policy_rollout(c, "ilqg_batch_policy_rollout_params_device", 1, 1, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok,
                           x_end, x, u, stream);
+}
+
+/* Per-trajectory problem parameters: trajectory b plans — and is rolled out, and its plant advances — under the batch's
+ * fixed-size parameters with the named ones replaced by row b of the caller's table.  Names are resolved by the code
+ * ilqg_batch_policy_rollout_params uses (policy_names); every refusal happens before a group is touched.  The groups each
+ * hold their slice of the rows (ilqg_dev_set_params_batch). */
+static int set_params_batch(ilqg_batch_t *c, const char *who, int on_device, int n_names, const char *const *names, const double *values,
+                            void *stream) {
+    int g, dims[8], named[POLICY_MAX_NAMES], W = 0;
+    ilqg_dev_dims(dims);
+    if(dims[7]) {
+        snprintf(c->err, sizeof(c->err), "%s: this library maps one wavefront to a trajectory (the wave mapping: the *_wave libraries and the "
+                 "problems with N_X = 10 or 16); its kernels do not carry parameters per lane.  Per-trajectory parameters need a lane-mapped "
+                 "library", who);
+        return 1;
+    }
+    if(n_names < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0 clears the per-trajectory set)", who, n_names);
+        return 1;
+    }
+    if(n_names > 0 && !names) {
+        snprintf(c->err, sizeof(c->err), "%s: names is NULL (n_names parameter names)", who);
+        return 1;
+    }
+    if(n_names > 0 && !values) {
+        snprintf(c->err, sizeof(c->err), "%s: values is NULL (the parameter rows, [B][W])", who);
+        return 1;
+    }
+    if(n_names > 0 && policy_names(c, who, n_names, names, values, named, &W)) return 1;
+    if(n_names > 0 && on_device && ilqg_dev_check_device_ptr(c->dev[0], values, "values")) return fail(c, who);
+    if(n_names > 0 && on_device) EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "set_params_batch: stream");
+    EACH_GROUP(g) {
+        if(ilqg_dev_set_params_batch(c->dev[g], n_names, named, n_names > 0 ? values + (size_t)c->first[g] * (size_t)W : NULL, on_device))
+            return fail(c, who);
+        if(n_names > 0 && on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "set_params_batch: stream");
+    }
+    c->pb_n = n_names;
+    c->pb_W = W;
+    memcpy(c->pb_named, named, sizeof(int) * (size_t)n_names);
+    return 0;
+}
+
+int ilqg_batch_set_params_batch(ilqg_batch_t *c, int n_names, const char *const *names, const double *values) {
+    return set_params_batch(c, "ilqg_batch_set_params_batch", 0, n_names, names, values, NULL);
+}
+
+int ilqg_batch_set_params_batch_device(ilqg_batch_t *c, int n_names, const char *const *names, const double *values, void *stream) {
+    return set_params_batch(c, "ilqg_batch_set_params_batch_device", 1, n_names, names, values, stream);
+}
+
+/* what trajectory b sees of fixed-size parameter `name`: its row where the parameter is per-trajectory (read back from the
+ * groups' tables), else the batch's shared value, repeated */
+int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out) {
+    static const char who[] = "ilqg_batch_get_params_batch";
+    int i, j, g, b, col = 0, size;
+    double *rows;
+    if(!name || !out) {
+        snprintf(c->err, sizeof(c->err), "%s: %s is NULL", who, !name ? "name" : "out");
+        return 1;
+    }
+    for(i = 0; i < n_params; i++)
+        if(strcmp(paramdesc[i]->name, name) == 0) break;
+    if(i == n_params) {
+        snprintf(c->err, sizeof(c->err), "%s: name: Parameter name '%s' is not member of parameters struct.", who, name);
+        return 1;
+    }
+    size = paramdesc[i]->size;
+    if(size == -1) {
+        snprintf(c->err, sizeof(c->err), "%s: name: parameter '%s' has one value per time step (size -1); per-time-step parameters stay "
+                 "shared by all trajectories", who, name);
+        return 1;
+    }
+    for(j = 0; j < c->pb_n && c->pb_named[j] != i; j++) col += paramdesc[c->pb_named[j]]->size;
+    if(j == c->pb_n) {  /* shared */
+        if(!c->p_given[i]) {
+            snprintf(c->err, sizeof(c->err), "Parameter name '%s' was not set.", name);
+            return 1;
+        }
+        for(b = 0; b < c->B; b++) memcpy(out + (size_t)b * size, c->p[i], sizeof(double) * (size_t)size);
+        return 0;
+    }
+    rows = (double *)malloc(sizeof(double) * (size_t)c->B * (size_t)c->pb_W);
+    if(!rows) return fail_msg(c, "ilqg_batch_get_params_batch: out of memory");
+    EACH_GROUP(g)
+        if(ilqg_dev_get_params_batch(c->dev[g], rows + (size_t)c->first[g] * (size_t)c->pb_W)) {
+            free(rows);
+            return fail(c, who);
+        }
+    for(b = 0; b < c->B; b++) memcpy(out + (size_t)b * size, rows + (size_t)b * c->pb_W + col, sizeof(double) * (size_t)size);
+    free(rows);
+    return 0;
 }
 
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
@@ -1021,6 +1125,10 @@ int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const 
     ilqg_batch_t *stage = NULL;
     const int S = B < ILQG_STREAM_STAGE ? B : ILQG_STREAM_STAGE;
     if(total < 1) return fail_msg(c, "ilqg_batch_solve_stream: no starts");
+    if(c->pb_n > 0)
+        return fail_msg(c, "ilqg_batch_solve_stream: the batch has per-trajectory parameters (ilqg_batch_set_params_batch), which belong to "
+                           "its slots, while the starts of a stream pass through them: a table per start is not supported.  Clear the set "
+                           "first: ilqg_batch_set_params_batch(c, 0, NULL, NULL)");
     if(push_config(c)) return 1;
     ilqg_dev_dims(dims);
     NXd = dims[0];
@@ -1759,6 +1867,18 @@ int ilqg_multi_set_option(ilqg_multi_t *m, const char *name, const double *value
 int ilqg_multi_set_param(ilqg_multi_t *m, const char *name, const double *value, int n) {
     int g;
     EACH_SHARD(g) if(ilqg_batch_set_param(m->shard[g], name, value, n)) return multi_fail(m, g);
+    return 0;
+}
+/* every shard's rows: those from its first trajectory on */
+int ilqg_multi_set_params_batch(ilqg_multi_t *m, int n_names, const char *const *names, const double *values) {
+    int g, i, k;
+    size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
+    if(names && values)
+        for(i = 0; i < n_names; i++)
+            for(k = 0; names[i] && k < n_params; k++)
+                if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    EACH_SHARD(g)
+        if(ilqg_batch_set_params_batch(m->shard[g], n_names, names, values ? values + (size_t)m->first[g] * W : NULL)) return multi_fail(m, g);
     return 0;
 }
 int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0) {

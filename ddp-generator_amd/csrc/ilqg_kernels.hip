@@ -1047,6 +1047,13 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
     host[i] = (fcol < wd) ? dev[(size_t)k * wd * Bp + (size_t)(b >> 6) * (wd * WAVE) + (size_t)fcol * WAVE + (b & 63)] : 0.0;
 }
 
+// per-trajectory problem parameters: row b of the context's table over the lane's private parameters (k_policy.inc, where
+// the order rule is stated); the kernels below call it with their pack `rows`
+struct PolicyParamMap;
+template <class... Behind>
+__device__ __forceinline__ void trajectory_params(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *__restrict__ values,
+                                                  const PolicyParamMap &map, const Behind &...);
+
 #if !ILQG_WAVE_MAP
 #include "k_lane_backward.inc"  // k_derivs, k_backward, k_backward_split, k_pack_records
 #else

@@ -139,6 +139,18 @@ void ilqg_dev_dims(int *out);
 void ilqg_dev_multiplier_dims(int *out);
 
 int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const double *const *values);
+/* Per-trajectory problem parameters (lane mapping only; the wave mapping refuses, naming itself).  From the next launch on
+ * every generated callback evaluated for trajectory b sees the context's fixed-size parameters with the n_named parameters
+ * named[] (indices into paramdesc[], as for ilqg_dev_policy_rollout with R = 1 and shared = 0: fixed size, none twice)
+ * replaced by row b of values [batch][W].  The context keeps its own copy of the table, in a buffer that only grows.
+ * on_device = 0: values is host memory, waits once; on_device != 0: device memory of the context's device, copied in the
+ * order of the context's stream, no wait and (at an unchanged size) no allocation.  n_named = 0 clears the set: the kernels
+ * are then those of a context that never had one; named and values are not read.  A call replaces the whole set.  Order with
+ * the tables of ilqg_dev_policy_rollout and ilqg_dev_plant_begin: the trajectory's row first, then the roll-out's or plant's.
+ * ilqg_dev_move carries the rows of the trajectories it moves; the destination takes the source's map.  Touches no
+ * trajectory and launches no kernel.  get: the table as it is on the device, rows [batch][W] (host); waits. */
+int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, const double *values, int on_device);
+int ilqg_dev_get_params_batch(ilqg_dev_t *d, double *rows);
 int ilqg_dev_set_opts(ilqg_dev_t *d, const ilqg_dev_opts_t *o);
 
 /* host <-> device, host side trajectory-major [batch][steps][width] */

@@ -88,6 +88,13 @@ struct ilqg_dev {
     int *plant_failed;
     bool plant_named;
     PolicyParamMap plant_map;
+    // per-trajectory problem parameters (ilqg_dev_set_params_batch): the rows [B][W] with their map; the buffer only grows
+    // and outlives a cleared set.  pb_on: the lane-mapped kernels that take ParamValues run as the instantiation whose pack is this table and
+    // its map (LAUNCH_PV)
+    double *pb_values;
+    size_t pb_bytes;
+    bool pb_on;
+    PolicyParamMap pb_map;
     hipEvent_t ext_in, ext_out;  // ordering with a stream of the caller (ilqg_dev_stream_in / _out), made with the context
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
@@ -414,6 +421,9 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
     memset(&d->P, 0, sizeof(d->P));
     memset(&d->O, 0, sizeof(d->O));
     memset(&d->pv, 0, sizeof(d->pv));
+    d->pb_values = nullptr;
+    d->pb_bytes = 0;
+    d->pb_on = false;
     d->P.B = d->B;
     d->P.Bp = d->Bp;
     d->P.N = d->N;
@@ -628,6 +638,7 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
     if(d->log_u) hipFree(d->log_u);
     if(d->log_c) hipFree(d->log_c);
     plant_release(d);
+    if(d->pb_values) hipFree(d->pb_values);
     for(double *p : d->param_bufs) hipFree(p);
     if(d->P.p) hipFree(d->P.p);
     if(d->staging) hipFree(d->staging);
@@ -681,6 +692,54 @@ int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const dou
     HIP_TRY(hipMalloc((void **)&d->P.p, ptrs.size() * sizeof(double *)));
     HIP_TRY(hipMemcpy(d->P.p, ptrs.data(), ptrs.size() * sizeof(double *), hipMemcpyHostToDevice));
     d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
+    return 0;
+}
+
+// Per-trajectory problem parameters.  Nothing here touches a trajectory: like ilqg_dev_set_params it only changes what the
+// NEXT launch reads.  The copy is enqueued on the context's stream, behind every launch that still reads the old rows.
+static const PolicyParamMap *policy_param_map(int n_named, const int *named, const double *values, PolicyParamMap &map);
+int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, const double *values, int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(WAVE_MAP) {
+        g_err = "set_params_batch: this library maps one wavefront to a trajectory (wave mapping); its kernels do not carry "
+                "parameters per lane, per-trajectory parameters need a lane-mapped library";
+        return 1;
+    }
+    if(n_named < 0) {
+        g_err = "set_params_batch: n_names must not be negative";
+        return 1;
+    }
+    if(n_named == 0) {
+        d->pb_on = false;  // (the buffer stays: a set that comes back allocates nothing)
+        return 0;
+    }
+    PolicyParamMap map;
+    if(!policy_param_map(n_named, named, values, map)) return 1;
+    const size_t bytes = (size_t)d->B * (size_t)map.W * sizeof(double);
+    if(bytes > d->pb_bytes) {
+        HIP_TRY(hipStreamSynchronize(d->stream));  // (launches in flight read the old buffer)
+        if(d->pb_values) HIP_TRY(hipFree(d->pb_values));
+        d->pb_values = nullptr;
+        d->pb_bytes = 0;
+        d->pb_on = false;
+        HIP_TRY(hipMalloc((void **)&d->pb_values, bytes));
+        d->pb_bytes = bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(d->pb_values, values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+    if(!on_device) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's array is its own again
+    d->pb_map = map;
+    d->pb_on = true;
+    return 0;
+}
+
+int ilqg_dev_get_params_batch(ilqg_dev_t *d, double *rows) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!d->pb_on) {
+        g_err = "get_params_batch: the context has no per-trajectory parameters";
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(rows, d->pb_values, (size_t)d->B * (size_t)d->pb_map.W * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
 
@@ -929,6 +988,27 @@ int ilqg_dev_io_end(ilqg_dev_t *d) {
         return 1;                                                        \
     }
 
+// The ONE place that picks the instantiation of a lane-mapped kernel that takes ParamValues: the kernel as it was before
+// there were per-trajectory parameters — its old name, an empty pack, not one argument more — unless the context holds a
+// table (ilqg_dev_set_params_batch); then the instantiation whose pack is the table and its map, behind the kernel's own
+// arguments.  K: the kernel's name with its own template arguments, left open, in parentheses: (k_rollout<RK_INIT).  The two
+// kernels that are no templates have a twin of another name: LAUNCH_PV_AS(d, (k_derivs), (k_derivs_rows<ILQG_PV_ROWS>), ...).
+// Both forms share the kernel's timing slot.  The wave mapping has no second form (ilqg_dev_set_params_batch refuses).
+#define ILQG_OPEN_NAME(...) __VA_ARGS__
+#define ILQG_PV_ROWS const double *, PolicyParamMap
+#if !ILQG_WAVE_MAP
+#define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...)                                                                    \
+    do {                                                                                                                                \
+        if((d)->pb_on)                                                                                                                  \
+            hipLaunchKernelGGL((ILQG_OPEN_NAME ROWS), grid, block, lds, stream, __VA_ARGS__, (const double *)(d)->pb_values, (d)->pb_map); \
+        else                                                                                                                            \
+            hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__);                                         \
+    } while(0)
+#else
+#define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...) hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__)
+#endif
+#define LAUNCH_PV(d, K, ...) LAUNCH_PV_AS(d, (ILQG_OPEN_NAME K>), (ILQG_OPEN_NAME K, ILQG_PV_ROWS>), __VA_ARGS__)
+
 // (re)allocates a device buffer that must hold `need` bytes; what is queued on `rs` may still use the old one
 static int ensure_buffer(ilqg_dev_t *d, double **buf, size_t *have, size_t need, hipStream_t rs) {
     if(*have >= need) return 0;
@@ -977,7 +1057,7 @@ int ilqg_dev_reset(ilqg_dev_t *d) {
     if(HAS_MUL) {  // update_multipliers(o, 1) of the solver entry (iLQG.c:236)
         NEED_PARAMS(d);
         Timed t(d, ILQG_K_MULTIPLIERS);
-        hipLaunchKernelGGL(k_multipliers, dim3(d->Bp / WAVE), dim3(WAVE), 0, d->stream, d->P, d->O, d->pv, 1);
+        LAUNCH_PV_AS(d, (k_multipliers), (k_multipliers_rows<ILQG_PV_ROWS>), dim3(d->Bp / WAVE), dim3(WAVE), 0, d->stream, d->P, d->O, d->pv, 1);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1004,9 +1084,9 @@ static void launch_rollout(ilqg_dev_t *d, int mode, int kernel_id, int a0, int n
     Timed t(d, kernel_id, stream);
     const dim3 grid((d->Bp + ROLL_BLOCK - 1) / ROLL_BLOCK, n_alpha), block(ROLL_BLOCK);
     if(mode == ROLL_INIT)
-        hipLaunchKernelGGL(k_rollout<RK_INIT>, grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
+        LAUNCH_PV(d, (k_rollout<RK_INIT), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
     else if(mode == ROLL_COST)
-        hipLaunchKernelGGL(k_rollout<RK_COST>, grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
+        LAUNCH_PV(d, (k_rollout<RK_COST), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
 #if ILQG_WAVE_MAP && defined(ILQG_ROLLOUT_PARTS)
     else if(!HAS_MUL && !d->env.no_rollout_parts) {  // the generated file offers the step in parts: several wavefronts per 64 trajectories
         DevPtrs Q = d->P;
@@ -1024,7 +1104,7 @@ static void launch_rollout(ilqg_dev_t *d, int mode, int kernel_id, int a0, int n
     }
 #endif
     else
-        hipLaunchKernelGGL(k_rollout<RK_GENERAL>, grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
+        LAUNCH_PV(d, (k_rollout<RK_GENERAL), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
 }
 
 int ilqg_dev_rollout_init(ilqg_dev_t *d) {
@@ -1239,14 +1319,27 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
                          int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     if(roll_enter(d)) return 1;
     const dim3 grid = grid1((size_t)d->B * (size_t)R, ROLL_BLOCK);
+    // (with a per-trajectory table — lane mapping only — the trajectory's row goes first, the roll-out's behind it)
+#if !ILQG_WAVE_MAP
+    if(d->pb_on && !map) {
+        Timed t(d, ILQG_K_POLICY, roll_stream(d));
+        hipLaunchKernelGGL((k_policy<false, const double *, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0,
+                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values, d->pb_map);
+    } else if(d->pb_on) {
+        Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
+        hipLaunchKernelGGL((k_policy<true, const double *, PolicyParamMap, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0,
+                           roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values,
+                           d->pb_map, values, shared ? 1 : 0, *map);
+    } else
+#endif
     if(!map) {
         Timed t(d, ILQG_K_POLICY, roll_stream(d));
-        hipLaunchKernelGGL(k_policy<false>, grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok,
-                           x_end, x, u);
+        hipLaunchKernelGGL(k_policy<false>, grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost,
+                           ok, x_end, x, u);
     } else {
         Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
-        hipLaunchKernelGGL((k_policy<true, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0,
-                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, values, shared ? 1 : 0, *map);
+        hipLaunchKernelGGL((k_policy<true, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R,
+                           x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, values, shared ? 1 : 0, *map);
     }
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
@@ -1379,6 +1472,18 @@ int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
     if(roll_enter(d)) return 1;
     {
         Timed t(d, ILQG_K_PLANT, roll_stream(d));
+#if !ILQG_WAVE_MAP  // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
+        if(d->pb_on && d->plant_named)
+            hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK),
+                               dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed,
+                               (const double *)d->plant_dist, round * steps, rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c,
+                               (const double *)d->pb_values, d->pb_map, (const double *)d->plant_values, d->plant_map);
+        else if(d->pb_on)
+            hipLaunchKernelGGL((k_plant<false, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d),
+                               d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps,
+                               rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c, (const double *)d->pb_values, d->pb_map);
+        else
+#endif
         if(d->plant_named)
             hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
                                d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps, rounds * steps,
@@ -1704,7 +1809,7 @@ int ilqg_dev_derivs(ilqg_dev_t *d) {
     {
         Timed t(d, ILQG_K_DERIVS);
         const size_t total = (size_t)d->Bp * (d->N + 1);
-        hipLaunchKernelGGL(k_derivs, grid1(total, 256), dim3(256), 0, d->stream, d->P, d->O, d->pv);
+        LAUNCH_PV_AS(d, (k_derivs), (k_derivs_rows<ILQG_PV_ROWS>), grid1(total, 256), dim3(256), 0, d->stream, d->P, d->O, d->pv);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1726,15 +1831,15 @@ int ilqg_dev_backward(ilqg_dev_t *d, int mode) {
         Timed t(d, mode == 2 ? ILQG_K_BACKWARD_FUSED : ILQG_K_BACKWARD);
         const dim3 grid(d->Bp / WAVE), block(WAVE);
         if(mode == 0)
-            hipLaunchKernelGGL(k_backward<0>, grid, block, 0, d->stream, d->P, d->O, d->pv);
+            LAUNCH_PV(d, (k_backward<0), grid, block, 0, d->stream, d->P, d->O, d->pv);
         else if(mode == 1)
-            hipLaunchKernelGGL(k_backward<1>, grid, block, 0, d->stream, d->P, d->O, d->pv);
+            LAUNCH_PV(d, (k_backward<1), grid, block, 0, d->stream, d->P, d->O, d->pv);
 #if ILQG_HAVE_SPLIT
-        else if(d->O.bw_split && !HAS_MUL)
+        else if(d->O.bw_split && !HAS_MUL && !d->pb_on)  // (k_backward_split knows the shared parameters only)
             hipLaunchKernelGGL(k_backward_split, grid, dim3(2 * WAVE), 0, d->stream, d->P, d->O, d->pv);
 #endif
         else
-            hipLaunchKernelGGL(k_backward<2>, grid, block, 0, d->stream, d->P, d->O, d->pv);
+            LAUNCH_PV(d, (k_backward<2), grid, block, 0, d->stream, d->P, d->O, d->pv);
     }
     if(mode != 2) {
         Timed t(d, ILQG_K_TRANSPOSE);
@@ -1794,9 +1899,9 @@ int ilqg_dev_search(ilqg_dev_t *d) {
             const int T = WAVE / s1;
             const bool dma = T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma;
             if(dma)
-                hipLaunchKernelGGL((k_search<0, true>), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, 0, s1, set);
+                LAUNCH_PV(d, (k_search<0, true), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, 0, s1, set);
             else
-                hipLaunchKernelGGL((k_search<0, false>), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0, s1, set);
+                LAUNCH_PV(d, (k_search<0, false), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0, s1, set);
         }
         if(n2 > 0) {  // the grid covers the worst case; wavefronts beyond the pending count return at once
             {
@@ -1804,9 +1909,9 @@ int ilqg_dev_search(ilqg_dev_t *d) {
                 const int T = WAVE / n2;
                 const bool dma = T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma;
                 if(dma)
-                    hipLaunchKernelGGL((k_search<1, true>), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, s1, n2, set);
+                    LAUNCH_PV(d, (k_search<1, true), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, s1, n2, set);
                 else
-                    hipLaunchKernelGGL((k_search<1, false>), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, s1, n2, set);
+                    LAUNCH_PV(d, (k_search<1, false), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, s1, n2, set);
             }
             Timed t(d, ILQG_K_ADOPT, rs);
             hipLaunchKernelGGL(k_adopt_home, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1);
@@ -1932,7 +2037,7 @@ int ilqg_dev_update(ilqg_dev_t *d) {
     }
     if(HAS_MUL) {
         Timed t(d, ILQG_K_MULTIPLIERS, rs);
-        hipLaunchKernelGGL(k_multipliers, dim3(d->Bp / WAVE), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0);
+        LAUNCH_PV_AS(d, (k_multipliers), (k_multipliers_rows<ILQG_PV_ROWS>), dim3(d->Bp / WAVE), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0);
     }
     if(d->O.resweep || HAS_MUL) launch_rollout(d, ROLL_COST, ILQG_K_ROLLOUT_COST, 0, 1, rs);
     HIP_TRY(hipGetLastError());
@@ -1983,6 +2088,28 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
     hipLaunchKernelGGL(k_move_traj, grid1((size_t)count * (src->N + 1), 256), dim3(256), 0, dst->stream, dst->P, src->P, idx, idx + count, count,
                        (with_records && !WAVE_MAP) ? 1 : 0);
     HIP_TRY(hipGetLastError());
+    if(src->pb_on) {  // the trajectories' parameter rows travel with them; a destination without a table gets the source's map
+        const size_t W = (size_t)src->pb_map.W, bytes = (size_t)dst->B * W * sizeof(double);
+        bool same = dst->pb_on && dst->pb_map.W == src->pb_map.W;
+        for(int j = 0; same && j < ILQG_PTOTAL; j++) same = dst->pb_map.src[j] == src->pb_map.src[j];
+        if(!same) {
+            if(bytes > dst->pb_bytes) {
+                HIP_TRY(hipStreamSynchronize(dst->stream));
+                if(dst->pb_values) HIP_TRY(hipFree(dst->pb_values));
+                dst->pb_values = nullptr;
+                dst->pb_bytes = 0;
+                dst->pb_on = false;
+                HIP_TRY(hipMalloc((void **)&dst->pb_values, bytes));
+                dst->pb_bytes = bytes;
+            }
+            HIP_TRY(hipMemsetAsync(dst->pb_values, 0, bytes, dst->stream));  // (rows nothing has moved into yet)
+            dst->pb_map = src->pb_map;
+            dst->pb_on = true;
+        }
+        hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->pb_values, (const double *)src->pb_values, idx,
+                           idx + count, count, (int)W);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(dst->stream));
     return 0;
 }

@@ -165,7 +165,16 @@ __global__ void k_update(DevPtrs P, ilqg_dev_opts_t O, int commit_s1, int commit
 // that stored them).  What they do across steps is restated around the calls: one raise of w_pen_l after the
 // walk if any step asked for it; with init != 0 the running part returns inside its loop after the first element
 // (iLQG_func.tem:447), so only step 0 is visited.
+#if ILQG_WAVE_MAP  // (this mapping has no per-trajectory parameters: the kernel itself)
 __global__ __launch_bounds__(WAVE) void k_multipliers(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int init) {
+#else
+// (lane mapping: the lane's work, for k_multipliers and for k_multipliers_rows below — Rows is empty or the context's
+// per-trajectory table and its map)
+template <class... Rows>
+__device__ __forceinline__ void multipliers_lane(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int init, Rows... rows) {
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
+    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "multipliers_lane(P, O, A, init) or multipliers_lane(P, O, A, init, table, map)");
+#endif
     const int b = blockIdx.x * WAVE + threadIdx.x;
     if(b >= P.B) return;
     if(init) {
@@ -175,6 +184,9 @@ __global__ __launch_bounds__(WAVE) void k_multipliers(DevPtrs P, ilqg_dev_opts_t
     }
     const int N = P.N;
     ILQG_CALLBACKS(C, H);
+#if !ILQG_WAVE_MAP
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+#endif
     load_penalty_weights(C, P, b);
     const double wl = C.o.w_pen_l;
     eltraj_t view;
@@ -245,6 +257,14 @@ __global__ __launch_bounds__(WAVE) void k_multipliers(DevPtrs P, ilqg_dev_opts_t
     P.f[ILQG_F_WPEN_L_DER][b] = wl_new;
     P.f[ILQG_F_WPEN_F_DER][b] = (MF > 0) ? C.o.w_pen_f : P.f[ILQG_F_WPEN_F][b];
 }
+#if !ILQG_WAVE_MAP
+__global__ __launch_bounds__(WAVE) void k_multipliers(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int init) { multipliers_lane(P, O, A, init); }
+// ... under per-trajectory parameters (k_multipliers keeps its name: it is no template)
+template <class... Rows>
+__global__ __launch_bounds__(WAVE) void k_multipliers_rows(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int init, Rows... rows) {
+    multipliers_lane(P, O, A, init, rows...);
+}
+#endif
 
 // solver entry state (iLQG.c:226-237)
 __global__ void k_reset(DevPtrs P, ilqg_dev_opts_t O) {
@@ -325,6 +345,14 @@ __global__ void k_move_traj(DevPtrs D, DevPtrs S, const int *to, const int *from
         for(int i = 0; i < wd; i++) D.i[f][(size_t)i * D.Bp + bd] = (f == ILQG_I_LOC) ? 0 : S.i[f][(size_t)i * S.Bp + bs];
     }
     D.derivs_failed[bd] = S.derivs_failed[bs];
+}
+
+// ... and with them their rows of the per-trajectory parameter table [B][W] (ilqg_dev_set_params_batch)
+__global__ void k_move_rows(double *__restrict__ dst, const double *__restrict__ src, const int *to, const int *from, int count, int W) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(w >= (size_t)count * W) return;
+    const int j = (int)(w / W), i = (int)(w % W);
+    dst[(size_t)to[j] * W + i] = src[(size_t)from[j] * W + i];
 }
 
 __global__ void k_count_active(const int *status, int B, int *out) {

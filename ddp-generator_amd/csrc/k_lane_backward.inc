@@ -103,7 +103,11 @@ using RecZeros = NoZeros;
 // ---------------------------------------------------------------------------
 // calc_derivs: one lane per (trajectory, time step); step N is the final record
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_derivs(DevPtrs P, ilqg_dev_opts_t O, ParamValues A) {
+// (the lane's work, for k_derivs and for k_derivs_rows below: Rows is empty or the context's per-trajectory table and its map)
+template <class... Rows>
+__device__ __forceinline__ void derivs_lane(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
+    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "derivs_lane(P, O, A) or derivs_lane(P, O, A, table, map)");
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int b = (int)(tid % P.Bp);
     const int k = (int)(tid / P.Bp);
@@ -111,6 +115,7 @@ __global__ __launch_bounds__(256) void k_derivs(DevPtrs P, ilqg_dev_opts_t O, Pa
     if(P.i[ILQG_I_STATUS][b] != ILQG_ST_ACTIVE || !P.i[ILQG_I_NEED_DERIVS][b]) return;
 
     ILQG_CALLBACKS(C, H);
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
     load_penalty_weights_der(C, P, b);
     int ok = 1;
     if(k < P.N) {
@@ -144,6 +149,12 @@ __global__ __launch_bounds__(256) void k_derivs(DevPtrs P, ilqg_dev_opts_t O, Pa
 #undef PUT
     }
     if(!ok || H.nonfinite != 0.0) P.derivs_failed[b] = 1;
+}
+__global__ __launch_bounds__(256) void k_derivs(DevPtrs P, ilqg_dev_opts_t O, ParamValues A) { derivs_lane(P, O, A); }
+// ... under per-trajectory parameters (k_derivs keeps its name: it is no template)
+template <class... Rows>
+__global__ __launch_bounds__(256) void k_derivs_rows(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
+    derivs_lane(P, O, A, rows...);
 }
 
 // ---------------------------------------------------------------------------
@@ -378,8 +389,11 @@ __device__ __forceinline__ int backward_sweep_fused(const DevPtrs &P, Callbacks 
 #ifndef ILQG_BACKWARD_OCC  // wavefronts of k_backward per SIMD the register allocation must allow
 #define ILQG_BACKWARD_OCC 1
 #endif
-template <int mode>
-__global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P, ilqg_dev_opts_t O, ParamValues A) {
+template <int mode, class... Rows>
+__global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
+    // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
+    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "k_backward<...>(...) or k_backward<..., const double *, PolicyParamMap>(..., table, map)");
     const Place place(1);
 #ifdef ILQG_BACKWARD_PRIO  // measurement builds: issue priority of the sweep's wavefront over search wavefronts on its SIMD
     __builtin_amdgcn_s_setprio(ILQG_BACKWARD_PRIO);
@@ -394,6 +408,7 @@ __global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P,
         return;
     }
     ILQG_CALLBACKS(C, H);
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
     load_penalty_weights_der(C, P, b);
     double lambda = P.f[ILQG_F_LAMBDA][b], dlambda = P.f[ILQG_F_DLAMBDA][b];
     double dV0 = 0.0, dV1 = 0.0, g_norm = P.f[ILQG_F_GNORM][b];

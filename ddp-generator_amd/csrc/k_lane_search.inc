@@ -33,8 +33,12 @@
 // read T consecutive 16-byte pieces (no bank conflicts).  Two buffers: the records of step k+2 are on their way while
 // step k+1's are read.  Used when a step's pieces fit DMA_LOADS loads (T * RN / 2 <= 64 DMA_LOADS).
 constexpr int DMA_LOADS = 3;
-template <int stage, bool DMA>
-__global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int a0, int n, int set) {
+template <int stage, bool DMA, class... Rows>
+__global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int a0, int n, int set,
+                                                                  Rows... rows) {
+    // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
+    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "k_search<...>(...) or k_search<..., const double *, PolicyParamMap>(..., table, map)");
     extern __shared__ __attribute__((aligned(16))) double s_rec[];  // DMA: [2][T * RN] doubles
     const Place place(2 + stage);
     const int lane = threadIdx.x;
@@ -56,6 +60,8 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
     const bool feedback = (alpha != 0.0);  // alpha == 0.0: u = u_nom without feedback (iLQG_func.tem:156-158)
 
     ILQG_CALLBACKS(C, H);
+    // (b = pending[ee] or ee: lanes beyond the end repeat the last entry, and read its row)
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
     load_penalty_weights(C, P, b);
     trajEl_t ct;
     multipliersEl_t mk;

@@ -31,6 +31,11 @@ __device__ __forceinline__ void plant_params(ParamValues &V, ParamTable &T, cons
                                              const PolicyParamMap &map) {
     override_params(V, T, P, (size_t)b, 0, values, 0, map);
 }
+// the plant's row behind the trajectory's (the model's): trajectory_params' order
+__device__ __forceinline__ void plant_params_behind(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *, const PolicyParamMap &,
+                                                    const double *__restrict__ values, const PolicyParamMap &map) {
+    override_params(V, T, P, (size_t)b, 0, values, 0, map, true);
+}
 
 template <bool PLANT_PARAMS, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int steps, int feedback,
@@ -38,7 +43,9 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
                                                                         const double *__restrict__ dist, int at0, int total, int round, int rounds,
                                                                         double *__restrict__ lx, double *__restrict__ lu, double *__restrict__ lc,
                                                                         double *__restrict__ lp, Rows... rows) {
-    static_assert(sizeof...(Rows) == (PLANT_PARAMS ? 2 : 0), "k_plant<true>(..., values, map); k_plant<false>(...)");
+    // the pack: [the context's per-trajectory table, its map,] [the plants' table, its map]
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) == (PLANT_PARAMS ? 4 : 2);
+    static_assert(sizeof...(Rows) == (PER_TRAJECTORY ? 2 : 0) + (PLANT_PARAMS ? 2 : 0), "k_plant<true>(..., [table, map,] values, map); k_plant<false>(..., [table, map])");
     const int b = (int)(blockIdx.x * ROLL_BLOCK + threadIdx.x);
     if(b >= P.B) return;
     const int N = P.N;
@@ -59,7 +66,9 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
     }
 
     ILQG_CALLBACKS(C, H);
-    if constexpr(PLANT_PARAMS) plant_params(C_values, C_table, P, b, rows...);
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    if constexpr(PLANT_PARAMS && PER_TRAJECTORY) plant_params_behind(C_values, C_table, P, b, rows...);
+    if constexpr(PLANT_PARAMS && !PER_TRAJECTORY) plant_params(C_values, C_table, P, b, rows...);
     load_penalty_weights(C, P, b);
     el_t ct;
     multipliersEl_t mk;

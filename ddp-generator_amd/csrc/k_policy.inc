@@ -94,15 +94,16 @@ struct PolicyParamMap {
 #define ILQG_POLICY_PARAMS_IN_MEMORY 0
 #endif
 #endif
+// behind: a second override of the same lane (below); in the pointer form a slot it does not name keeps what the first one left
 __device__ __forceinline__ void override_params(ParamValues &V, ParamTable &T, const DevPtrs &P, size_t g, int r, const double *__restrict__ values,
-                                                int shared, const PolicyParamMap &map) {
+                                                int shared, const PolicyParamMap &map, bool behind = false) {
     const double *row = values + (shared ? (size_t)r : g) * (size_t)map.W;
     if(ILQG_POLICY_PARAMS_IN_MEMORY) {
         constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
         constexpr int offs[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_POFFSETS;
 #pragma unroll
         for(int i = 0; i < ILQG_NP; i++)
-            if(sizes[i] > 0) T.ptr[i] = map.src[offs[i]] >= 0 ? const_cast<double *>(row + map.src[offs[i]]) : P.p[i];
+            if(sizes[i] > 0) T.ptr[i] = map.src[offs[i]] >= 0 ? const_cast<double *>(row + map.src[offs[i]]) : (behind ? T.ptr[i] : P.p[i]);
     } else {
 #pragma unroll
         for(int j = 0; j < ILQG_PTOTAL; j++)
@@ -110,12 +111,34 @@ __device__ __forceinline__ void override_params(ParamValues &V, ParamTable &T, c
     }
 }
 
+// Per-trajectory problem parameters (ilqg_batch_set_params_batch): the context's table [B][W] with its map, the first two of
+// a kernel's pack `rows` (a kernel with an EMPTY pack is the kernel of before, under its old name; the two kernels that were no
+// templates, k_derivs and k_multipliers, stay so and have the twins k_derivs_rows / k_multipliers_rows).  Right behind ILQG_CALLBACKS a lane overrides the mapped slots of its private ParamValues with row b
+// of the table — b = the trajectory the lane works for, whatever its lane index means — ONCE per launch, never inside a step
+// loop: from there on the values are the lane's registers, where the shared ones are the wavefront's.  This is the one place
+// that states it, for k_rollout, k_derivs, k_backward, k_search, k_multipliers, k_policy and k_plant (and, with the plant's
+// table, for plant_params).  ORDER: the trajectory's row first, then the roll-out's or the plant's row — whatever the pack
+// holds behind the first two: a slot named in both gets the latter.
+template <class... Behind>
+__device__ __forceinline__ void trajectory_params(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *__restrict__ values,
+                                                  const PolicyParamMap &map, const Behind &...) {
+    override_params(V, T, P, (size_t)b, 0, values, 0, map);
+}
+// the roll-out's own row (k_policy: values, shared, map) behind the trajectory's
+__device__ __forceinline__ void rollout_params_behind(ParamValues &V, ParamTable &T, const DevPtrs &P, size_t g, int r, const double *, const PolicyParamMap &,
+                                                      const double *__restrict__ values, int shared, const PolicyParamMap &map) {
+    override_params(V, T, P, g, r, values, shared, map, true);
+}
+
 template <bool PER_ROLLOUT_PARAMS, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
                                                                          double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
                                                                          double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
                                                                          Rows... rows) {
-    static_assert(sizeof...(Rows) == (PER_ROLLOUT_PARAMS ? 3 : 0), "k_policy<true>(..., values, shared, map); k_policy<false>(...)");
+    // the pack: [the context's per-trajectory table, its map,] [values, shared, map of the roll-outs' own rows]
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) == (PER_ROLLOUT_PARAMS ? 5 : 2);
+    static_assert(sizeof...(Rows) == (PER_TRAJECTORY ? 2 : 0) + (PER_ROLLOUT_PARAMS ? 3 : 0),
+                  "k_policy<true>(..., [table, map,] values, shared, map); k_policy<false>(..., [table, map])");
     const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
     if(g >= (size_t)P.B * (size_t)R) return;
     const int b = (int)(g / (size_t)R);
@@ -136,7 +159,9 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
     }
 
     ILQG_CALLBACKS(C, H);
-    if constexpr(PER_ROLLOUT_PARAMS) override_params(C_values, C_table, P, g, (int)(g - (size_t)b * (size_t)R), rows...);
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    if constexpr(PER_ROLLOUT_PARAMS && PER_TRAJECTORY) rollout_params_behind(C_values, C_table, P, g, (int)(g - (size_t)b * (size_t)R), rows...);
+    if constexpr(PER_ROLLOUT_PARAMS && !PER_TRAJECTORY) override_params(C_values, C_table, P, g, (int)(g - (size_t)b * (size_t)R), rows...);
     load_penalty_weights(C, P, b);
     el_t ct;
     multipliersEl_t mk;

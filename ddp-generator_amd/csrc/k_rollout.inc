@@ -79,8 +79,11 @@ constexpr int ROLL_BLOCK = WAVE * ILQG_ROLL_WAVES;
 static_assert(ILQG_ROLL_WAVES == ilqgdev::WAVES, "ilqgdev's ring is that of ONE wavefront per workgroup");
 #endif
 
-template <int KIND>
-__global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int mode, int a0) {
+template <int KIND, class... Rows>
+__global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int mode, int a0, Rows... rows) {
+    // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
+    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
+    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "k_rollout<...>(...) or k_rollout<..., const double *, PolicyParamMap>(..., table, map)");
     int b = blockIdx.x * ROLL_BLOCK + threadIdx.x;
     int ai = a0 + blockIdx.y;
     double *keep = nullptr;  // second stage: where this lane's trajectory is kept
@@ -125,6 +128,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
     const bool feedback = (alpha != 0.0);  // alpha == 0.0: u = u_nom without feedback (iLQG_func.tem:156-158)
 
     ILQG_CALLBACKS(C, H);
+    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
     // penalty weights of this trajectory; the initial roll-out runs before the solver entry sets them, with the
     // zero-initialised option set of the MEX entry (iLQG_mex.c:23,116; iLQG.c:233-234)
     if(HAS_MUL && KIND == RK_INIT) set_penalty_weights(C, 0.0, 0.0);

@@ -228,6 +228,50 @@ def _plant_param_rows(problem, params, B):
     return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1))
 
 
+def _params_batch_sizes(problem, params):
+    """the sizes of the parameters set_params_batch names, in dict order; refused here as the library refuses them"""
+    known = dict(problem.params)
+    sizes = []
+    for name in params:
+        if name not in known:
+            raise IlqgError("set_params_batch: params: Parameter name '%s' is not member of parameters struct." % name)
+        if known[name] < 1:
+            raise IlqgError("set_params_batch: params: '%s' has one value per time step; per-time-step parameters stay shared by all trajectories" % name)
+        sizes.append(known[name])
+    return sizes
+
+
+def _params_batch_rows(problem, params, B):
+    """(names, values [B, W]) for ilqg_batch_set_params_batch from host arrays: the named parameters one behind the other in
+    dict order, each array [B, size] (the last axis may be left out for size 1), copied as C-contiguous doubles whatever
+    their dtype and strides"""
+    cols = []
+    for (name, a), size in zip(params.items(), _params_batch_sizes(problem, params)):
+        if _is_cuda(a):
+            raise IlqgError("set_params_batch: params['%s'] is a tensor on the device: pass device=True" % name)
+        a = np.asarray(a, dtype=np.float64)
+        if tuple(a.shape) != (B, size) and not (size == 1 and tuple(a.shape) == (B,)):
+            raise IlqgError("set_params_batch: params['%s'] has shape %s, expected (%d, %d)%s"
+                            % (name, tuple(a.shape), B, size, " or (%d,)" % B if size == 1 else ""))
+        cols.append(a.reshape(B, size))
+    return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1))
+
+
+def _params_batch_tensors(problem, params, B, device):
+    """the same checks for float64 torch tensors on the solver's GPU: [(tensor, (B, size))]"""
+    cols = []
+    for (name, a), size in zip(params.items(), _params_batch_sizes(problem, params)):
+        what = "set_params_batch: params['%s']" % name
+        if not _is_cuda(a):
+            raise IlqgError("%s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % what)
+        shape = tuple(int(n) for n in a.shape)
+        if shape != (B, size) and not (size == 1 and shape == (B,)):
+            raise IlqgError("%s has shape %s, expected (%d, %d)%s" % (what, shape, B, size, " or (%d,)" % B if size == 1 else ""))
+        _cuda_address(a, shape, device, what)
+        cols.append((a, (B, size)))
+    return cols
+
+
 def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant, params, disturbance):
     """BatchSolver.receding_plant / MultiSolver.receding_plant: the checks, the arrays and the one library call"""
     B, nx, nu = solver.B, solver.problem.nx, solver.problem.nu
@@ -340,6 +384,11 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_policy_rollout_params.argtypes = named
         lib.ilqg_batch_policy_rollout_params_device.argtypes = named + [v]
         lib.ilqg_multi_policy_rollout_params.argtypes = named
+    if hasattr(lib, "ilqg_batch_set_params_batch"):  # (and for problem parameters per trajectory)
+        lib.ilqg_batch_set_params_batch.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v]
+        lib.ilqg_batch_set_params_batch_device.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v, v]
+        lib.ilqg_batch_get_params_batch.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_multi_set_params_batch.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v]
     if hasattr(lib, "ilqg_batch_receding_plant"):  # (and for the closed loop of planner and plant)
         lib.ilqg_batch_receding_plant.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, v, v, v, v, v, v]
         lib.ilqg_multi_receding_plant.argtypes = lib.ilqg_batch_receding_plant.argtypes
@@ -453,6 +502,43 @@ class BatchSolver:
     def set_param(self, name, value):
         v = np.ascontiguousarray(np.atleast_1d(value), dtype=np.float64)
         self._ck(self.lib.ilqg_batch_set_param(self.h, name.encode(), v, v.size))
+
+    def set_params_batch(self, params, device=False):
+        """problem parameters PER TRAJECTORY (ilqg_batch_set_params_batch): params = {name: array [B,size]} (the last axis
+        may be left out for size 1) — from the next launch on trajectory b plans, is rolled out and has its plant advance
+        under the batch's fixed-size parameters with every named one replaced by array[b].  Packed in dict order; a call
+        replaces the whole set; {} or None clears it (the batch is shared-only again).  Nothing is recomputed: costs and
+        records stay as they are until init() or shift().  Order with policy_rollout(params=...) and
+        receding_plant(params=...): the trajectory's row first, then the roll-out's or the plant's.  Per-time-step
+        parameters stay shared and cannot be named; set_param of a name that is per-trajectory is refused; lane-mapped
+        libraries only.  With device=True contiguous float64 torch tensors on the solver's GPU, packed with torch.cat on
+        torch's current stream (a single tensor is read where it is) and copied by the library in that stream's order
+        without a host wait (ilqg_batch_set_params_batch_device)."""
+        if params is not None and not isinstance(params, dict):
+            raise IlqgError("set_params_batch: params must be a dict of parameter name -> array [B, size]; {} or None clears the set")
+        if not params:
+            self._ck(_receding_entry(self.lib, "ilqg_batch_set_params_batch")(self.h, 0, None, None))
+            return
+        if not device:
+            names, values = _params_batch_rows(self.problem, params, self.B)
+            self._ck(_receding_entry(self.lib, "ilqg_batch_set_params_batch")(self.h, len(names), names, _address(values)))
+            return
+        cols = _params_batch_tensors(self.problem, params, self.B, self.device)
+        entry = _receding_entry(self.lib, "ilqg_batch_set_params_batch_device")
+        torch = _torch_on_gpu()
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):  # (a single tensor is the table as it lies: [B] and [B, 1] are the same memory)
+            values = cols[0][0] if len(cols) == 1 else torch.cat([a.reshape(shape) for a, shape in cols], dim=-1)
+        names = _policy_param_names(params)
+        self._ck(entry(self.h, len(names), names, C.c_void_p(values.data_ptr() or None), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+
+    def params_batch(self, name):
+        """[B,size]: what trajectory b sees of fixed-size parameter `name` (ilqg_batch_get_params_batch) — its row of
+        set_params_batch, or the shared value repeated"""
+        size = dict(self.problem.params).get(name, 0)
+        out = np.zeros((self.B, max(size, 1)))
+        self._ck(_receding_entry(self.lib, "ilqg_batch_get_params_batch")(self.h, name.encode(), _address(out)))
+        return out
 
     def init(self, x0, u0):
         """x0 [B,nx], u0 [B,N,nu]: initial roll-out (clamps u) and solver entry state"""
@@ -828,6 +914,18 @@ class MultiSolver:
 
     def iterate(self, n=1):
         self._ck(self.lib.ilqg_multi_iterate(self.h, int(n)))
+
+    def set_params_batch(self, params):
+        """BatchSolver.set_params_batch on every shard, each with the rows of its trajectories (ilqg_multi_set_params_batch),
+        numpy arrays"""
+        if params is not None and not isinstance(params, dict):
+            raise IlqgError("set_params_batch: params must be a dict of parameter name -> array [B, size]; {} or None clears the set")
+        entry = _receding_entry(self.lib, "ilqg_multi_set_params_batch")
+        if not params:
+            self._ck(entry(self.h, 0, None, None))
+            return
+        names, values = _params_batch_rows(self.problem, params, self.B)
+        self._ck(entry(self.h, len(names), names, _address(values)))
 
     def shift(self, steps, x0=None, u_tail=None):
         """BatchSolver.shift on every shard (ilqg_multi_shift)"""

@@ -94,6 +94,50 @@ const char *ilqg_batch_error(const ilqg_batch_t *c);
 int ilqg_batch_set_option(ilqg_batch_t *c, const char *name, const double *value, int n);
 /* problem parameter by name, shared by all trajectories (iLQG_mex.c:70-84) */
 int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value, int n);
+/* PROBLEM PARAMETERS PER TRAJECTORY: a goal per agent, a model per vehicle, a sweep over a cost weight — a batch that differs
+ * in more than x0.  From the next launch on, every generated callback evaluated for trajectory b sees the batch's fixed-size
+ * parameters with the NAMED ones replaced by row b of values — in every stage: the initial roll-out of ilqg_batch_init and
+ * ilqg_batch_shift, calc_derivs, back_pass in all three modes, line_search, the multiplier update and the cost re-sweep,
+ * iterate, solve, receding.  Like ilqg_batch_set_param the call recomputes nothing: costs and records of the current
+ * trajectories stay as they are until ilqg_batch_init or ilqg_batch_shift.  PER-TIME-STEP PARAMETERS (size -1) STAY SHARED.
+ *
+ * names, W and the row layout are those of ilqg_batch_policy_rollout_params with n_starts = 1 and shared = 0: n_names host
+ * strings, each a fixed-size parameter of paramdesc[], in any order, none twice; W = the sum of their sizes; values [B][W],
+ * row b belongs to trajectory b, the named parameters one behind the other in the order of names, each contiguous.  A call
+ * REPLACES the whole per-trajectory set, it is not incremental.  n_names = 0 clears it (names and values are not read): the
+ * batch is shared-only again and runs the very kernels of a batch that never had a table.
+ *
+ * ORDER WITH THE ROLL-OUT AND PLANT TABLES: THE TRAJECTORY'S ROW FIRST, THEN THE ROLL-OUT'S OR THE PLANT'S ROW.  Where those
+ * entries say "the batch's parameters", read "trajectory b's": ilqg_batch_policy_rollout evaluates roll-out (b, r) under
+ * trajectory b's parameters; ilqg_batch_policy_rollout_params puts its named columns on top of them (a parameter named in
+ * both gets the roll-out's value); the plant of ilqg_batch_receding_plant with n_names = 0 is trajectory b's model, and with
+ * named plant parameters the plant's row goes on top of it.  ilqg_batch_head, ilqg_batch_shift_param and every getter are
+ * unaffected.
+ * Option "compact": the rows travel with their trajectories, a compacted solve stays bit for bit the plain one.
+ * ilqg_batch_solve_stream is REFUSED while a per-trajectory set exists: the rows belong to slots, the starts of a stream pass
+ * through them, and a table per start is out of scope.  Option bw_split runs the one-wavefront backward pass while a set
+ * exists.
+ *
+ * ilqg_batch_set_params_batch takes host memory and waits once per group; ilqg_batch_set_params_batch_device takes DEVICE
+ * memory under the stream contract of ilqg_batch_head_device (event in, one event per group out, no host wait, no allocation
+ * in steady state) — for an estimator on the GPU that refreshes the rows every control interval.  The library copies the
+ * table into a buffer of its own, which only grows: the caller's memory is free afterwards (in the device form: once its
+ * stream has passed the call).
+ * ilqg_batch_get_params_batch: out [B][size], what trajectory b sees of fixed-size parameter `name` — its row, or the shared
+ * value repeated where the parameter is not per-trajectory.
+ * ilqg_multi_set_params_batch (below): every shard gets the rows from its first trajectory on.
+ *
+ * REFUSED, with the argument named in the error text and before anything is launched, allocated or changed: a name that is
+ * no parameter ("Parameter name '%s' is not member of parameters struct."), a per-time-step parameter, a name given twice,
+ * n_names < 0, n_names > 0 with names or values NULL, in the device form values that is not device memory of the context's
+ * device; ilqg_batch_set_param of a name that currently is per-trajectory (the text points at
+ * ilqg_batch_set_params_batch(c, 0, NULL, NULL)); and every library of the WAVE MAPPING (one wavefront per trajectory: the
+ * *_wave libraries and the problems with N_X = 10 or 16 — the text names the mapping): those kernels do not carry parameters
+ * per lane.  Not supported, beside the wave, row and quad mappings: per-trajectory values of per-time-step parameters, a
+ * table per start in ilqg_batch_solve_stream, the drop-in iLQG(). */
+int ilqg_batch_set_params_batch(ilqg_batch_t *c, int n_names, const char *const *names, const double *values /* [B][W] host */);
+int ilqg_batch_set_params_batch_device(ilqg_batch_t *c, int n_names, const char *const *names, const double *values /* [B][W] device */, void *stream);
+int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out /* [B][size] host */);
 
 /* initial conditions and initial controls, then the initial roll-out
  * (forward_pass with alpha = 0, which also clamps u; iLQG_mex.c:113-120)
@@ -338,6 +382,7 @@ int ilqg_multi_devices(const ilqg_multi_t *m);
 ilqg_batch_t *ilqg_multi_shard(ilqg_multi_t *m, int g, int *first, int *count);
 int ilqg_multi_set_option(ilqg_multi_t *m, const char *name, const double *value, int n);
 int ilqg_multi_set_param(ilqg_multi_t *m, const char *name, const double *value, int n);
+int ilqg_multi_set_params_batch(ilqg_multi_t *m, int n_names, const char *const *names, const double *values);  /* [batch][W], sharded by rows */
 int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0);
 int ilqg_multi_set_u(ilqg_multi_t *m, const double *u);
 int ilqg_multi_init(ilqg_multi_t *m);
