@@ -76,6 +76,9 @@ struct ilqg_batch {
     /* per-trajectory problem parameters (ilqg_batch_set_params_batch): the indices of the named parameters in the order of
      * the caller's names, and W, the width of a row; pb_n = 0: none, the batch is shared-only */
     int pb_n, pb_W, pb_named[64];
+    /* per-time-step parameters per trajectory (ilqg_batch_set_param_steps_batch): ps_on[i] != 0 while parameter i (size -1)
+     * has a row per trajectory on the groups' devices; c->p[i] keeps the shared window set_param last gave it */
+    char ps_on[64];
     /* full solves: finished trajectories are retired (ilqg_batch_solve) */
     int compact;                     /* 0: never; else the smallest number of live trajectories still worth a smaller context */
     int trace_n;                     /* the last solve, poll by poll: iterations done, trajectories active, slots iterated */
@@ -458,6 +461,13 @@ int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value,
                     return 1;
                 }
         }
+        if(i < 64 && c->ps_on[i]) {
+            snprintf(c->err, sizeof(c->err), "ilqg_batch_set_param: name: parameter '%s' currently has a window per trajectory "
+                     "(ilqg_batch_set_param_steps_batch); a shared window would be read by no trajectory.  Use "
+                     "ilqg_batch_set_param_steps_batch / ilqg_batch_shift_param_batch, or make the name shared again first: "
+                     "ilqg_batch_set_param_steps_batch(c, name, values = NULL)", name);
+            return 1;
+        }
         memcpy(c->p[i], value, sizeof(double) * n);
         c->p_given[i] = 1;
         c->params_pushed = 0;
@@ -820,6 +830,122 @@ int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out) 
     return 0;
 }
 
+/* Per-time-step parameters per trajectory: a reference track per agent.  The rows live on the groups' devices only, each
+ * group its slice (ilqg_dev_set_param_steps_batch); the host keeps which names have them (ps_on).  step_name resolves a name
+ * to a parameter of size -1 and makes the refusals every entry below shares, before a group is touched. */
+static int step_name(ilqg_batch_t *c, const char *who, const char *name, int need_rows, int *index) {
+    int i, dims[8];
+    ilqg_dev_dims(dims);
+    if(dims[7]) {
+        snprintf(c->err, sizeof(c->err), "%s: this library maps one wavefront to a trajectory (the wave mapping: the *_wave libraries and the "
+                 "problems with N_X = 10 or 16); its kernels do not carry parameters per lane.  Per-trajectory parameters need a lane-mapped "
+                 "library", who);
+        return 1;
+    }
+    if(!name) {
+        snprintf(c->err, sizeof(c->err), "%s: name is NULL", who);
+        return 1;
+    }
+    for(i = 0; i < n_params; i++)
+        if(strcmp(paramdesc[i]->name, name) == 0) break;
+    if(i == n_params) {
+        snprintf(c->err, sizeof(c->err), "%s: name: Parameter name '%s' is not member of parameters struct.", who, name);
+        return 1;
+    }
+    if(paramdesc[i]->size != -1) {
+        snprintf(c->err, sizeof(c->err), "%s: name: parameter '%s' has a fixed size of %d, not one value per time step (size -1); fixed-size "
+                 "parameters per trajectory are set by ilqg_batch_set_params_batch", who, name, paramdesc[i]->size);
+        return 1;
+    }
+    if(i >= 64) {
+        snprintf(c->err, sizeof(c->err), "%s: name: more than 64 problem parameters", who);
+        return 1;
+    }
+    if(need_rows && !c->ps_on[i]) {
+        snprintf(c->err, sizeof(c->err), "%s: name: parameter '%s' is currently shared by all trajectories: it has no rows to move.  Give it "
+                 "rows first (ilqg_batch_set_param_steps_batch), or move the shared window (ilqg_batch_shift_param)", who, name);
+        return 1;
+    }
+    *index = i;
+    return 0;
+}
+
+static int set_param_steps_batch(ilqg_batch_t *c, const char *who, int on_device, const char *name, const double *values, void *stream) {
+    int g, i = 0;
+    const size_t n = (size_t)c->N + 1;
+    if(step_name(c, who, name, 0, &i)) return 1;
+    if(values && on_device && ilqg_dev_check_device_ptr(c->dev[0], values, "values")) return fail(c, who);
+    if(values && on_device) EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "set_param_steps_batch: stream");
+    EACH_GROUP(g) {
+        if(ilqg_dev_set_param_steps_batch(c->dev[g], i, values ? values + (size_t)c->first[g] * n : NULL, on_device)) return fail(c, who);
+        if(values && on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "set_param_steps_batch: stream");
+    }
+    c->ps_on[i] = values ? 1 : 0;
+    return 0;
+}
+
+int ilqg_batch_set_param_steps_batch(ilqg_batch_t *c, const char *name, const double *values) {
+    if(!c) return 1;
+    return set_param_steps_batch(c, "ilqg_batch_set_param_steps_batch", 0, name, values, NULL);
+}
+
+int ilqg_batch_set_param_steps_batch_device(ilqg_batch_t *c, const char *name, const double *values, void *stream) {
+    if(!c) return 1;
+    return set_param_steps_batch(c, "ilqg_batch_set_param_steps_batch_device", 1, name, values, stream);
+}
+
+/* what trajectory b sees of per-time-step parameter `name`: its row (read back from the groups), or the shared window, repeated */
+int ilqg_batch_get_param_steps_batch(ilqg_batch_t *c, const char *name, double *out) {
+    static const char who[] = "ilqg_batch_get_param_steps_batch";
+    int g, b, i = 0;
+    size_t n;
+    if(!c) return 1;
+    if(!out) {
+        snprintf(c->err, sizeof(c->err), "%s: out is NULL", who);
+        return 1;
+    }
+    if(step_name(c, who, name, 0, &i)) return 1;
+    n = (size_t)c->N + 1;
+    if(!c->ps_on[i]) {
+        if(!c->p_given[i]) {
+            snprintf(c->err, sizeof(c->err), "Parameter name '%s' was not set.", name);
+            return 1;
+        }
+        for(b = 0; b < c->B; b++) memcpy(out + (size_t)b * n, c->p[i], sizeof(double) * n);
+        return 0;
+    }
+    EACH_GROUP(g) if(ilqg_dev_get_param_steps_batch(c->dev[g], i, out + (size_t)c->first[g] * n)) return fail(c, who);
+    return 0;
+}
+
+/* the windows move with the horizon, each row in place on the device (k_shift_param_rows) */
+static int shift_param_batch(ilqg_batch_t *c, const char *who, int on_device, const char *name, int steps, const double *tail, void *stream) {
+    int g, i = 0;
+    if(step_name(c, who, name, 1, &i)) return 1;
+    if(steps < 0 || steps > c->N) {
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 0 .. n_hor = %d", who, steps, c->N);
+        return 1;
+    }
+    if(tail && on_device && ilqg_dev_check_device_ptr(c->dev[0], tail, "tail")) return fail(c, who);
+    if(steps == 0) return 0;
+    if(tail && on_device) EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "shift_param_batch: stream");
+    EACH_GROUP(g) {
+        if(ilqg_dev_shift_param_batch(c->dev[g], i, steps, tail ? tail + (size_t)c->first[g] * (size_t)steps : NULL, on_device)) return fail(c, who);
+        if(tail && on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift_param_batch: stream");
+    }
+    return 0;
+}
+
+int ilqg_batch_shift_param_batch(ilqg_batch_t *c, const char *name, int steps, const double *tail) {
+    if(!c) return 1;
+    return shift_param_batch(c, "ilqg_batch_shift_param_batch", 0, name, steps, tail, NULL);
+}
+
+int ilqg_batch_shift_param_batch_device(ilqg_batch_t *c, const char *name, int steps, const double *tail, void *stream) {
+    if(!c) return 1;
+    return shift_param_batch(c, "ilqg_batch_shift_param_batch_device", 1, name, steps, tail, stream);
+}
+
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
     int g;
     if(steps < 0 || steps >= c->N) {
@@ -927,6 +1053,13 @@ int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const d
     }
     if(steps < 0 || steps > c->N) {
         snprintf(c->err, sizeof(c->err), "ilqg_batch_shift_param: steps = %d, must be in 0 .. n_hor = %d", steps, c->N);
+        return 1;
+    }
+    if(i < 64 && c->ps_on[i]) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift_param: name: parameter '%s' currently has a window per trajectory "
+                 "(ilqg_batch_set_param_steps_batch); moving the shared window would move what no trajectory reads.  Use "
+                 "ilqg_batch_shift_param_batch, or make the name shared again first: ilqg_batch_set_param_steps_batch(c, name, "
+                 "values = NULL)", name);
         return 1;
     }
     if(steps == 0) return 0;
@@ -1129,6 +1262,15 @@ int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const 
         return fail_msg(c, "ilqg_batch_solve_stream: the batch has per-trajectory parameters (ilqg_batch_set_params_batch), which belong to "
                            "its slots, while the starts of a stream pass through them: a table per start is not supported.  Clear the set "
                            "first: ilqg_batch_set_params_batch(c, 0, NULL, NULL)");
+    {
+        int i;
+        for(i = 0; i < n_params && i < 64; i++)
+            if(c->ps_on[i])
+                return fail_msg(c, "ilqg_batch_solve_stream: the batch has per-trajectory windows of a per-time-step parameter "
+                                   "(ilqg_batch_set_param_steps_batch), which belong to its slots, while the starts of a stream pass "
+                                   "through them: rows per start are not supported.  Make the names shared again first: "
+                                   "ilqg_batch_set_param_steps_batch(c, name, values = NULL)");
+    }
     if(push_config(c)) return 1;
     ilqg_dev_dims(dims);
     NXd = dims[0];
@@ -1879,6 +2021,22 @@ int ilqg_multi_set_params_batch(ilqg_multi_t *m, int n_names, const char *const 
                 if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
     EACH_SHARD(g)
         if(ilqg_batch_set_params_batch(m->shard[g], n_names, names, values ? values + (size_t)m->first[g] * W : NULL)) return multi_fail(m, g);
+    return 0;
+}
+/* every shard's rows of a per-time-step parameter, and its tails: those from its first trajectory on */
+int ilqg_multi_set_param_steps_batch(ilqg_multi_t *m, const char *name, const double *values) {
+    int g;
+    if(!m) return 1;
+    EACH_SHARD(g)
+        if(ilqg_batch_set_param_steps_batch(m->shard[g], name, values ? values + (size_t)m->first[g] * ((size_t)m->N + 1) : NULL)) return multi_fail(m, g);
+    return 0;
+}
+int ilqg_multi_shift_param_batch(ilqg_multi_t *m, const char *name, int steps, const double *tail) {
+    int g;
+    if(!m) return 1;
+    EACH_SHARD(g)
+        if(ilqg_batch_shift_param_batch(m->shard[g], name, steps, tail ? tail + (size_t)m->first[g] * (size_t)(steps > 0 ? steps : 0) : NULL))
+            return multi_fail(m, g);
     return 0;
 }
 int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0) {

@@ -122,6 +122,7 @@ enum {
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
     ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout with a table) */
     ILQG_K_PLANT,    /* k_plant (ilqg_dev_plant_advance) */
+    ILQG_K_SHIFT_PARAM_ROWS, /* k_shift_param_rows (ilqg_dev_shift_param_batch) */
     ILQG_K_COUNT
 };
 
@@ -151,6 +152,17 @@ int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const dou
  * trajectory and launches no kernel.  get: the table as it is on the device, rows [batch][W] (host); waits. */
 int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, const double *values, int on_device);
 int ilqg_dev_get_params_batch(ilqg_dev_t *d, double *rows);
+/* Per-time-step parameters per trajectory (lane mapping only).  index: a parameter of size -1 in paramdesc[].  From the next
+ * launch on the callbacks evaluated for trajectory b read p[index][k], k = 0 .. n_hor, from row b of values [batch][n_hor + 1]
+ * (trajectory-major); values = NULL: the shared window of ilqg_dev_set_params again.  One grow-only buffer per parameter,
+ * independent of the fixed-size table above and of ilqg_dev_set_params; on_device as above.  With no rows and no table left
+ * the kernels are those of a context that never had either.  ilqg_dev_move carries the rows.  Launches no kernel.
+ * get: the rows as they are on the device (host, [batch][n_hor + 1]); waits; an error where the parameter is shared.
+ * shift: per row what ilqg_dev_shift_param does, in place (k_shift_param_rows); tail [batch][steps] or NULL (each row's
+ * last value held), host memory (staged, waits once) or with on_device != 0 device memory (no wait). */
+int ilqg_dev_set_param_steps_batch(ilqg_dev_t *d, int index, const double *values, int on_device);
+int ilqg_dev_get_param_steps_batch(ilqg_dev_t *d, int index, double *rows);
+int ilqg_dev_shift_param_batch(ilqg_dev_t *d, int index, int steps, const double *tail, int on_device);
 int ilqg_dev_set_opts(ilqg_dev_t *d, const ilqg_dev_opts_t *o);
 
 /* host <-> device, host side trajectory-major [batch][steps][width] */

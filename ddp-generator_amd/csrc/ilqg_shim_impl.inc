@@ -95,6 +95,16 @@ struct ilqg_dev {
     size_t pb_bytes;
     bool pb_on;
     PolicyParamMap pb_map;
+    // per-time-step parameters per trajectory (ilqg_dev_set_param_steps_batch): for the s-th parameter of size -1 its rows
+    // [Bp][N + 1] (trajectory-major; rows B .. Bp - 1 are zero and belong to nobody); grow-only like pb_values, sr_on[s]: in use
+    static constexpr int SR = N_STEP_PARAMS > 0 ? N_STEP_PARAMS : 1;
+    double *sr_rows[SR];
+    size_t sr_bytes[SR];
+    bool sr_on[SR];
+    // what LAUNCH_PV hands the rows twins: rows_on = pb_on or some sr_on; rows_map = pb_map (empty without a table) with the
+    // step rows in use (rows_refresh, after every change of either set)
+    bool rows_on;
+    PolicyParamMap rows_map;
     hipEvent_t ext_in, ext_out;  // ordering with a stream of the caller (ilqg_dev_stream_in / _out), made with the context
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
@@ -342,6 +352,19 @@ static int on_scratch_stream(ilqg_dev_t *d, bool needed, hipStream_t st, Fn &&la
     return 0;
 }
 
+// the step rows in use into a map (rows_refresh)
+template <class Map>
+static bool step_rows_into(Map &m, const ilqg_dev_t *d) {  // (a template: the member exists only with N_STEP_PARAMS > 0)
+    bool any = false;
+    if constexpr(N_STEP_PARAMS > 0) {
+        for(int s = 0; s < N_STEP_PARAMS; s++) {
+            m.rows[s] = d->sr_on[s] ? d->sr_rows[s] : nullptr;
+            any = any || d->sr_on[s];
+        }
+    }
+    return any;
+}
+
 extern "C" {
 
 const char *ilqg_dev_error(void) { return g_err.c_str(); }
@@ -373,7 +396,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
-                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant"};
+                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant", "k_shift_param_rows"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -424,6 +447,12 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
     d->pb_values = nullptr;
     d->pb_bytes = 0;
     d->pb_on = false;
+    for(int s = 0; s < ilqg_dev::SR; s++) {
+        d->sr_rows[s] = nullptr;
+        d->sr_bytes[s] = 0;
+        d->sr_on[s] = false;
+    }
+    d->rows_on = false;
     d->P.B = d->B;
     d->P.Bp = d->Bp;
     d->P.N = d->N;
@@ -639,6 +668,8 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
     if(d->log_c) hipFree(d->log_c);
     plant_release(d);
     if(d->pb_values) hipFree(d->pb_values);
+    for(int s = 0; s < ilqg_dev::SR; s++)
+        if(d->sr_rows[s]) hipFree(d->sr_rows[s]);
     for(double *p : d->param_bufs) hipFree(p);
     if(d->P.p) hipFree(d->P.p);
     if(d->staging) hipFree(d->staging);
@@ -698,6 +729,19 @@ int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const dou
 // Per-trajectory problem parameters.  Nothing here touches a trajectory: like ilqg_dev_set_params it only changes what the
 // NEXT launch reads.  The copy is enqueued on the context's stream, behind every launch that still reads the old rows.
 static const PolicyParamMap *policy_param_map(int n_named, const int *named, const double *values, PolicyParamMap &map);
+// the map the rows twins get (LAUNCH_PV): the table's, or an empty one, with the step rows in use
+static void rows_refresh(ilqg_dev_t *d) {
+    PolicyParamMap m;
+    if(d->pb_on) {
+        m = d->pb_map;
+    } else {
+        for(int j = 0; j < ILQG_PTOTAL; j++) m.src[j] = -1;
+        m.W = 0;
+    }
+    const bool steps = step_rows_into(m, d);
+    d->rows_map = m;
+    d->rows_on = d->pb_on || steps;
+}
 int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, const double *values, int on_device) {
     HIP_TRY(hipSetDevice(d->device));
     if(WAVE_MAP) {
@@ -711,6 +755,7 @@ int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, cons
     }
     if(n_named == 0) {
         d->pb_on = false;  // (the buffer stays: a set that comes back allocates nothing)
+        rows_refresh(d);
         return 0;
     }
     PolicyParamMap map;
@@ -722,6 +767,7 @@ int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, cons
         d->pb_values = nullptr;
         d->pb_bytes = 0;
         d->pb_on = false;
+        rows_refresh(d);
         HIP_TRY(hipMalloc((void **)&d->pb_values, bytes));
         d->pb_bytes = bytes;
     }
@@ -729,6 +775,72 @@ int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, cons
     if(!on_device) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's array is its own again
     d->pb_map = map;
     d->pb_on = true;
+    rows_refresh(d);
+    return 0;
+}
+
+// Per-time-step parameters per trajectory.  The same contract: only what the NEXT launch reads changes, the copy goes onto
+// the context's stream behind every launch that reads the old rows, the buffer of a parameter only grows.
+// step_slot: which of the problem's size -1 parameters `index` is, or -1
+static int step_slot(int index) {
+    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+    if(index < 0 || index >= ILQG_NP || sizes[index] != -1) return -1;
+    int s = 0;
+    for(int i = 0; i < index; i++) s += sizes[i] == -1 ? 1 : 0;
+    return s;
+}
+// the buffer of slot s holds Bp rows, the rows beyond B zero (no lane reads them; a stray one would read zeros, not beyond)
+static int step_rows_buffer(ilqg_dev_t *d, int s) {
+    const size_t n = (size_t)d->N + 1, bytes = (size_t)d->Bp * n * sizeof(double);
+    if(bytes > d->sr_bytes[s]) {
+        HIP_TRY(hipStreamSynchronize(d->stream));  // (launches in flight read the old buffer)
+        if(d->sr_rows[s]) HIP_TRY(hipFree(d->sr_rows[s]));
+        d->sr_rows[s] = nullptr;
+        d->sr_bytes[s] = 0;
+        d->sr_on[s] = false;
+        rows_refresh(d);
+        HIP_TRY(hipMalloc((void **)&d->sr_rows[s], bytes));
+        d->sr_bytes[s] = bytes;
+    }
+    if(!d->sr_on[s] && d->Bp > d->B)
+        HIP_TRY(hipMemsetAsync(d->sr_rows[s] + (size_t)d->B * n, 0, (size_t)(d->Bp - d->B) * n * sizeof(double), d->stream));
+    return 0;
+}
+int ilqg_dev_set_param_steps_batch(ilqg_dev_t *d, int index, const double *values, int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(WAVE_MAP) {
+        g_err = "set_param_steps_batch: this library maps one wavefront to a trajectory (wave mapping); its kernels do not carry "
+                "parameters per lane, per-trajectory parameters need a lane-mapped library";
+        return 1;
+    }
+    const int s = step_slot(index);
+    if(s < 0) {
+        g_err = "set_param_steps_batch: not a parameter with one value per time step";
+        return 1;
+    }
+    if(!values) {
+        d->sr_on[s] = false;  // (the buffer stays: rows that come back allocate nothing)
+        rows_refresh(d);
+        return 0;
+    }
+    if(step_rows_buffer(d, s)) return 1;
+    const size_t bytes = (size_t)d->B * ((size_t)d->N + 1) * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(d->sr_rows[s], values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+    if(!on_device) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's array is its own again
+    d->sr_on[s] = true;
+    rows_refresh(d);
+    return 0;
+}
+
+int ilqg_dev_get_param_steps_batch(ilqg_dev_t *d, int index, double *rows) {
+    HIP_TRY(hipSetDevice(d->device));
+    const int s = step_slot(index);
+    if(s < 0 || !d->sr_on[s]) {
+        g_err = "get_param_steps_batch: the parameter has no rows per trajectory in this context";
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(rows, d->sr_rows[s], (size_t)d->B * ((size_t)d->N + 1) * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
 
@@ -990,8 +1102,9 @@ int ilqg_dev_io_end(ilqg_dev_t *d) {
 
 // The ONE place that picks the instantiation of a lane-mapped kernel that takes ParamValues: the kernel as it was before
 // there were per-trajectory parameters — its old name, an empty pack, not one argument more — unless the context holds a
-// table (ilqg_dev_set_params_batch); then the instantiation whose pack is the table and its map, behind the kernel's own
-// arguments.  K: the kernel's name with its own template arguments, left open, in parentheses: (k_rollout<RK_INIT).  The two
+// table (ilqg_dev_set_params_batch) or rows of a per-time-step parameter (ilqg_dev_set_param_steps_batch); then the
+// instantiation whose pack is the table and its map, behind the kernel's own arguments — with step rows only, a table that
+// is not read under an empty map (rows_refresh).  K: the kernel's name with its own template arguments, left open, in parentheses: (k_rollout<RK_INIT).  The two
 // kernels that are no templates have a twin of another name: LAUNCH_PV_AS(d, (k_derivs), (k_derivs_rows<ILQG_PV_ROWS>), ...).
 // Both forms share the kernel's timing slot.  The wave mapping has no second form (ilqg_dev_set_params_batch refuses).
 #define ILQG_OPEN_NAME(...) __VA_ARGS__
@@ -999,8 +1112,8 @@ int ilqg_dev_io_end(ilqg_dev_t *d) {
 #if !ILQG_WAVE_MAP
 #define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...)                                                                    \
     do {                                                                                                                                \
-        if((d)->pb_on)                                                                                                                  \
-            hipLaunchKernelGGL((ILQG_OPEN_NAME ROWS), grid, block, lds, stream, __VA_ARGS__, (const double *)(d)->pb_values, (d)->pb_map); \
+        if((d)->rows_on)                                                                                                                \
+            hipLaunchKernelGGL((ILQG_OPEN_NAME ROWS), grid, block, lds, stream, __VA_ARGS__, (const double *)(d)->pb_values, (d)->rows_map); \
         else                                                                                                                            \
             hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__);                                         \
     } while(0)
@@ -1321,15 +1434,15 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
     const dim3 grid = grid1((size_t)d->B * (size_t)R, ROLL_BLOCK);
     // (with a per-trajectory table — lane mapping only — the trajectory's row goes first, the roll-out's behind it)
 #if !ILQG_WAVE_MAP
-    if(d->pb_on && !map) {
+    if(d->rows_on && !map) {
         Timed t(d, ILQG_K_POLICY, roll_stream(d));
         hipLaunchKernelGGL((k_policy<false, const double *, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0,
-                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values, d->pb_map);
-    } else if(d->pb_on) {
+                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values, d->rows_map);
+    } else if(d->rows_on) {
         Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
         hipLaunchKernelGGL((k_policy<true, const double *, PolicyParamMap, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0,
                            roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values,
-                           d->pb_map, values, shared ? 1 : 0, *map);
+                           d->rows_map, values, shared ? 1 : 0, *map);
     } else
 #endif
     if(!map) {
@@ -1473,15 +1586,15 @@ int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
     {
         Timed t(d, ILQG_K_PLANT, roll_stream(d));
 #if !ILQG_WAVE_MAP  // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
-        if(d->pb_on && d->plant_named)
+        if(d->rows_on && d->plant_named)
             hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK),
                                dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed,
                                (const double *)d->plant_dist, round * steps, rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c,
-                               (const double *)d->pb_values, d->pb_map, (const double *)d->plant_values, d->plant_map);
-        else if(d->pb_on)
+                               (const double *)d->pb_values, d->rows_map, (const double *)d->plant_values, d->plant_map);
+        else if(d->rows_on)
             hipLaunchKernelGGL((k_plant<false, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d),
                                d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps,
-                               rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c, (const double *)d->pb_values, d->pb_map);
+                               rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c, (const double *)d->pb_values, d->rows_map);
         else
 #endif
         if(d->plant_named)
@@ -1589,6 +1702,35 @@ int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail
     HIP_TRY(hipGetLastError());
     d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
     return tail ? io_done(d) : 0;
+}
+
+// the same per row of a per-trajectory window: k_shift_param_rows, one workgroup per trajectory
+int ilqg_dev_shift_param_batch(ilqg_dev_t *d, int index, int steps, const double *tail, int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    const int s = step_slot(index);
+    if(s < 0 || !d->sr_on[s]) {
+        g_err = "ilqg_dev_shift_param_batch: the parameter has no rows per trajectory in this context";
+        return 1;
+    }
+    if(steps < 0 || steps > d->N) {
+        g_err = "ilqg_dev_shift_param_batch: steps must be in 0 .. n_hor";
+        return 1;
+    }
+    if(steps == 0) return 0;
+    const double *tail_dev = tail;
+    if(tail && !on_device) {
+        void *dev, *pin;
+        const size_t bytes = (size_t)d->B * (size_t)steps * sizeof(double);
+        if(stage(d, bytes, &dev, &pin)) return 1;
+        if(stage_in(d, dev, pin, tail, bytes)) return 1;
+        tail_dev = (const double *)dev;
+    }
+    {
+        Timed t(d, ILQG_K_SHIFT_PARAM_ROWS);
+        hipLaunchKernelGGL(k_shift_param_rows, dim3(d->B), dim3(PARAM_BLOCK), 0, d->stream, d->sr_rows[s], d->N + 1, steps, tail_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    return (tail && !on_device) ? io_done(d) : 0;
 }
 
 #if ILQG_WAVE_MAP
@@ -1835,7 +1977,7 @@ int ilqg_dev_backward(ilqg_dev_t *d, int mode) {
         else if(mode == 1)
             LAUNCH_PV(d, (k_backward<1), grid, block, 0, d->stream, d->P, d->O, d->pv);
 #if ILQG_HAVE_SPLIT
-        else if(d->O.bw_split && !HAS_MUL && !d->pb_on)  // (k_backward_split knows the shared parameters only)
+        else if(d->O.bw_split && !HAS_MUL && !d->rows_on)  // (k_backward_split knows the shared parameters only)
             hipLaunchKernelGGL(k_backward_split, grid, dim3(2 * WAVE), 0, d->stream, d->P, d->O, d->pv);
 #endif
         else
@@ -2106,7 +2248,21 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
             dst->pb_map = src->pb_map;
             dst->pb_on = true;
         }
+        rows_refresh(dst);
         hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->pb_values, (const double *)src->pb_values, idx,
+                           idx + count, count, (int)W);
+        HIP_TRY(hipGetLastError());
+    }
+    for(int s = 0; s < N_STEP_PARAMS; s++) {  // ... and their rows of the per-time-step parameters, W = n_hor + 1
+        if(!src->sr_on[s]) continue;
+        const size_t W = (size_t)src->N + 1;
+        if(!dst->sr_on[s]) {  // (rows nothing has moved into yet are zero)
+            if(step_rows_buffer(dst, s)) return 1;
+            HIP_TRY(hipMemsetAsync(dst->sr_rows[s], 0, (size_t)dst->B * W * sizeof(double), dst->stream));
+            dst->sr_on[s] = true;
+            rows_refresh(dst);
+        }
+        hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->sr_rows[s], (const double *)src->sr_rows[s], idx,
                            idx + count, count, (int)W);
         HIP_TRY(hipGetLastError());
     }

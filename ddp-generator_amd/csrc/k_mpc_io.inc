@@ -71,3 +71,20 @@ __global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param(double *__restrict_
         if(k < n) p[k] = v;
     }
 }
+
+// The per-row form, for the per-trajectory windows (ilqg_dev_shift_param_batch): rows [B][n], tail [B][steps] or null.  The
+// row is picked by the workgroup index; within a row the same ascending blocks, the same barrier, the same argument — no
+// other workgroup touches the row.  Index arithmetic over B n in size_t.
+__global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param_rows(double *__restrict__ rows, int n, int steps, const double *__restrict__ tail) {
+    const int t = (int)threadIdx.x;
+    if(steps <= 0) return;
+    double *p = rows + (size_t)blockIdx.x * (size_t)n;
+    const double *tl = tail ? tail + (size_t)blockIdx.x * (size_t)steps : nullptr;
+    for(int k0 = 0; k0 < n; k0 += PARAM_BLOCK) {
+        const int k = k0 + t, from = k + steps;
+        double v = 0.0;
+        if(k < n) v = from < n ? p[from] : (tl ? tl[from - n] : p[n - 1]);
+        __syncthreads();
+        if(k < n) p[k] = v;
+    }
+}

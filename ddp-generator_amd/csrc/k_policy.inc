@@ -78,7 +78,24 @@ __device__ __forceinline__ void policy_control(double (&uin)[NU], const NomStep 
 // branch; an overridden slot lives in two vector registers instead of two scalar ones.  The policy (x, u, l, L of slot b),
 // the multipliers, the penalty weights and the per-time-step parameters are the batch's.  k_policy<false> has no further
 // argument (the pack is empty) and not one statement more than before.
-struct PolicyParamMap {
+// Per-time-step parameters per trajectory (ilqg_batch_set_param_steps_batch) ride in the same map: for the s-th parameter of
+// size -1 in paramdesc[] order, rows[s] = its table [B][n_hor + 1], trajectory-major, or null while that parameter is the
+// shared window.  The member exists only in libraries whose problem has such a parameter (N_STEP_PARAMS, from ILQG_PSIZES):
+// everywhere else the map, and with it every kernel that takes one, is what it was.
+constexpr int n_step_params() {
+    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+    int n = 0;
+    for(int i = 0; i < ILQG_NP; i++) n += sizes[i] == -1 ? 1 : 0;
+    return n;
+}
+constexpr int N_STEP_PARAMS = n_step_params();
+template <int n>
+struct StepRows {
+    const double *rows[n] = {};
+};
+template <>
+struct StepRows<0> {};
+struct PolicyParamMap : StepRows<N_STEP_PARAMS> {
     short src[ILQG_PTOTAL];
     int W;
 };
@@ -117,12 +134,30 @@ __device__ __forceinline__ void override_params(ParamValues &V, ParamTable &T, c
 // of the table — b = the trajectory the lane works for, whatever its lane index means — ONCE per launch, never inside a step
 // loop: from there on the values are the lane's registers, where the shared ones are the wavefront's.  This is the one place
 // that states it, for k_rollout, k_derivs, k_backward, k_search, k_multipliers, k_policy and k_plant (and, with the plant's
-// table, for plant_params).  ORDER: the trajectory's row first, then the roll-out's or the plant's row — whatever the pack
+// table, for plant_params).  The same statement points the lane at its rows of the per-time-step parameters
+// (trajectory_step_params); with step rows only, the table's map is empty (every src -1, W = 0) and `values` is not read.  ORDER: the trajectory's row first, then the roll-out's or the plant's row — whatever the pack
 // holds behind the first two: a slot named in both gets the latter.
+// The trajectory's windows of the per-time-step parameters.  load_params left T.ptr[i] = the shared array, which the
+// generated callbacks index as p[i][k], k = 0 .. n_hor: that indexing is fixed, so a window per trajectory is a POINTER PER
+// LANE, row b of the table (two vector registers per such parameter, and a vector load per use where the shared window takes
+// a scalar one; eight consecutive steps of a lane share a 64-byte line).  A null table (a scalar test: the map is a kernel
+// argument) leaves the shared window.  Index arithmetic over B (n_hor + 1) in size_t.
+template <class Map>
+__device__ __forceinline__ void trajectory_step_params(ParamTable &T, const DevPtrs &P, int b, const Map &map) {
+    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+    int s = 0;
+#pragma unroll
+    for(int i = 0; i < ILQG_NP; i++)
+        if(sizes[i] == -1) {
+            if(map.rows[s]) T.ptr[i] = const_cast<double *>(map.rows[s]) + (size_t)b * (size_t)(P.N + 1);
+            s++;
+        }
+}
 template <class... Behind>
 __device__ __forceinline__ void trajectory_params(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *__restrict__ values,
                                                   const PolicyParamMap &map, const Behind &...) {
     override_params(V, T, P, (size_t)b, 0, values, 0, map);
+    if constexpr(N_STEP_PARAMS > 0) trajectory_step_params(T, P, b, map);
 }
 // the roll-out's own row (k_policy: values, shared, map) behind the trajectory's
 __device__ __forceinline__ void rollout_params_behind(ParamValues &V, ParamTable &T, const DevPtrs &P, size_t g, int r, const double *, const PolicyParamMap &,

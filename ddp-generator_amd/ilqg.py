@@ -272,6 +272,34 @@ def _params_batch_tensors(problem, params, B, device):
     return cols
 
 
+def _param_steps_name(problem, who, name):
+    """the name of a per-time-step parameter for set_param_steps_batch / shift_param_batch; refused here as the library refuses it"""
+    known = dict(problem.params)
+    if name not in known:
+        raise IlqgError("%s: name: Parameter name '%s' is not member of parameters struct." % (who, name))
+    if known[name] != -1:
+        raise IlqgError("%s: name: '%s' has a fixed size of %d, not one value per time step: fixed-size parameters per trajectory "
+                        "are set by set_params_batch" % (who, name, known[name]))
+    return name.encode()
+
+
+def _param_steps_rows(who, what, a, shape, device, gpu):
+    """the rows [B, n_hor+1] (or a tail [B, steps]) of a per-time-step parameter as the library reads them: (address, keep).
+    Host arrays are copied as C-contiguous doubles whatever their dtype and strides; with device=True a contiguous float64
+    torch tensor on the solver's GPU is read where it is."""
+    if not device:
+        if _is_cuda(a):
+            raise IlqgError("%s: %s is a tensor on the device: pass device=True" % (who, what))
+        a = np.asarray(a, dtype=np.float64)
+        if tuple(a.shape) != tuple(shape):
+            raise IlqgError("%s: %s has shape %s, expected %s" % (who, what, tuple(a.shape), tuple(shape)))
+        a = np.ascontiguousarray(a)
+        return _address(a), a
+    if not _is_cuda(a):
+        raise IlqgError("%s: %s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % (who, what))
+    return _cuda_address(a, shape, gpu, "%s: %s" % (who, what)), a
+
+
 def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant, params, disturbance):
     """BatchSolver.receding_plant / MultiSolver.receding_plant: the checks, the arrays and the one library call"""
     B, nx, nu = solver.B, solver.problem.nx, solver.problem.nu
@@ -389,6 +417,14 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_set_params_batch_device.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v, v]
         lib.ilqg_batch_get_params_batch.argtypes = [v, C.c_char_p, v]
         lib.ilqg_multi_set_params_batch.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v]
+    if hasattr(lib, "ilqg_batch_set_param_steps_batch"):  # (and for per-time-step parameters per trajectory)
+        lib.ilqg_batch_set_param_steps_batch.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_batch_set_param_steps_batch_device.argtypes = [v, C.c_char_p, v, v]
+        lib.ilqg_batch_get_param_steps_batch.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_batch_shift_param_batch.argtypes = [v, C.c_char_p, C.c_int, v]
+        lib.ilqg_batch_shift_param_batch_device.argtypes = [v, C.c_char_p, C.c_int, v, v]
+        lib.ilqg_multi_set_param_steps_batch.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_multi_shift_param_batch.argtypes = [v, C.c_char_p, C.c_int, v]
     if hasattr(lib, "ilqg_batch_receding_plant"):  # (and for the closed loop of planner and plant)
         lib.ilqg_batch_receding_plant.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, v, v, v, v, v, v]
         lib.ilqg_multi_receding_plant.argtypes = lib.ilqg_batch_receding_plant.argtypes
@@ -539,6 +575,54 @@ class BatchSolver:
         out = np.zeros((self.B, max(size, 1)))
         self._ck(_receding_entry(self.lib, "ilqg_batch_get_params_batch")(self.h, name.encode(), _address(out)))
         return out
+
+    def set_param_steps_batch(self, name, values, device=False):
+        """ONE per-time-step parameter PER TRAJECTORY (ilqg_batch_set_param_steps_batch): values [B, n_hor+1] — a reference
+        track per agent.  From the next launch on trajectory b reads p[name][k] from values[b], running steps and the final
+        step, in every stage set_params_batch covers and in policy_rollout.  Per name: None makes the name shared again,
+        with the window set_param last gave it.  Independent of set_params_batch.  Nothing is recomputed.  set_param and
+        shift_param of a name that has rows are refused (use this and shift_param_batch); lane-mapped libraries only.  With
+        device=True a contiguous float64 torch tensor on the solver's GPU, copied by the library in the order of torch's
+        current stream without a host wait (ilqg_batch_set_param_steps_batch_device)."""
+        who = "set_param_steps_batch"
+        cname = _param_steps_name(self.problem, who, name)
+        if values is None:
+            self._ck(_receding_entry(self.lib, "ilqg_batch_set_param_steps_batch")(self.h, cname, None))
+            return
+        ptr, keep = _param_steps_rows(who, "values", values, (self.B, self.N + 1), device, self.device)
+        if not device:
+            self._ck(_receding_entry(self.lib, "ilqg_batch_set_param_steps_batch")(self.h, cname, ptr))
+            return
+        entry = _receding_entry(self.lib, "ilqg_batch_set_param_steps_batch_device")
+        torch = _torch_on_gpu()
+        self._ck(entry(self.h, cname, ptr, C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream or None)))
+
+    def param_steps_batch(self, name):
+        """[B, n_hor+1]: what trajectory b sees of per-time-step parameter `name` (ilqg_batch_get_param_steps_batch) — its
+        row of set_param_steps_batch, or the shared window repeated"""
+        cname = _param_steps_name(self.problem, "param_steps_batch", name)
+        out = np.zeros((self.B, self.N + 1))
+        self._ck(_receding_entry(self.lib, "ilqg_batch_get_param_steps_batch")(self.h, cname, _address(out)))
+        return out
+
+    def shift_param_batch(self, name, steps, tail=None, device=False):
+        """the windows of set_param_steps_batch move `steps` values on, each row in place on the device
+        (ilqg_batch_shift_param_batch): p'[b][k] = p[b][k+steps], the last `steps` values from tail [B, steps], or each row's
+        last value held; bit for bit what set_param_steps_batch(name, [rows[:, steps:], tail]) gives.  With device=True tail
+        is a contiguous float64 torch tensor on the solver's GPU (ilqg_batch_shift_param_batch_device, torch's current
+        stream, no host wait)."""
+        who = "shift_param_batch"
+        cname = _param_steps_name(self.problem, who, name)
+        if tail is None:
+            self._ck(_receding_entry(self.lib, "ilqg_batch_shift_param_batch")(self.h, cname, int(steps), None))
+            return
+        ptr, keep = _param_steps_rows(who, "tail", tail, (self.B, max(int(steps), 0)), device, self.device)
+        if not device:
+            self._ck(_receding_entry(self.lib, "ilqg_batch_shift_param_batch")(self.h, cname, int(steps), ptr))
+            return
+        entry = _receding_entry(self.lib, "ilqg_batch_shift_param_batch_device")
+        torch = _torch_on_gpu()
+        self._ck(entry(self.h, cname, int(steps), ptr, C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream or None)))
 
     def init(self, x0, u0):
         """x0 [B,nx], u0 [B,N,nu]: initial roll-out (clamps u) and solver entry state"""
@@ -926,6 +1010,21 @@ class MultiSolver:
             return
         names, values = _params_batch_rows(self.problem, params, self.B)
         self._ck(entry(self.h, len(names), names, _address(values)))
+
+    def set_param_steps_batch(self, name, values):
+        """BatchSolver.set_param_steps_batch on every shard, each with the rows of its trajectories
+        (ilqg_multi_set_param_steps_batch), numpy arrays; None makes the name shared again"""
+        who = "set_param_steps_batch"
+        cname = _param_steps_name(self.problem, who, name)
+        ptr, keep = (None, None) if values is None else _param_steps_rows(who, "values", values, (self.B, self.N + 1), False, None)
+        self._ck(_receding_entry(self.lib, "ilqg_multi_set_param_steps_batch")(self.h, cname, ptr))
+
+    def shift_param_batch(self, name, steps, tail=None):
+        """BatchSolver.shift_param_batch on every shard, each with the tails of its trajectories (ilqg_multi_shift_param_batch)"""
+        who = "shift_param_batch"
+        cname = _param_steps_name(self.problem, who, name)
+        ptr, keep = (None, None) if tail is None else _param_steps_rows(who, "tail", tail, (self.B, max(int(steps), 0)), False, None)
+        self._ck(_receding_entry(self.lib, "ilqg_multi_shift_param_batch")(self.h, cname, int(steps), ptr))
 
     def shift(self, steps, x0=None, u_tail=None):
         """BatchSolver.shift on every shard (ilqg_multi_shift)"""

@@ -99,7 +99,8 @@ int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value,
  * parameters with the NAMED ones replaced by row b of values — in every stage: the initial roll-out of ilqg_batch_init and
  * ilqg_batch_shift, calc_derivs, back_pass in all three modes, line_search, the multiplier update and the cost re-sweep,
  * iterate, solve, receding.  Like ilqg_batch_set_param the call recomputes nothing: costs and records of the current
- * trajectories stay as they are until ilqg_batch_init or ilqg_batch_shift.  PER-TIME-STEP PARAMETERS (size -1) STAY SHARED.
+ * trajectories stay as they are until ilqg_batch_init or ilqg_batch_shift.  PER-TIME-STEP PARAMETERS (size -1) STAY SHARED
+ * HERE; they have an entry of their own, ilqg_batch_set_param_steps_batch (below).
  *
  * names, W and the row layout are those of ilqg_batch_policy_rollout_params with n_starts = 1 and shared = 0: n_names host
  * strings, each a fixed-size parameter of paramdesc[], in any order, none twice; W = the sum of their sizes; values [B][W],
@@ -133,8 +134,8 @@ int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value,
  * device; ilqg_batch_set_param of a name that currently is per-trajectory (the text points at
  * ilqg_batch_set_params_batch(c, 0, NULL, NULL)); and every library of the WAVE MAPPING (one wavefront per trajectory: the
  * *_wave libraries and the problems with N_X = 10 or 16 — the text names the mapping): those kernels do not carry parameters
- * per lane.  Not supported, beside the wave, row and quad mappings: per-trajectory values of per-time-step parameters, a
- * table per start in ilqg_batch_solve_stream, the drop-in iLQG(). */
+ * per lane.  Not supported, beside the wave, row and quad mappings: a table per start in ilqg_batch_solve_stream, the
+ * drop-in iLQG().  (Per-trajectory values of per-time-step parameters: ilqg_batch_set_param_steps_batch, below.) */
 int ilqg_batch_set_params_batch(ilqg_batch_t *c, int n_names, const char *const *names, const double *values /* [B][W] host */);
 int ilqg_batch_set_params_batch_device(ilqg_batch_t *c, int n_names, const char *const *names, const double *values /* [B][W] device */, void *stream);
 int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out /* [B][size] host */);
@@ -296,6 +297,41 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
  * (Wave-mapped problems: written as the full re-send implies, but no such problem with a per-time-step parameter is
  * built in this tree, so that path is untested.) */
 int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const double *tail /* [steps] or NULL */);
+/* PER-TIME-STEP PARAMETERS PER TRAJECTORY: a reference track or speed profile per agent, a moving obstacle bound per vehicle,
+ * a forecast per unit.  ilqg_batch_set_param_steps_batch(c, name, values): name is ONE parameter of size -1, values
+ * [B][n_hor + 1] trajectory-major.  From the next launch on every generated callback evaluated for trajectory b reads
+ * p[name][k] from row b, for the running steps and the final step k = n_hor, in every stage ilqg_batch_set_params_batch
+ * covers (the initial roll-out of init and shift, calc_derivs, back_pass in all three modes, line_search, the multiplier
+ * update and the cost re-sweep, iterate, solve) and in ilqg_batch_policy_rollout*: where that entry says "the per-time-step
+ * parameters as they stand", read "trajectory b's".  Like ilqg_batch_set_param the call recomputes nothing.  It works PER
+ * NAME: values = NULL makes that name shared again, with the window ilqg_batch_set_param last gave it; other names keep what
+ * they have.  The fixed-size set of ilqg_batch_set_params_batch is independent: setting or clearing one leaves the other
+ * alone.  With no per-trajectory name left and no fixed-size table the batch runs the very kernels of a batch that never had
+ * one.  The library copies the rows into a buffer of its own per name, which only grows.  The _device forms take DEVICE
+ * memory under the stream contract of ilqg_batch_head_device (event in, one event per group out, no host wait, no
+ * allocation in steady state).
+ * ilqg_batch_get_param_steps_batch: out [B][n_hor + 1], what trajectory b sees: its row, or the shared window repeated.
+ * ilqg_batch_shift_param_batch: per row what ilqg_batch_shift_param does, p'[b][k] = p[b][k + steps], the last `steps` values
+ * from tail [B][steps], or p[b][n_hor] held if tail is NULL; 0 <= steps <= n_hor, steps = 0 is a no-op.  The rows move in
+ * place on the device; the result is bit for bit what re-sending [rows[:, steps:], tail] through the setter gives.
+ * Option "compact": the rows travel with their trajectories, a compacted solve stays bit for bit the plain one.
+ *
+ * REFUSED, with the argument named in the error text and before anything is launched, allocated or changed: a name that is
+ * no parameter ("Parameter name '%s' is not member of parameters struct."), a fixed-size name (the text points at
+ * ilqg_batch_set_params_batch), out NULL (c NULL returns 1), steps out of range, ilqg_batch_shift_param_batch of a name
+ * that is currently shared, in the device forms memory that is not device memory of the context's device;
+ * ilqg_batch_set_param and ilqg_batch_shift_param of a name that currently is per-trajectory (the text points at the _batch
+ * forms and at values = NULL); ilqg_batch_solve_stream while any name has rows; every library of the WAVE MAPPING (the text
+ * names the mapping).  A per-time-step name given to ilqg_batch_set_params_batch, _policy_rollout_params or _receding_plant
+ * stays refused, and ilqg_batch_receding / _receding_plant still refuse a problem that has a per-time-step parameter.
+ * Not supported: the wave, row and quad mappings; the drop-in iLQG(); rows per start in ilqg_batch_solve_stream; the
+ * resident closed loops receding / receding_plant for problems with per-time-step parameters (moving windows inside those
+ * loops). */
+int ilqg_batch_set_param_steps_batch(ilqg_batch_t *c, const char *name, const double *values /* [B][n_hor+1] host, or NULL */);
+int ilqg_batch_set_param_steps_batch_device(ilqg_batch_t *c, const char *name, const double *values /* device, or NULL */, void *stream);
+int ilqg_batch_get_param_steps_batch(ilqg_batch_t *c, const char *name, double *out /* [B][n_hor+1] host */);
+int ilqg_batch_shift_param_batch(ilqg_batch_t *c, const char *name, int steps, const double *tail /* [B][steps] host, or NULL */);
+int ilqg_batch_shift_param_batch_device(ilqg_batch_t *c, const char *name, int steps, const double *tail /* device or NULL */, void *stream);
 
 /* n lock-step iterations of { calc_derivs, back_pass (+ lambda retries),
  * line_search over all alpha, accept/reject } for every still-active trajectory */
@@ -383,6 +419,8 @@ ilqg_batch_t *ilqg_multi_shard(ilqg_multi_t *m, int g, int *first, int *count);
 int ilqg_multi_set_option(ilqg_multi_t *m, const char *name, const double *value, int n);
 int ilqg_multi_set_param(ilqg_multi_t *m, const char *name, const double *value, int n);
 int ilqg_multi_set_params_batch(ilqg_multi_t *m, int n_names, const char *const *names, const double *values);  /* [batch][W], sharded by rows */
+int ilqg_multi_set_param_steps_batch(ilqg_multi_t *m, const char *name, const double *values);  /* [batch][n_hor+1], sharded by rows */
+int ilqg_multi_shift_param_batch(ilqg_multi_t *m, const char *name, int steps, const double *tail);  /* [batch][steps] or NULL */
 int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0);
 int ilqg_multi_set_u(ilqg_multi_t *m, const double *u);
 int ilqg_multi_init(ilqg_multi_t *m);
