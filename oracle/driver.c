@@ -221,6 +221,15 @@ void drv_get_traj(drv_t *d, int which, double *x, double *u) {
     for(i = 0; i < N_X; i++) x[d->n_hor * N_X + i] = tr->f.x[i];
 }
 
+/* the cost of every step as forward_pass left it (iLQG_func.tem:175-176): c[k] = t[k].c for k < n_hor, c[n_hor] = f.c;
+ * their sum in this order from 0.0 is the total forward_pass returns.  which as in drv_get_traj */
+void drv_get_step_costs(drv_t *d, int which, double *c) {
+    int k;
+    traj_t *tr = which ? d->o.candidates[0] : d->o.nominal;
+    for(k = 0; k < d->n_hor; k++) c[k] = tr->t[k].c;
+    c[d->n_hor] = tr->f.c;
+}
+
 /* l is [n_hor][N_U], L is [n_hor][N_U*N_X] (column-major m x n per step) */
 void drv_get_gains(drv_t *d, double *l, double *L) {
     int k;

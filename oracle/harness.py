@@ -185,6 +185,8 @@ def _bind(lib):
     if hasattr(lib, "drv_set_state"):
         lib.drv_set_state.argtypes = [C.c_void_p, _dp, _dp, _dp]
         lib.drv_set_multipliers.argtypes = [C.c_void_p, _dp, _dp]
+    if hasattr(lib, "drv_get_step_costs"):
+        lib.drv_get_step_costs.argtypes = [C.c_void_p, C.c_int, _dp]
     if hasattr(lib, "drv_solve_many"):
         lib.drv_solve_many.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _ip, _ip]
     return lib
@@ -279,6 +281,13 @@ class Driver:
         u = np.zeros((self.N, self.nu))
         self.lib.drv_get_traj(self.h, which, x, u)
         return x, u
+
+    def step_costs(self, which=0):
+        """[N + 1]: the running cost of every step as forward_pass left it, then the final cost; summed in this order
+        from 0.0 they are the total forward_pass returns"""
+        c = np.zeros(self.N + 1)
+        self.lib.drv_get_step_costs(self.h, which, c)
+        return c
 
     def gains(self):
         l = np.zeros((self.N, self.nu))

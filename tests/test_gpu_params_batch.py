@@ -10,10 +10,11 @@ import pytest
 
 from oracle.harness import HX_N, HX_PARAMS, hx_inputs, lib_path
 from params_batch_cases import BUILDS, SLOTS, B, FdCase, dict_of, oracle_stages, rows
+from plant_cases import BOTH, noise, plant_over_rows, plant_starts
 from policy_cases import perturbed_starts, reference_rollout
 from policy_param_cases import NAMED, PER_STEP, draws, params_of
 from test_gpu_policy_rollout import close, ilqg, outputs_equal, torch, worst  # noqa: F401 (fixtures)
-from test_gpu_receding_plant import full_state
+from test_gpu_receding_plant import composition, full_state, hold_rounds
 
 pytestmark = pytest.mark.gpu
 
@@ -320,6 +321,48 @@ def test_the_plant_without_names_is_the_trajectorys_model(ilqg):
     assert np.all(log["ok"] == 1) and np.all(roll["ok"] == 1)
     assert np.array_equal(log["x"], roll["x"][:, 0, :steps]) and np.array_equal(log["u"], roll["u"][:, 0, :steps])
     states_equal(full_state(loop), full_state(comp), "the loop against its composition")
+    c.close()
+
+
+@pytest.mark.parametrize("name,fd", [("carparking", 0), ("hxtest", 1)])
+def test_the_plant_with_names_runs_over_the_trajectorys_row(ilqg, name, fd):
+    """per-trajectory rows AND a plant with named parameters (k_plant<true> with both tables): one round of three steps behind
+    four iterations, feedback, a disturbance behind every step.  The plant names one parameter the trajectories' rows name too
+    and one they do not (tests/plant_cases.py); slot b's plant runs under the batch's parameters with the trajectory's row
+    first and the plant's row on top.  x, u, the applied cost and x_plant against policy_cases.reference_plant under that
+    dict (tests/test_plant_reference_recipe.py: the other order misses the bar by 1e4 times or more)."""
+    steps, iters = 3, 4
+    c = FdCase(ilqg, name, fd, count=2)
+    loop, twin = c.solvers
+    table, mine, plant_table, plant_rows = plant_over_rows(name, c.params, loop.problem.params)
+    assert BOTH[name] in mine and BOTH[name] in plant_rows and sum(n not in mine for n in plant_rows) == 1
+    for q in (loop, twin):
+        q.set_params_batch(mine)
+        q.init(c.x0, c.u0)
+    X, w = plant_starts(c), noise(c, steps, rounds=1)
+    out = loop.receding_plant(1, steps, iters, True, X, plant_rows, w)
+    what = "%s fd%d, plant rows over trajectory rows" % (name, fd)
+    dev = hold_rounds(c, out, twin, lambda b: params_of(dict_of(c.params, table, b), plant_table, b, 1), X, w, 1, steps, 1, what, iterations=iters)
+    print(what + ": worst deviation from the reference's plant " + ", ".join("%s %.3g" % kv for kv in dev.items()))
+    c.close()
+
+
+def test_the_plant_with_names_over_rows_equals_its_composition(ilqg):
+    """the same call in the FMA-free CarParking build, the disturbance behind the last step only, against iterate +
+    policy_rollout(params = the plants' rows) on the same per-trajectory batch + shift: logs, x_plant and the batch, bit for bit"""
+    steps, iters = 3, 4
+    c = FdCase(ilqg, "carparking", 0, True, count=2)
+    loop, comp = c.solvers
+    table, mine, plant_table, plant_rows = plant_over_rows("carparking", c.params, loop.problem.params)
+    for q in (loop, comp):
+        q.set_params_batch(mine)
+        q.init(c.x0, c.u0)
+    X, w = plant_starts(c), noise(c, steps, rounds=1, last_only=True)
+    out = loop.receding_plant(1, steps, iters, True, X, plant_rows, w)
+    assert np.all(out["ok"] == 1)
+    want = composition(comp, plant_rows, X, w, 1, steps, iterations=iters)
+    outputs_equal(out, want, "plant rows over trajectory rows: one call against the composition, FMA-free build", sorted(want))
+    states_equal(full_state(loop), full_state(comp), "plant rows over trajectory rows: the loop against its composition")
     c.close()
 
 

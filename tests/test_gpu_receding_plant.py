@@ -4,26 +4,30 @@ Per round: iterate(2); every trajectory's plant advances `steps` steps from its 
 (u = u_nom_k [+ L_k (x_plant - x_nom_k)]), each step the reference's forward_pass step (iLQG_func.tem:121-185) under the
 PLANT's parameters, the disturbance added behind it; then shift(steps, x0 = the plants' states).
 
-Test 1 holds one round against the reference's own forward_pass through the CPU oracle's driver under each compared
-trajectory's parameter dict (tests/policy_cases.py, tests/policy_param_cases.py) with the tree's single-pass bar,
-|d| <= 1e-10 max(1, |ref|).  Tests 2 and 4 hold the loop against compositions of entries that existed before (bit for bit in
-the FMA-free builds), test 3 holds identities within the new code bit for bit, tests 5 and 6 failures and refusals.
-Builds, inputs, B = 70 (one full and one partly filled wavefront), SLOTS and Case are those of
+Tests 1, 7, 8 and 9 hold the logs against the reference's own forward_pass through the CPU oracle's driver under each compared
+trajectory's parameter dict (tests/policy_cases.py, tests/policy_param_cases.py, tests/plant_cases.py) with the tree's
+single-pass bar, |d| <= 1e-10 max(1, |ref|).  Tests 2 and 4 hold the loop against compositions of entries that existed before
+(bit for bit in the FMA-free builds), test 3 holds identities within the new code bit for bit, tests 5 and 6 failures and
+refusals.  Builds, inputs, B = 70 (one full and one partly filled wavefront), SLOTS and Case are those of
 tests/test_gpu_policy_rollout.py; rounds = 3 and iterations = 2 unless a test says otherwise.
 
-THE SUM OF THE APPLIED RUNNING COSTS (`cost`) HAS NO REFERENCE VALUE HERE.  The oracle's driver returns forward_pass's total
-alone (all N running costs plus the final cost), and so does the public policy_rollout, whose roll-outs moreover all begin
-at time index 0: no difference of such totals isolates the running costs of the first `steps` steps.  `cost` is therefore
-held by identities only: equal bits for one call of three rounds and three calls of one (test 3), for groups, shards, name
-orders and an extra nominal parameter (test 3), and for every trajectory beside a failed one (test 5)."""
+The sum of the applied running costs (`cost`) is held against the reference too: forward_pass leaves every step's cost in the
+candidate trajectory, and the oracle's driver returns them (Driver.step_costs).  Test 1 compares `cost` with the sum of the
+first `steps` of them, in step order from 0.0 under the plant's parameters; tests 7 to 9 with policy_cases.reference_plant, the
+chain of one-step roll-outs that also takes a disturbance inside a round (the read of the table at the steps before the last
+one, x_next + w, and the feedback of the next step from the disturbed state) and, teacher-forced on the device's own plant
+states, the later rounds.  tests/test_plant_reference_recipe.py pins that chain to the reference build without a GPU and shows
+that the cost under the model's parameters, a dropped inner disturbance and the wrong order of two overrides each miss the bar
+by 1e4 times or more.  The identities of tests 3 and 5 hold `cost` as before."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from oracle.harness import lib_path
-from policy_cases import perturbed_starts, reference_rollout
-from policy_param_cases import NAMED, PER_STEP, SCALE, draws, limits_ordered, nominal_table, params_of
+from plant_cases import SHORT_N, SHORT_SEED, noise, plant_rows, plant_starts, short_car  # noqa: F401
+from policy_cases import reference_plant, reference_rollout
+from policy_param_cases import NAMED, PER_STEP, SCALE, draws, nominal_table, params_of
 from test_gpu_policy_rollout import B, SLOTS, Case, assert_state_equal, close, ilqg, outputs_equal, state, worst  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -40,25 +44,75 @@ def full_state(s):
     return out
 
 
-def plant_rows(c, names=None, batch=B, seed=None):
-    """(table [batch, 2, size] per name, rows [batch, size] per name): 5 % draws; row 1 of a draw, row 0 being the nominal values"""
-    kw = {} if seed is None else dict(seed=seed)
-    t = draws(c.params, names or NAMED[c.name], batch, 2, scale=SCALE[c.name], **kw)
-    assert limits_ordered(t)
-    return t, {n: np.ascontiguousarray(a[:, 1]) for n, a in t.items()}
+def plan_of(b):
+    """slot -> (policy, what reference_rollout / reference_plant take beside it) of the batch's current plans: heads with
+    gains, costs, and the multipliers and penalty weights of a problem that has them"""
+    h = b.head(b.N, gains=True)
+    cost = b.scalar("cost")
+    mul = sum(b.multiplier_dims()) > 0
+    w_l, w_f = (b.scalar("w_pen_l"), b.scalar("w_pen_f")) if mul else (np.zeros(b.B), np.zeros(b.B))
+    m_run, m_fin = b.multipliers() if mul else (None, None)
+    return lambda s: ((h["x"][s], h["u"][s], h["l"][s], h["L"][s]),
+                      dict(cost=cost[s], w_pen=(w_l[s], w_f[s]), multipliers=(m_run[s], m_fin[s]) if mul else None))
 
 
-def plant_starts(c, seed=17):
-    return np.ascontiguousarray(perturbed_starts(c.x0, 2, seed=seed)[:, 1])
+def hold_rounds(c, out, twin, plant, X, w, rounds, steps, feedback, what, iterations=ITERATIONS):
+    """the logs `out` of receding_plant(rounds, steps, iterations, feedback, X, ..., w) against policy_cases.reference_plant,
+    round by round, teacher-forced on the device's own plant states: the twin batch (the loop's inputs) runs iterate, its
+    plans' policies are read, the reference's plant goes from X_r = out["x"][:, r * steps] (round 0: the given X) under
+    plant(s), slot s's parameter dict, and that round's slice of w, and the twin is shifted to X_{r+1} (behind the last round
+    out["x_plant"]).  plan_cost: the twin's, bit for bit (the same kernels on the same bits).  x, u, cost[:, r] and
+    X_{r+1} against the reference's at the single-pass bar.  Returns the worst deviations."""
+    lib = lib_path("oracle", c.problem, c.fd)
+    dev = dict(x=0.0, u=0.0, cost=0.0, x_plant=0.0)
+    assert np.all(out["ok"] == 1), what
+    Xr = X
+    for r in range(rounds):
+        twin.iterate(iterations)
+        plan = plan_of(twin)
+        assert np.array_equal(out["plan_cost"][:, r], twin.scalar("cost")), "%s round %d: the plans' costs are not the twin's" % (what, r)
+        lo, hi = r * steps, (r + 1) * steps
+        nxt = out["x"][:, hi] if r + 1 < rounds else out["x_plant"]
+        for s in SLOTS:
+            policy, kw = plan(s)
+            x, u, _, cost, x_end = reference_plant(lib, c.N, plant(s), c.opts, Xr[s], policy, feedback, steps, w=w[s, lo:hi], **kw)
+            assert all(np.all(np.isfinite(v)) for v in (x, u, cost, x_end)), "%s round %d slot %d: the reference is not finite (a compared slot may not be left out)" % (what, r, s)
+            got = dict(x=out["x"][s, lo:hi], u=out["u"][s, lo:hi], cost=out["cost"][s, r], x_plant=nxt[s])
+            want = dict(x=x, u=u, cost=cost, x_plant=x_end)
+            for k in got:
+                dev[k] = max(dev[k], worst(got[k], want[k]))
+            for k in got:
+                assert close(got[k], want[k]), "%s round %d slot %d: %s off by %.3g" % (what, r, s, k, worst(got[k], want[k]))
+        twin.shift(steps, x0=np.ascontiguousarray(nxt))
+        Xr = nxt
+    return dev
 
 
-def noise(c, steps, rounds=ROUNDS, last_only=False, batch=B, seed=3, sigma=0.01):
-    w = sigma * np.random.default_rng(seed).standard_normal((batch, rounds * steps, c.nx))
-    if last_only:
-        keep = np.zeros(rounds * steps, dtype=bool)
-        keep[steps - 1::steps] = True
-        w[:, ~keep] = 0.0
-    return w
+def composition(b, rows, X, w, rounds, steps, iterations=ITERATIONS):
+    """rounds x { iterate; policy_rollout(x_plant[:, None], alpha = 0, feedback, trajectories, params = rows[:, None]); x, u of
+    the first `steps` steps; x_plant = x[steps] + w of the round's LAST step (policy_rollout has no disturbance inside a
+    roll-out); shift(steps, x0 = x_plant) } on batch b: what the loop's x, u, plan_cost and x_plant are compared with"""
+    xp, xs, us, pc = X.copy(), [], [], []
+    for r in range(rounds):
+        b.iterate(iterations)
+        pc.append(b.scalar("cost"))
+        o = b.policy_rollout(xp[:, None], alpha=0.0, feedback=True, trajectories=True, params={n: t[:, None] for n, t in rows.items()})
+        assert np.all(o["ok"] == 1)
+        xs.append(o["x"][:, 0, 0:steps]), us.append(o["u"][:, 0, 0:steps])
+        xp = o["x"][:, 0, steps] + w[:, r * steps + steps - 1]
+        b.shift(steps, x0=xp)
+    return dict(x=np.concatenate(xs, axis=1), u=np.concatenate(us, axis=1), plan_cost=np.stack(pc, axis=1), x_plant=xp)
+
+
+class ShortCase(Case):
+    """Case for CarParking with the horizon of SHORT_N steps (tests/plant_cases.py short_car)"""
+
+    def __init__(self, ilqg, count=1, strict=False):
+        self.name, self.problem, self.fd, self.opts, self.plant_seed = "carparking", "carparking", 0, {}, SHORT_SEED
+        self.N, self.params, self.x0, self.u0 = short_car()
+        self.solvers = [ilqg.BatchSolver("carparking", 0, batch=B, n_hor=self.N, params=self.params, opts=dict(max_iter=40), strict=strict, groups=0)
+                        for _ in range(count)]
+        self.nx, self.nu = self.solvers[0].problem.nx, self.solvers[0].problem.nu
 
 
 # ---------------------------------------------------------------------------
@@ -70,7 +124,9 @@ def test_one_round_equals_the_references_forward_pass_under_the_plants_parameter
     """rounds = 1, steps = 3, a disturbance on the last step only.  The policy, multipliers and penalty weights are read from
     a twin batch advanced by iterate(2) alone (identical inputs; lock-step iterations are deterministic).  strict=True: the
     FMA-free n = 16 build, which reads the plant's parameters from memory.  almix has a per-time-step parameter: the loop
-    refuses it, which is what is asserted for it here.  The applied costs are not compared (module docstring)."""
+    refuses it, which is what is asserted for it here.  The applied cost is compared with the sum of the first three step
+    costs of the same forward_pass, in step order from 0.0 (the disturbance sits behind the last step: no step's cost reads
+    it)."""
     steps = 3
     c = Case(ilqg, name, 0, count=2, strict=strict)
     a, b = c.history("init")
@@ -93,15 +149,18 @@ def test_one_round_equals_the_references_forward_pass_under_the_plants_parameter
     assert np.array_equal(out["plan_cost"][:, 0], cost)
     assert np.all(out["ok"] == 1)
     oracle = lib_path("oracle", c.problem, c.fd)
-    dev = dict(x=0.0, u=0.0, x_plant=0.0)
+    dev = dict(x=0.0, u=0.0, x_plant=0.0, cost=0.0)
     for s in SLOTS:
         policy = (h["x"][s], h["u"][s], h["l"][s], h["L"][s])
-        ok, _, xr, ur = reference_rollout(oracle, c.N, params_of(c.params, table, s, 1), c.opts, X[s], policy, 0.0, feedback, cost=cost[s],
-                                          w_pen=(w_l[s], w_f[s]), multipliers=(m_run[s], m_fin[s]) if mul else None)
+        ok, _, xr, ur, sc = reference_rollout(oracle, c.N, params_of(c.params, table, s, 1), c.opts, X[s], policy, 0.0, feedback, cost=cost[s],
+                                              w_pen=(w_l[s], w_f[s]), multipliers=(m_run[s], m_fin[s]) if mul else None, step_costs=True)
         what = "%s strict=%s feedback=%d slot %d" % (name, strict, feedback, s)
-        assert ok == 1 and np.all(np.isfinite(xr)) and np.all(np.isfinite(ur)), what + ": the oracle's roll-out is not finite (a compared slot may not be left out)"
-        got = dict(x=out["x"][s], u=out["u"][s], x_plant=out["x_plant"][s])
-        want = dict(x=xr[0:steps], u=ur[0:steps], x_plant=xr[steps] + w[s, steps - 1])
+        assert ok == 1 and np.all(np.isfinite(xr)) and np.all(np.isfinite(ur)) and np.all(np.isfinite(sc)), what + ": the oracle's roll-out is not finite (a compared slot may not be left out)"
+        applied = 0.0
+        for k in range(steps):
+            applied += sc[k]
+        got = dict(x=out["x"][s], u=out["u"][s], x_plant=out["x_plant"][s], cost=out["cost"][s, 0])
+        want = dict(x=xr[0:steps], u=ur[0:steps], x_plant=xr[steps] + w[s, steps - 1], cost=applied)
         for k in got:
             dev[k] = max(dev[k], worst(got[k], want[k]))
         for k in got:
@@ -128,15 +187,7 @@ def test_loop_equals_the_public_composition(ilqg, name, strict, steps):
     X, w = plant_starts(c), noise(c, steps, rounds=rounds, last_only=steps > 1)
     out = a.receding_plant(rounds, steps, ITERATIONS, True, X, rows, w)
     assert np.all(out["ok"] == 1)
-    xp, xs, us, pc = X.copy(), [], [], []
-    for r in range(rounds):
-        b.iterate(ITERATIONS)
-        pc.append(b.scalar("cost"))
-        o = b.policy_rollout(xp[:, None], alpha=0.0, feedback=True, trajectories=True, params={n: t[:, None] for n, t in rows.items()})
-        xs.append(o["x"][:, 0, 0:steps]), us.append(o["u"][:, 0, 0:steps])
-        xp = o["x"][:, 0, steps] + w[:, r * steps + steps - 1]
-        b.shift(steps, x0=xp)
-    want = dict(x=np.concatenate(xs, axis=1), u=np.concatenate(us, axis=1), plan_cost=np.stack(pc, axis=1), x_plant=xp)
+    want = composition(b, rows, X, w, rounds, steps)
     print("%s strict=%s steps=%d: worst deviation from the composition " % (name, strict, steps) + ", ".join("%s %.3g" % (k, worst(out[k], v)) for k, v in want.items()))
     if strict:
         outputs_equal(out, want, "one call against the composition, FMA-free build", sorted(want))
@@ -355,4 +406,84 @@ def test_refused_calls_name_the_argument_change_nothing_and_launch_nothing(ilqg)
     for k in ("x", "u", "cost", "plan_cost", "ok"):
         assert np.array_equal(logs[k], model[k]), k
     assert np.array_equal(xp, model["x_plant"])
+    c.close()
+
+
+# ---------------------------------------------------------------------------
+# 7. a disturbance on every step of a round, against the reference's plant
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("feedback", [1, 0])
+@pytest.mark.parametrize("name,strict", [(n, None) for n in ("carparking", "carparking_wave", "hxtest", "synth16x8", "synth10hx")] + [("synth16x8", True)])
+def test_a_dense_disturbance_inside_a_round_equals_the_references_plant(ilqg, name, strict, feedback):
+    """rounds = 1, steps = 4, a disturbance behind EVERY step: the read of the table at the steps before the last one,
+    x_next + w, and the control of step k + 1 from the disturbed state.  x, u, the applied cost and x_plant against
+    policy_cases.reference_plant under the plant's parameters."""
+    steps = 4
+    c = Case(ilqg, name, 0, count=2, strict=strict)
+    a, b = c.history("init")
+    table, rows = plant_rows(c)
+    X, w = plant_starts(c), noise(c, steps, rounds=1)
+    assert np.all(w != 0.0)
+    out = a.receding_plant(1, steps, ITERATIONS, bool(feedback), X, rows, w)
+    what = "%s strict=%s feedback=%d" % (name, strict, feedback)
+    dev = hold_rounds(c, out, b, lambda s: params_of(c.params, table, s, 1), X, w, 1, steps, feedback, what)
+    print(what + ": dense disturbance, worst deviation from the reference's plant " + ", ".join("%s %.3g" % kv for kv in dev.items()))
+    c.close()
+
+
+# ---------------------------------------------------------------------------
+# 8. three rounds, teacher-forced on the device's own plant states
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["carparking", "synth16x8"])
+def test_three_rounds_equal_the_references_plant_round_by_round(ilqg, name):
+    """steps = 2, a disturbance behind every step, feedback: every round's x, u and applied cost, and the state the next
+    round starts from, against the reference's plant from the state the DEVICE's plant had at the round's start about the
+    policy a twin batch has there (hold_rounds); the plans' costs are the twin's bit for bit."""
+    steps = 2
+    c = Case(ilqg, name, 0, count=2)
+    a, b = c.history("init")
+    table, rows = plant_rows(c)
+    X, w = plant_starts(c), noise(c, steps)
+    out = a.receding_plant(ROUNDS, steps, ITERATIONS, True, X, rows, w)
+    dev = hold_rounds(c, out, b, lambda s: params_of(c.params, table, s, 1), X, w, ROUNDS, steps, 1, name)
+    assert_state_equal(full_state(a), full_state(b), "%s: the batch behind the loop against the teacher-forced twin" % name)
+    print("%s: three rounds, worst deviation from the reference's plant " % name + ", ".join("%s %.3g" % kv for kv in dev.items()))
+    c.close()
+
+
+# ---------------------------------------------------------------------------
+# 9. the largest step count the entry accepts
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("steps", [SHORT_N - 1, 1])
+def test_the_largest_step_count_equals_the_references_plant(ilqg, steps):
+    """CarParking with n_hor = 6, steps = n_hor - 1 = 5 (the plant applies every control of the plan but the last; the
+    prefetch of step k + 1's nominal data reaches the plan's last step) and steps = 1 at the same horizon: two rounds, a
+    disturbance behind every step, feedback, round by round against the reference's plant (hold_rounds)."""
+    rounds = 2
+    c = ShortCase(ilqg, count=2)
+    assert c.N == SHORT_N and steps < c.N
+    a, b = c.history("init")
+    table, rows = plant_rows(c)
+    X, w = plant_starts(c), noise(c, steps, rounds=rounds)
+    out = a.receding_plant(rounds, steps, ITERATIONS, True, X, rows, w)
+    what = "carparking n_hor=%d steps=%d" % (c.N, steps)
+    dev = hold_rounds(c, out, b, lambda s: params_of(c.params, table, s, 1), X, w, rounds, steps, 1, what)
+    assert_state_equal(full_state(a), full_state(b), what + ": the batch behind the loop against the teacher-forced twin")
+    print(what + ": worst deviation from the reference's plant " + ", ".join("%s %.3g" % kv for kv in dev.items()))
+    c.close()
+
+
+def test_the_largest_step_count_equals_the_public_composition_bit_for_bit(ilqg):
+    """test 2's composition in the FMA-free CarParking build at n_hor = 6, steps = 5, three rounds, the disturbance on each
+    round's last step only (policy_rollout has none inside a roll-out): logs, x_plant and the batch afterwards bit for bit"""
+    steps = SHORT_N - 1
+    c = ShortCase(ilqg, count=2, strict=True)
+    a, b = c.history("init")
+    _, rows = plant_rows(c)
+    X, w = plant_starts(c), noise(c, steps, last_only=True)
+    out = a.receding_plant(ROUNDS, steps, ITERATIONS, True, X, rows, w)
+    assert np.all(out["ok"] == 1)
+    want = composition(b, rows, X, w, ROUNDS, steps)
+    outputs_equal(out, want, "n_hor = %d, steps = %d: one call against the composition, FMA-free build" % (c.N, steps), sorted(want))
+    assert_state_equal(full_state(a), full_state(b), "n_hor = %d, steps = %d: the batch behind the loop" % (c.N, steps))
     c.close()
