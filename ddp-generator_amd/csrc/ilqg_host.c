@@ -1557,6 +1557,15 @@ int ilqg_boxqp_table_batch(int device, int n, int count, const double *H, const 
     return ilqg_dev_boxqp_table_batch(device, n, count, H, g, lower, upper, x, clamp, n_free, invH, rc);
 }
 
+int ilqg_boxqp_quad_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
+                          const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc, const int *active) {
+    if(ilqg_dev_boxqp_quad_batch(device, n, count, H, g, lower, upper, x, clamp, n_free, invH, rc, active)) {
+        snprintf(g_create_err, sizeof(g_create_err), "ilqg_boxqp_quad_batch: %s", ilqg_dev_error());  /* ilqg_batch_error(NULL) */
+        return 1;
+    }
+    return 0;
+}
+
 int ilqg_sincos_batch(int device, int n, const double *x, double *s, double *c) {
     return ilqg_dev_sincos_batch(device, n, x, s, c);
 }

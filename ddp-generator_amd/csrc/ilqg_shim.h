@@ -308,6 +308,12 @@ int ilqg_dev_boxqp_wave_batch(int device, int n, int count, const double *H, con
 int ilqg_dev_boxqp_table_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
                                const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc);
 
+/* ... and for the quad mapping's form (ilqg_quad.hpp box_qp_quad: four problems per wavefront, one per 16-lane row;
+ * n = 2 or N_U).  active: one int per problem, 0 = the row computes along and commits nothing (x unchanged, rc 0);
+ * NULL = all active.  Libraries of the wave mapping only; elsewhere refused, with a message, before anything is allocated */
+int ilqg_dev_boxqp_quad_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
+                              const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc, const int *active);
+
 /* the reference's small dense helpers on the device (one problem): op 0 addMulVec, 1 addSquareTri, 2 addMul2Tri
  * (shape 0 = (N_X,N_U), 1 = (N_X,N_X), 2 = (N_U,N_X[,1])), 3 cholesky_tri, 4 cholesky_tri_inv (shape = n).
  * flag: 1 ok, 0 Cholesky pivot <= 0, -1 size not built */

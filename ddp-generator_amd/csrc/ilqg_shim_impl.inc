@@ -2433,11 +2433,24 @@ int ilqg_dev_sincos_batch(int device, int n, const double *x, double *s, double 
     return 0;
 }
 
+// rows: 0 box_qp (one problem per lane), 1 the cooperative form of the wave mapping (one per wavefront), 2 box_qp with the
+// pattern tables, 3 box_qp_quad (four per wavefront; `active`: one int per problem, NULL = all active)
 static int boxqp_batch(int rows, int device, int n, int count, const double *H, const double *g, const double *lower,
-                       const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc) {
+                       const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc, const int *active = nullptr) {
     if(n != 2 && n != 8 && n != NU) {
         g_err = "ilqg_dev_boxqp_batch: n must be 2, 8 or N_U";
         return 1;
+    }
+    if(rows == 3) {
+#if ILQG_WAVE_MAP
+        if(n != 2 && n != NU) {
+            g_err = "ilqg_dev_boxqp_quad_batch: n must be 2 or N_U";
+            return 1;
+        }
+#else
+        g_err = "ilqg_dev_boxqp_quad_batch: the quad form is compiled into the libraries of the wave mapping only (N_X > 8, lib*_wave.so)";
+        return 1;
+#endif
     }
     HIP_TRY(hipSetDevice(device));
     const size_t T = n * (n + 1) / 2;
@@ -2457,7 +2470,19 @@ static int boxqp_batch(int rows, int device, int n, int count, const double *H, 
     HIP_TRY(hipMemcpy(dlo, lower, count * n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dup, upper, count * n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dx, x, count * n * 8, hipMemcpyHostToDevice));
-    const dim3 grid = rows == 1 ? dim3(count) : grid1(count, 64), block(64);
+    const dim3 grid = rows == 1 ? dim3(count) : (rows == 3 ? grid1(count, 4) : grid1(count, 64)), block(64);
+    int *dact = nullptr;
+#if ILQG_WAVE_MAP
+    if(rows == 3) {
+        HIP_TRY(hipMalloc((void **)&dact, count * 4));
+        const std::vector<int> every(count, 1);
+        HIP_TRY(hipMemcpy(dact, active ? active : every.data(), count * 4, hipMemcpyHostToDevice));
+        if(n == NU)
+            hipLaunchKernelGGL(k_boxqp_quad_test<NU>, grid, block, 0, 0, count, dact, dH, dg, dlo, dup, dx, dcl, dnf, dinv, drc);
+        else
+            hipLaunchKernelGGL(k_boxqp_quad_test<2>, grid, block, 0, 0, count, dact, dH, dg, dlo, dup, dx, dcl, dnf, dinv, drc);
+    } else
+#endif
 #if ILQG_EXPERIMENTS
     if(rows == 2 && n == 2)
         hipLaunchKernelGGL((k_boxqp_test<2, true>), grid, block, 0, 0, count, dH, dg, dlo, dup, dx, dcl, dnf, dinv, drc);
@@ -2493,7 +2518,7 @@ static int boxqp_batch(int rows, int device, int n, int count, const double *H, 
     HIP_TRY(hipMemcpy(n_free, dnf, count * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rc, drc, count * 4, hipMemcpyDeviceToHost));
     hipFree(dH); hipFree(dinv); hipFree(dg); hipFree(dlo); hipFree(dup); hipFree(dx);
-    hipFree(dcl); hipFree(dnf); hipFree(drc);
+    hipFree(dcl); hipFree(dnf); hipFree(drc); hipFree(dact);
     return 0;
 }
 
@@ -2510,6 +2535,11 @@ int ilqg_dev_boxqp_wave_batch(int device, int n, int count, const double *H, con
 int ilqg_dev_boxqp_table_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
                                const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc) {
     return boxqp_batch(2, device, n, count, H, g, lower, upper, x, clamp, n_free, invH, rc);
+}
+
+int ilqg_dev_boxqp_quad_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
+                              const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc, const int *active) {
+    return boxqp_batch(3, device, n, count, H, g, lower, upper, x, clamp, n_free, invH, rc, active);
 }
 
 // ---------------------------------------------------------------------------

@@ -457,7 +457,9 @@ __global__ __launch_bounds__(64, 1) void k_boxqp_test(int count, const double *H
     for(int i = 0; i < T; i++) invH[(size_t)t * T + i] = inv[i];
 }
 
-// unit-test kernel for box_qp_rows<M> (wave mapping): one problem per wavefront
+// unit-test kernel for the cooperative box QP of the wave mapping, one problem per wavefront, in the form this library's
+// backward step runs: box_qp_row<M> (ilqg_row.hpp) where the step is the row mapping's, box_qp_rows<M> (ilqg_wave.hpp)
+// where it is the one-output-element-per-lane one (N_X or N_U beyond 16, and the `_elem` library)
 template <int M>
 __global__ __launch_bounds__(64) void k_boxqp_rows_test(int count, const double *H, const double *g, const double *lower,
                                                         const double *upper, double *x, int *clamp, int *n_free, double *invH,
@@ -470,9 +472,9 @@ __global__ __launch_bounds__(64) void k_boxqp_rows_test(int count, const double 
     for(int i = lane; i < T; i += 64) sH[i] = H[(size_t)t * T + i];
     if(lane < M) sl[lane] = x[(size_t)t * M + lane];
     wave_sync();
-    const int me = (M <= 16) ? (lane & 15) % M : lane % M;
+    const int me = (ROW_STEP && M <= 16) ? (lane & 15) % M : lane % M;
     int nf, r;
-    if constexpr(M <= 16)  // the form the row-mapped backward step uses
+    if constexpr(ROW_STEP && M <= 16)
         r = box_qp_row<M>(sH, g[(size_t)t * M + me], lower[(size_t)t * M + me], upper[(size_t)t * M + me], sl, scl, sinv, nf);
     else
         r = box_qp_rows<M>(sH, g[(size_t)t * M + me], lower[(size_t)t * M + me], upper[(size_t)t * M + me], sl, scl, sinv, nf);
@@ -487,3 +489,49 @@ __global__ __launch_bounds__(64) void k_boxqp_rows_test(int count, const double 
     }
     for(int i = lane; i < T; i += 64) invH[(size_t)t * T + i] = sinv[i];
 }
+
+#if ILQG_WAVE_MAP
+// unit-test kernel for box_qp_quad<M> (quad mapping, ilqg_quad.hpp): one wavefront per workgroup, four problems per
+// wavefront — row r = lane / 16 takes problem 4 * blockIdx.x + r.  A row whose problem lies beyond `count` loads and
+// stores nothing and is not active, nor is one whose entry of `active` is 0; every lane reaches the call (its ballots
+// are the wavefront's).  n_free is M minus the clamp flags set (box_qp_quad does not hand it back); the inverse goes out
+// in the packed full-index form of k_boxqp_test, lane `me` writing the entries (me, j), j >= me, of its row.
+template <int M>
+__global__ __launch_bounds__(64) void k_boxqp_quad_test(int count, const int *active, const double *H, const double *g, const double *lower,
+                                                        const double *upper, double *x, int *clamp, int *n_free, double *invH,
+                                                        int *rc) {
+    constexpr int T = tri(M), INV = (M + 1) * M, ROW = INV + 2 * M;  // per row: the inverse's exchange, the lean build's diagonal
+    __shared__ double S[4 * ROW];
+    const int lane = threadIdx.x & 63, row = lane >> 4, c = lane & 15, me = c % M;
+    const int t = 4 * (int)blockIdx.x + row;
+    const bool in = t < count;
+    double Hrow[M], gg = 0.0, lo = 0.0, up = 0.0, xx = 0.0, invrow[M];
+#pragma unroll
+    for(int j = 0; j < M; j++) Hrow[j] = 0.0;
+    bool act = false;
+    if(in) {
+#pragma unroll
+        for(int j = 0; j < M; j++) Hrow[j] = H[(size_t)t * T + sy(me, j)];
+        gg = g[(size_t)t * M + me];
+        lo = lower[(size_t)t * M + me];
+        up = upper[(size_t)t * M + me];
+        xx = x[(size_t)t * M + me];
+        act = active[t] != 0;
+    }
+    const unsigned inv_at = lds_addr(S + row * ROW);
+    int cl;
+    const int r = box_qp_quad<M>(Hrow, gg, lo, up, xx, act, inv_at, cl, invrow, inv_at + INV * 8);
+    const unsigned set = row_bits(__builtin_amdgcn_ballot_w64(cl != 0 && c < M), lane);
+    if(in && c < M) {
+        x[(size_t)t * M + me] = xx;
+        clamp[t * M + me] = cl;
+#pragma unroll
+        for(int j = 0; j < M; j++)
+            if(j >= me) invH[(size_t)t * T + ut(me, j)] = invrow[j];
+        if(c == 0) {
+            rc[t] = r;
+            n_free[t] = M - __builtin_popcount(set);
+        }
+    }
+}
+#endif

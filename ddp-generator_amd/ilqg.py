@@ -455,6 +455,8 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
     lib.ilqg_boxqp_batch.argtypes = [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _ip]
     lib.ilqg_boxqp_wave_batch.argtypes = lib.ilqg_boxqp_batch.argtypes
     lib.ilqg_boxqp_table_batch.argtypes = lib.ilqg_boxqp_batch.argtypes
+    if hasattr(lib, "ilqg_boxqp_quad_batch"):  # (a unit-test entry: a library built before it existed still loads and solves)
+        lib.ilqg_boxqp_quad_batch.argtypes = lib.ilqg_boxqp_batch.argtypes + [C.c_void_p]
     lib.ilqg_sincos_batch.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
     lib.ilqg_multi_create.restype = v
     lib.ilqg_multi_create.argtypes = [C.c_int, _ip, C.c_int, C.c_int]
@@ -1113,10 +1115,14 @@ def solve_single(x0, u_nom, params, opts=None, problem="carparking", full_ddp=0,
     return dict(success=int(rc), x=x, u=u, cost=float(cost[0]), iterations=int(iters[0]), seconds=float(secs[0]))
 
 
-def boxqp_batch(n, H, g, lower, upper, x0, problem="carparking", full_ddp=0, device=0, strict=False, cooperative=False):
+def boxqp_batch(n, H, g, lower, upper, x0, problem="carparking", full_ddp=0, device=0, strict=False, cooperative=False, active=None):
     """device box-QP on `count` independent problems (arrays [count, ...]); unit-test entry.
-    cooperative: the form of the one-wavefront-per-trajectory mapping (one lane per variable);
-    cooperative="table": the per-lane form with the factorisations of all clamp patterns made up front"""
+    cooperative: the form of the one-wavefront-per-trajectory mapping (one lane per variable; the one the library's
+    backward step runs: box_qp_row, or box_qp_rows in the `elem` library);
+    cooperative="table": the per-lane form with the factorisations of all clamp patterns made up front;
+    cooperative="quad": the form of the quad mapping, four problems per wavefront (problems 4 w ... 4 w + 3 are the rows of
+    wavefront w; libraries of the wave mapping only).  active [count] (quad only): 0 = the problem's row runs along and
+    commits nothing — x as given, rc 0; None = all active"""
     lib = load_library(problem, full_ddp, strict)
     H = np.ascontiguousarray(H, dtype=np.float64)
     count = H.shape[0]
@@ -1127,11 +1133,23 @@ def boxqp_batch(n, H, g, lower, upper, x0, problem="carparking", full_ddp=0, dev
     invH = np.zeros((count, t))
     rc = np.zeros(count, dtype=np.int32)
     fn = lib.ilqg_boxqp_table_batch if cooperative == "table" else (lib.ilqg_boxqp_wave_batch if cooperative else lib.ilqg_boxqp_batch)
+    more = ()
+    if cooperative == "quad":
+        if not hasattr(lib, "ilqg_boxqp_quad_batch"):
+            raise IlqgError("boxqp_batch: %s has no ilqg_boxqp_quad_batch: build it again" % library_path(problem, full_ddp, strict))
+        fn = lib.ilqg_boxqp_quad_batch
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.int32)
+            if active.shape != (count,):
+                raise IlqgError("boxqp_batch: active must hold one entry per problem")
+        more = (None if active is None else active.ctypes.data,)
+    elif active is not None:
+        raise IlqgError('boxqp_batch: active goes with cooperative="quad"')
     r = fn(device, n, count, H.reshape(count, t), np.ascontiguousarray(g, dtype=np.float64),
            np.ascontiguousarray(lower, dtype=np.float64), np.ascontiguousarray(upper, dtype=np.float64),
-           x, clamp, nfree, invH, rc)
+           x, clamp, nfree, invH, rc, *more)
     if r:
-        raise IlqgError("ilqg_boxqp_batch failed")
+        raise IlqgError(lib.ilqg_batch_error(None).decode() if cooperative == "quad" else "ilqg_boxqp_batch failed")
     return dict(rc=rc, x=x, clamp=clamp, n_free=nfree, invH=invH)
 
 

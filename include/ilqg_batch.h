@@ -481,6 +481,13 @@ int ilqg_boxqp_wave_batch(int device, int n, int count, const double *H, const d
 int ilqg_boxqp_table_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
                            const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc);
 
+/* ... and through the form of the quad mapping (four problems per wavefront, one per 16-lane row; n = 2 or N_U).
+ * active: one int per problem, 0 = the problem's row runs along without committing anything (x stays as given, rc 0),
+ * NULL = every problem active.  Only the libraries of the one-wavefront-per-trajectory mapping carry this form; any
+ * other refuses before anything is allocated, text via ilqg_batch_error(NULL) */
+int ilqg_boxqp_quad_batch(int device, int n, int count, const double *H, const double *g, const double *lower,
+                          const double *upper, double *x, int *clamp, int *n_free, double *invH, int *rc, const int *active);
+
 /* device sin/cos as the generated callbacks see them, on n arguments (unit tests) */
 int ilqg_sincos_batch(int device, int n, const double *x, double *s, double *c);
 
