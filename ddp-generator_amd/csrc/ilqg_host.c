@@ -275,6 +275,14 @@ const char *ilqg_batch_error(const ilqg_batch_t *c) { return c ? c->err : g_crea
 
 static int param_len(const ilqg_batch_t *c, int i) { return paramdesc[i]->size == -1 ? c->N + 1 : paramdesc[i]->size; }
 
+/* the one lookup of a parameter's name: its index in paramdesc[], or -1 */
+static int find_param(const char *name) {
+    int i;
+    for(i = 0; i < n_params; i++)
+        if(strcmp(paramdesc[i]->name, name) == 0) return i;
+    return -1;
+}
+
 /* groups = 0: automatic (ILQG_GROUPS in the environment, else 4 for large batches in the lane mapping, see above) */
 ilqg_batch_t *ilqg_batch_create_groups(int device, int batch, int n_hor, int groups) {
     int i, g, per, dims[8];
@@ -444,37 +452,34 @@ int ilqg_batch_set_option(ilqg_batch_t *c, const char *name, const double *value
 }
 
 int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value, int n) {
-    int i;
-    for(i = 0; i < n_params; i++) {
-        if(strcmp(paramdesc[i]->name, name) != 0) continue;
-        if(param_len(c, i) != n) {
-            snprintf(c->err, sizeof(c->err), "Parameter name '%s' must be a vector length %d.", name, param_len(c, i));
-            return 1;
-        }
-        {
-            int j;
-            for(j = 0; j < c->pb_n; j++)
-                if(c->pb_named[j] == i) {
-                    snprintf(c->err, sizeof(c->err), "ilqg_batch_set_param: name: parameter '%s' currently has a value per trajectory "
-                             "(ilqg_batch_set_params_batch); a shared value would be read by no trajectory.  Clear the per-trajectory set "
-                             "first: ilqg_batch_set_params_batch(c, 0, NULL, NULL)", name);
-                    return 1;
-                }
-        }
-        if(i < 64 && c->ps_on[i]) {
-            snprintf(c->err, sizeof(c->err), "ilqg_batch_set_param: name: parameter '%s' currently has a window per trajectory "
-                     "(ilqg_batch_set_param_steps_batch); a shared window would be read by no trajectory.  Use "
-                     "ilqg_batch_set_param_steps_batch / ilqg_batch_shift_param_batch, or make the name shared again first: "
-                     "ilqg_batch_set_param_steps_batch(c, name, values = NULL)", name);
-            return 1;
-        }
-        memcpy(c->p[i], value, sizeof(double) * n);
-        c->p_given[i] = 1;
-        c->params_pushed = 0;
-        return 0;
+    const int i = find_param(name);
+    int j;
+    if(i < 0) {
+        snprintf(c->err, sizeof(c->err), "Parameter name '%s' is not a parameter of this problem.", name);
+        return 1;
     }
-    snprintf(c->err, sizeof(c->err), "Parameter name '%s' is not a parameter of this problem.", name);
-    return 1;
+    if(param_len(c, i) != n) {
+        snprintf(c->err, sizeof(c->err), "Parameter name '%s' must be a vector length %d.", name, param_len(c, i));
+        return 1;
+    }
+    for(j = 0; j < c->pb_n; j++)
+        if(c->pb_named[j] == i) {
+            snprintf(c->err, sizeof(c->err), "ilqg_batch_set_param: name: parameter '%s' currently has a value per trajectory "
+                     "(ilqg_batch_set_params_batch); a shared value would be read by no trajectory.  Clear the per-trajectory set "
+                     "first: ilqg_batch_set_params_batch(c, 0, NULL, NULL)", name);
+            return 1;
+        }
+    if(i < 64 && c->ps_on[i]) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_set_param: name: parameter '%s' currently has a window per trajectory "
+                 "(ilqg_batch_set_param_steps_batch); a shared window would be read by no trajectory.  Use "
+                 "ilqg_batch_set_param_steps_batch / ilqg_batch_shift_param_batch, or make the name shared again first: "
+                 "ilqg_batch_set_param_steps_batch(c, name, values = NULL)", name);
+        return 1;
+    }
+    memcpy(c->p[i], value, sizeof(double) * n);
+    c->p_given[i] = 1;
+    c->params_pushed = 0;
+    return 0;
 }
 
 /* options and parameters are pushed lazily before any stage */
@@ -518,53 +523,92 @@ int ilqg_batch_set_x0(ilqg_batch_t *c, const double *x0) { return each_write_ste
 int ilqg_batch_set_u(ilqg_batch_t *c, const double *u) { return each_write(c, ILQG_F_U, u, "set_u"); }
 int ilqg_batch_set_x(ilqg_batch_t *c, const double *x) { return each_write(c, ILQG_F_X, x, "set_x"); }
 
-int ilqg_batch_init(ilqg_batch_t *c) {
+/* what init does: the initial roll-out and the solver's entry state, on every group */
+static int restart(ilqg_batch_t *c) {
     int g;
-    if(push_config(c)) return 1;
     EACH_GROUP(g) {
         if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
         if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
     }
+    return 0;
+}
+
+int ilqg_batch_init(ilqg_batch_t *c) { return push_config(c) || restart(c); }
+
+/* The _device forms take and fill device memory of the caller in the order of ITS stream, by events, and never wait on the
+ * host.  Their bracket opens in two parts, because entries refuse between them: device_ptrs refuses what is not device memory
+ * of this device among the pointers given (NULL: left out), stream_in makes every group's stream wait for the caller's; each
+ * group then closes its own (ilqg_dev_stream_out) behind its last kernel that touches the caller's memory. */
+typedef struct { const void *ptr; const char *name; } named_ptr_t;
+static int device_ptrs(ilqg_batch_t *c, const char *who, const named_ptr_t *ptrs, int n) {
+    int i;
+    for(i = 0; i < n; i++)
+        if(ptrs[i].ptr && ilqg_dev_check_device_ptr(c->dev[0], ptrs[i].ptr, ptrs[i].name)) return fail(c, who);
+    return 0;
+}
+static int stream_in(ilqg_batch_t *c, void *stream, const char *what) {
+    int g;
+    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, what);
     return 0;
 }
 
 /* Receding horizon (no reference counterpart as a call; it is what the MEX entry's caller does between two calls:
  * u_nom = [u(:, s+1:end), tail] and a new x0, iLQG_mex.c:113-120).  The plan moves on the device (ilqg_dev_shift); only
- * x0_new and u_tail go up.  Then exactly ilqg_batch_init: initial roll-out, solver entry state. */
-int ilqg_batch_shift(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail) {
+ * x0_new and u_tail go up, or are read where they lie (on_device: ilqg_batch_shift_device).  Then exactly ilqg_batch_init:
+ * initial roll-out, solver entry state. */
+static int shift(ilqg_batch_t *c, const char *who, int on_device, int steps, const double *x0_new, const double *u_tail, void *stream) {
+    const named_ptr_t ptrs[] = {{x0_new, "x0_new"}, {u_tail, "u_tail"}};
     int g;
     if(steps < 0 || steps >= c->N) {
-        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift: steps = %d, must be in 0 .. n_hor - 1 = %d", steps, c->N - 1);
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 0 .. n_hor - 1 = %d", who, steps, c->N - 1);
         return 1;
     }
+    if(on_device && device_ptrs(c, who, ptrs, 2)) return 1;
     if(push_config(c)) return 1;
+    if(on_device && stream_in(c, stream, "shift: stream")) return 1;
+    /* the shift kernel brings U home and clears the location indices, then the caller's values */
     EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, x0_new == NULL)) return fail(c, "shift");
     EACH_GROUP(g) {
-        if(x0_new && ilqg_dev_write_steps(c->dev[g], ILQG_F_X, x0_new + (size_t)c->first[g] * N_X, 1)) return fail(c, "shift: x0_new");
-        if(u_tail && steps > 0 && ilqg_dev_write_u_tail(c->dev[g], u_tail + (size_t)c->first[g] * steps * N_U, steps))
-            return fail(c, "shift: u_tail");
+        const double *const x0_g = x0_new ? x0_new + (size_t)c->first[g] * N_X : NULL;
+        const double *const tail_g = (u_tail && steps > 0) ? u_tail + (size_t)c->first[g] * steps * N_U : NULL;
+        if(x0_g && (on_device ? ilqg_dev_put_x0_device(c->dev[g], x0_g) : ilqg_dev_write_steps(c->dev[g], ILQG_F_X, x0_g, 1)))
+            return fail(c, "shift: x0_new");
+        if(tail_g && (on_device ? ilqg_dev_put_u_tail_device : ilqg_dev_write_u_tail)(c->dev[g], tail_g, steps)) return fail(c, "shift: u_tail");
+        /* behind the last kernel that reads the caller's memory, not behind the roll-out */
+        if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift: stream");
     }
-    EACH_GROUP(g) {
-        if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
-        if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
-    }
+    return restart(c);
+}
+
+int ilqg_batch_shift(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail) {
+    return shift(c, "ilqg_batch_shift", 0, steps, x0_new, u_tail, NULL);
+}
+
+int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
+    return shift(c, "ilqg_batch_shift_device", 1, steps, x0_new, u_tail, stream);
+}
+
+/* a batch entry that runs whole rounds cannot move the window of a per-time-step parameter: refused, and the loop named */
+static int no_step_params(ilqg_batch_t *c, const char *who) {
+    int i;
+    for(i = 0; i < n_params; i++)
+        if(paramdesc[i]->size == -1) {
+            snprintf(c->err, sizeof(c->err), "%s: parameter '%s' has one value per time step and its window must move "
+                     "with the horizon: loop over ilqg_batch_iterate, ilqg_batch_set_param and ilqg_batch_shift instead", who, paramdesc[i]->name);
+            return 1;
+        }
     return 0;
 }
 
 static int iterate_groups(ilqg_batch_t *c, int n);
 int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, double *x_applied, double *u_applied, double *cost) {
-    int g, r, i;
+    int g, r;
     if(rounds < 1 || iterations < 0) return fail_msg(c, "ilqg_batch_receding: need rounds >= 1 and iterations >= 0");
     if(steps < 1 || steps >= c->N) {
         snprintf(c->err, sizeof(c->err), "ilqg_batch_receding: steps = %d, must be in 1 .. n_hor - 1 = %d", steps, c->N - 1);
         return 1;
     }
-    for(i = 0; i < n_params; i++)
-        if(paramdesc[i]->size == -1) {
-            snprintf(c->err, sizeof(c->err), "ilqg_batch_receding: parameter '%s' has one value per time step and its window must move "
-                     "with the horizon: loop over ilqg_batch_iterate, ilqg_batch_set_param and ilqg_batch_shift instead", paramdesc[i]->name);
-            return 1;
-        }
+    if(no_step_params(c, "ilqg_batch_receding")) return 1;
     if(push_config(c)) return 1;
     EACH_GROUP(g) if(ilqg_dev_log_begin(c->dev[g], rounds, steps)) return fail(c, "receding: log");
     for(r = 0; r < rounds; r++) {
@@ -582,8 +626,7 @@ int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, 
 }
 
 /* The control interval of a caller with its own plant: {iterate; head; the caller's plant step; shift}.  The heads are read
- * where the plans live (nothing moves home, nothing else changes); the _device forms take and fill device memory of the
- * caller in the order of ITS stream, by events, and never wait on the host. */
+ * where the plans live (nothing moves home, nothing else changes). */
 static int head_steps(ilqg_batch_t *c, const char *who, int steps) {
     if(steps >= 1 && steps <= c->N) return 0;
     snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor = %d", who, steps, c->N);
@@ -602,13 +645,10 @@ int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l,
 }
 
 int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream) {
+    const named_ptr_t ptrs[] = {{x, "x"}, {u, "u"}, {l, "l"}, {L, "L"}, {cost, "cost"}};
     int g;
     if(head_steps(c, "ilqg_batch_head_device", steps)) return 1;
-    if((x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) || (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u")) ||
-       (l && ilqg_dev_check_device_ptr(c->dev[0], l, "l")) || (L && ilqg_dev_check_device_ptr(c->dev[0], L, "L")) ||
-       (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")))
-        return fail(c, "ilqg_batch_head_device");
-    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "head: stream");
+    if(device_ptrs(c, "ilqg_batch_head_device", ptrs, 5) || stream_in(c, stream, "head: stream")) return 1;
     EACH_GROUP(g) {
         if(ilqg_dev_head_device(c->dev[g], steps, HEAD_AT(x, N_X), HEAD_AT(u, N_U), HEAD_AT(l, N_U), HEAD_AT(L, N_U * N_X),
                                 cost ? cost + c->first[g] : NULL))
@@ -662,9 +702,8 @@ static int policy_names(ilqg_batch_t *c, const char *who, int n_names, const cha
             snprintf(c->err, sizeof(c->err), "%s: names[%d] is NULL", who, i);
             return 1;
         }
-        for(k = 0; k < n_params; k++)
-            if(strcmp(paramdesc[k]->name, names[i]) == 0) break;
-        if(k == n_params) {
+        k = find_param(names[i]);
+        if(k < 0) {
             snprintf(c->err, sizeof(c->err), "%s: names[%d]: Parameter name '%s' is not member of parameters struct.", who, i, names[i]);
             return 1;
         }
@@ -692,20 +731,14 @@ static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_d
                           double *x_end, double *x, double *u, void *stream) {
     const char *const what = params ? "policy_rollout_params" : "policy_rollout";
     const char *const what_stream = params ? "policy_rollout_params: stream" : "policy_rollout: stream";
+    const named_ptr_t ptrs[] = {{x0, "x0"}, {params ? values : NULL, "values"}, {cost, "cost"}, {ok, "ok"}, {x_end, "x_end"}, {x, "x"}, {u, "u"}};
     int g, named[POLICY_MAX_NAMES], W = 0;
     if(policy_args(c, who, n_starts, x0)) return 1;
     if(params && policy_names(c, who, n_names, names, values, named, &W)) return 1;
-    if(on_device &&
-       (ilqg_dev_check_device_ptr(c->dev[0], x0, "x0") || (params && ilqg_dev_check_device_ptr(c->dev[0], values, "values")) ||
-        (cost && ilqg_dev_check_device_ptr(c->dev[0], cost, "cost")) || (ok && ilqg_dev_check_device_ptr(c->dev[0], ok, "ok")) ||
-        (x_end && ilqg_dev_check_device_ptr(c->dev[0], x_end, "x_end")) || (x && ilqg_dev_check_device_ptr(c->dev[0], x, "x")) ||
-        (u && ilqg_dev_check_device_ptr(c->dev[0], u, "u"))))
-        return fail(c, who);
+    if(on_device && device_ptrs(c, who, ptrs, 7)) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
     if(push_config(c)) return 1;
-    if(on_device) {
-        EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, what_stream);
-    }
+    if(on_device && stream_in(c, stream, what_stream)) return 1;
     EACH_GROUP(g) {
         if((on_device ? ilqg_dev_policy_rollout : ilqg_dev_policy_rollout_host)(
                c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared, alpha, feedback,
@@ -739,20 +772,26 @@ int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const
                           x_end, x, u, stream);
 }
 
+/* the wave mapping carries no parameters per trajectory: refused by every entry that would set or read them */
+static int wave_mapped(ilqg_batch_t *c, const char *who) {
+    int dims[8];
+    ilqg_dev_dims(dims);
+    if(!dims[7]) return 0;
+    snprintf(c->err, sizeof(c->err), "%s: this library maps one wavefront to a trajectory (the wave mapping: the *_wave libraries and the "
+             "problems with N_X = 10 or 16); its kernels do not carry parameters per lane.  Per-trajectory parameters need a lane-mapped "
+             "library", who);
+    return 1;
+}
+
 /* Per-trajectory problem parameters: trajectory b plans — and is rolled out, and its plant advances — under the batch's
  * fixed-size parameters with the named ones replaced by row b of the caller's table.  Names are resolved by the code
  * ilqg_batch_policy_rollout_params uses (policy_names); every refusal happens before a group is touched.  The groups each
  * hold their slice of the rows (ilqg_dev_set_params_batch). */
 static int set_params_batch(ilqg_batch_t *c, const char *who, int on_device, int n_names, const char *const *names, const double *values,
                             void *stream) {
-    int g, dims[8], named[POLICY_MAX_NAMES], W = 0;
-    ilqg_dev_dims(dims);
-    if(dims[7]) {
-        snprintf(c->err, sizeof(c->err), "%s: this library maps one wavefront to a trajectory (the wave mapping: the *_wave libraries and the "
-                 "problems with N_X = 10 or 16); its kernels do not carry parameters per lane.  Per-trajectory parameters need a lane-mapped "
-                 "library", who);
-        return 1;
-    }
+    const named_ptr_t ptr = {values, "values"};
+    int g, named[POLICY_MAX_NAMES], W = 0;
+    if(wave_mapped(c, who)) return 1;
     if(n_names < 0) {
         snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0 clears the per-trajectory set)", who, n_names);
         return 1;
@@ -766,8 +805,7 @@ static int set_params_batch(ilqg_batch_t *c, const char *who, int on_device, int
         return 1;
     }
     if(n_names > 0 && policy_names(c, who, n_names, names, values, named, &W)) return 1;
-    if(n_names > 0 && on_device && ilqg_dev_check_device_ptr(c->dev[0], values, "values")) return fail(c, who);
-    if(n_names > 0 && on_device) EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "set_params_batch: stream");
+    if(n_names > 0 && on_device && (device_ptrs(c, who, &ptr, 1) || stream_in(c, stream, "set_params_batch: stream"))) return 1;
     EACH_GROUP(g) {
         if(ilqg_dev_set_params_batch(c->dev[g], n_names, named, n_names > 0 ? values + (size_t)c->first[g] * (size_t)W : NULL, on_device))
             return fail(c, who);
@@ -797,9 +835,8 @@ int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out) 
         snprintf(c->err, sizeof(c->err), "%s: %s is NULL", who, !name ? "name" : "out");
         return 1;
     }
-    for(i = 0; i < n_params; i++)
-        if(strcmp(paramdesc[i]->name, name) == 0) break;
-    if(i == n_params) {
+    i = find_param(name);
+    if(i < 0) {
         snprintf(c->err, sizeof(c->err), "%s: name: Parameter name '%s' is not member of parameters struct.", who, name);
         return 1;
     }
@@ -834,21 +871,14 @@ int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out) 
  * group its slice (ilqg_dev_set_param_steps_batch); the host keeps which names have them (ps_on).  step_name resolves a name
  * to a parameter of size -1 and makes the refusals every entry below shares, before a group is touched. */
 static int step_name(ilqg_batch_t *c, const char *who, const char *name, int need_rows, int *index) {
-    int i, dims[8];
-    ilqg_dev_dims(dims);
-    if(dims[7]) {
-        snprintf(c->err, sizeof(c->err), "%s: this library maps one wavefront to a trajectory (the wave mapping: the *_wave libraries and the "
-                 "problems with N_X = 10 or 16); its kernels do not carry parameters per lane.  Per-trajectory parameters need a lane-mapped "
-                 "library", who);
-        return 1;
-    }
+    int i;
+    if(wave_mapped(c, who)) return 1;
     if(!name) {
         snprintf(c->err, sizeof(c->err), "%s: name is NULL", who);
         return 1;
     }
-    for(i = 0; i < n_params; i++)
-        if(strcmp(paramdesc[i]->name, name) == 0) break;
-    if(i == n_params) {
+    i = find_param(name);
+    if(i < 0) {
         snprintf(c->err, sizeof(c->err), "%s: name: Parameter name '%s' is not member of parameters struct.", who, name);
         return 1;
     }
@@ -871,11 +901,11 @@ static int step_name(ilqg_batch_t *c, const char *who, const char *name, int nee
 }
 
 static int set_param_steps_batch(ilqg_batch_t *c, const char *who, int on_device, const char *name, const double *values, void *stream) {
+    const named_ptr_t ptr = {values, "values"};
     int g, i = 0;
     const size_t n = (size_t)c->N + 1;
     if(step_name(c, who, name, 0, &i)) return 1;
-    if(values && on_device && ilqg_dev_check_device_ptr(c->dev[0], values, "values")) return fail(c, who);
-    if(values && on_device) EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "set_param_steps_batch: stream");
+    if(values && on_device && (device_ptrs(c, who, &ptr, 1) || stream_in(c, stream, "set_param_steps_batch: stream"))) return 1;
     EACH_GROUP(g) {
         if(ilqg_dev_set_param_steps_batch(c->dev[g], i, values ? values + (size_t)c->first[g] * n : NULL, on_device)) return fail(c, who);
         if(values && on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "set_param_steps_batch: stream");
@@ -920,15 +950,16 @@ int ilqg_batch_get_param_steps_batch(ilqg_batch_t *c, const char *name, double *
 
 /* the windows move with the horizon, each row in place on the device (k_shift_param_rows) */
 static int shift_param_batch(ilqg_batch_t *c, const char *who, int on_device, const char *name, int steps, const double *tail, void *stream) {
+    const named_ptr_t ptr = {tail, "tail"};
     int g, i = 0;
     if(step_name(c, who, name, 1, &i)) return 1;
     if(steps < 0 || steps > c->N) {
         snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 0 .. n_hor = %d", who, steps, c->N);
         return 1;
     }
-    if(tail && on_device && ilqg_dev_check_device_ptr(c->dev[0], tail, "tail")) return fail(c, who);
+    if(on_device && device_ptrs(c, who, &ptr, 1)) return 1;
     if(steps == 0) return 0;
-    if(tail && on_device) EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "shift_param_batch: stream");
+    if(tail && on_device && stream_in(c, stream, "shift_param_batch: stream")) return 1;
     EACH_GROUP(g) {
         if(ilqg_dev_shift_param_batch(c->dev[g], i, steps, tail ? tail + (size_t)c->first[g] * (size_t)steps : NULL, on_device)) return fail(c, who);
         if(tail && on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift_param_batch: stream");
@@ -946,32 +977,6 @@ int ilqg_batch_shift_param_batch_device(ilqg_batch_t *c, const char *name, int s
     return shift_param_batch(c, "ilqg_batch_shift_param_batch_device", 1, name, steps, tail, stream);
 }
 
-int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream) {
-    int g;
-    if(steps < 0 || steps >= c->N) {
-        snprintf(c->err, sizeof(c->err), "ilqg_batch_shift_device: steps = %d, must be in 0 .. n_hor - 1 = %d", steps, c->N - 1);
-        return 1;
-    }
-    if((x0_new && ilqg_dev_check_device_ptr(c->dev[0], x0_new, "x0_new")) || (u_tail && ilqg_dev_check_device_ptr(c->dev[0], u_tail, "u_tail")))
-        return fail(c, "ilqg_batch_shift_device");
-    if(push_config(c)) return 1;
-    EACH_GROUP(g) if(ilqg_dev_stream_in(c->dev[g], stream)) return fail(c, "shift: stream");
-    /* the order of ilqg_batch_shift: the shift kernel brings U home and clears the location indices, then the caller's values */
-    EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, x0_new == NULL)) return fail(c, "shift");
-    EACH_GROUP(g) {
-        if(x0_new && ilqg_dev_put_x0_device(c->dev[g], x0_new + (size_t)c->first[g] * N_X)) return fail(c, "shift: x0_new");
-        if(u_tail && steps > 0 && ilqg_dev_put_u_tail_device(c->dev[g], u_tail + (size_t)c->first[g] * steps * N_U, steps))
-            return fail(c, "shift: u_tail");
-        /* behind the last kernel that reads the caller's memory, not behind the roll-out */
-        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift: stream");
-    }
-    EACH_GROUP(g) {
-        if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
-        if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
-    }
-    return 0;
-}
-
 /* The closed loop of planner and plant, resident on the device (k_plant.inc): per round { iterate; the plants advance
  * `steps` steps from their own states under the plans' policies and the plants' parameters; the plans shift and start again
  * from the plants' states }.  Everything is refused before anything is launched or allocated; values, disturbance and
@@ -980,7 +985,7 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
                               double *cost_applied, double *plan_cost, int *ok) {
     static const char who[] = "ilqg_batch_receding_plant";
-    int g, r, i, named[POLICY_MAX_NAMES], W = 0;
+    int g, r, named[POLICY_MAX_NAMES], W = 0;
     if(rounds < 1) {
         snprintf(c->err, sizeof(c->err), "%s: rounds = %d, must be at least 1", who, rounds);
         return 1;
@@ -993,12 +998,7 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
         snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", who, steps, c->N - 1);
         return 1;
     }
-    for(i = 0; i < n_params; i++)
-        if(paramdesc[i]->size == -1) {
-            snprintf(c->err, sizeof(c->err), "%s: parameter '%s' has one value per time step and its window must move "
-                     "with the horizon: loop over ilqg_batch_iterate, ilqg_batch_set_param and ilqg_batch_shift instead", who, paramdesc[i]->name);
-            return 1;
-        }
+    if(no_step_params(c, who)) return 1;
     if(n_names < 0) {
         snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0: the plant is the model)", who, n_names);
         return 1;
@@ -1020,10 +1020,7 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
             /* ilqg_batch_shift(c, steps, x0_new = the plants' states, NULL), the states being on the device already */
             EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, 0)) return fail(c, "shift");
             EACH_GROUP(g) if(ilqg_dev_plant_put_x0(c->dev[g])) return fail(c, "shift: x0_new");
-            EACH_GROUP(g) {
-                if(ilqg_dev_rollout_init(c->dev[g])) return fail(c, "initial roll-out");
-                if(ilqg_dev_reset(c->dev[g])) return fail(c, "reset");
-            }
+            if(restart(c)) return 1;
         }
         EACH_GROUP(g) {
             const size_t first = (size_t)c->first[g];
@@ -1039,10 +1036,9 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
 /* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param), and in the host
  * mirror c->p[i], from which a later ilqg_batch_set_param of another parameter re-pushes the whole table */
 int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const double *tail) {
-    int i, k, g, n;
-    for(i = 0; i < n_params; i++)
-        if(strcmp(paramdesc[i]->name, name) == 0) break;
-    if(i == n_params) {
+    const int i = find_param(name);
+    int k, g, n;
+    if(i < 0) {
         snprintf(c->err, sizeof(c->err), "Parameter name '%s' is not a parameter of this problem.", name);
         return 1;
     }
@@ -2020,14 +2016,19 @@ int ilqg_multi_set_param(ilqg_multi_t *m, const char *name, const double *value,
     EACH_SHARD(g) if(ilqg_batch_set_param(m->shard[g], name, value, n)) return multi_fail(m, g);
     return 0;
 }
+/* the width of a row of the named parameters, where every name is one of the problem's fixed-size ones; what is not (unknown,
+ * NULL, one value per time step) counts nothing here, and the shard refuses the call */
+static size_t rows_width(int n_names, const char *const *names) {
+    size_t W = 0;
+    int i, k;
+    for(i = 0; names && i < n_names; i++)
+        if(names[i] && (k = find_param(names[i])) >= 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    return W;
+}
 /* every shard's rows: those from its first trajectory on */
 int ilqg_multi_set_params_batch(ilqg_multi_t *m, int n_names, const char *const *names, const double *values) {
-    int g, i, k;
-    size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
-    if(names && values)
-        for(i = 0; i < n_names; i++)
-            for(k = 0; names[i] && k < n_params; k++)
-                if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    const size_t W = values ? rows_width(n_names, names) : 0;
+    int g;
     EACH_SHARD(g)
         if(ilqg_batch_set_params_batch(m->shard[g], n_names, names, values ? values + (size_t)m->first[g] * W : NULL)) return multi_fail(m, g);
     return 0;
@@ -2079,13 +2080,9 @@ int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l,
 static int multi_policy_rollout(ilqg_multi_t *m, const char *who, int params, int n_starts, const double *x0, int n_names, const char *const *names,
                                 const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
                                 double *u) {
-    int g, i, k;
-    size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
+    const size_t W = (params && values && !shared) ? rows_width(n_names, names) : 0;
     const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
-    if(params && names && values && !shared)
-        for(i = 0; i < n_names; i++)
-            for(k = 0; names[i] && k < n_params; k++)
-                if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    int g;
     EACH_SHARD(g) {
         const size_t at = (size_t)m->first[g] * r;
         if(policy_rollout(m->shard[g], who, params, 0, n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
@@ -2107,13 +2104,9 @@ int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double
 int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
                               double *cost_applied, double *plan_cost, int *ok) {
-    int g, i, k;
-    size_t W = 0;  /* the width of a row, where every name is one of the problem's (else the shard refuses the call) */
+    const size_t W = values ? rows_width(n_names, names) : 0;
     const size_t rn = rounds > 0 ? (size_t)rounds : 0, per = rn * (steps > 0 ? (size_t)steps : 0);
-    if(names && values)
-        for(i = 0; i < n_names; i++)
-            for(k = 0; names[i] && k < n_params; k++)
-                if(strcmp(paramdesc[k]->name, names[i]) == 0 && paramdesc[k]->size > 0) W += (size_t)paramdesc[k]->size;
+    int g;
     EACH_SHARD(g) {
         const size_t at = (size_t)m->first[g];
         if(ilqg_batch_receding_plant(m->shard[g], rounds, steps, iterations, feedback, x_plant ? x_plant + at * N_X : NULL, n_names, names,

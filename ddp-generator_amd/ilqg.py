@@ -111,12 +111,32 @@ def _cuda_address(a, shape, device, what):
     return C.c_void_p(a.data_ptr() or None)
 
 
-def _head_arrays(B, steps, nx, nu, gains):
-    n = max(int(steps), 0)
-    out = dict(x=np.zeros((B, n, nx)), u=np.zeros((B, n, nu)), cost=np.zeros(B))
+def _outputs(shapes, order, torch=None, dev=None):
+    """(the outputs of one library call, their addresses in the entry's order — None for one left out): numpy arrays, or
+    with torch tensors on `dev`; float64 but for `ok`"""
+    if torch is None:
+        out = {k: np.zeros(shape, dtype=np.int32 if k == "ok" else np.float64) for k, shape in shapes.items()}
+        return out, [_address(out.get(k)) for k in order]
+    out = {k: torch.empty(shape, dtype=torch.int32 if k == "ok" else torch.float64, device=dev) for k, shape in shapes.items()}
+    return out, [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in order]
+
+
+def _head_outputs(solver, steps, gains, torch=None, dev=None):
+    """the outputs of head(): see _outputs"""
+    B, n, nx, nu = solver.B, max(int(steps), 0), solver.problem.nx, solver.problem.nu
+    shapes = dict(x=(B, n, nx), u=(B, n, nu), cost=(B,))
     if gains:
-        out.update(l=np.zeros((B, n, nu)), L=np.zeros((B, n, nu * nx)))
-    return out
+        shapes.update(l=(B, n, nu), L=(B, n, nu * nx))
+    return _outputs(shapes, ("x", "u", "l", "L", "cost"), torch, dev)
+
+
+def _rollout_outputs(solver, R, trajectories, torch=None, dev=None):
+    """the outputs of policy_rollout(): see _outputs"""
+    B, N, nx, nu = solver.B, solver.N, solver.problem.nx, solver.problem.nu
+    shapes = dict(cost=(B, R), ok=(B, R), x_end=(B, R, nx))
+    if trajectories:
+        shapes.update(x=(B, R, N + 1, nx), u=(B, R, N, nu))
+    return _outputs(shapes, ("cost", "ok", "x_end", "x", "u"), torch, dev)
 
 
 def _policy_starts(x0, B, nx):
@@ -129,157 +149,116 @@ def _policy_starts(x0, B, nx):
     return np.ascontiguousarray(a)
 
 
-def _policy_param_sizes(problem, params):
-    """the sizes of the parameters a policy_rollout(params=...) names, in dict order; refused here as the library refuses
-    them: a name that is no parameter, and one with a value per time step"""
-    if not isinstance(params, dict) or not params:
-        raise IlqgError("policy_rollout: params must be a non-empty dict of parameter name -> array ([B, R, size], or [R, size] for every trajectory)")
+def _param_size(problem, who, what, name):
+    """the size of the problem's parameter `name` (-1: one value per time step); refused here as the library refuses it: a
+    name that is no parameter"""
     known = dict(problem.params)
-    sizes = []
-    for name in params:
-        if name not in known:
-            raise IlqgError("policy_rollout: params: Parameter name '%s' is not member of parameters struct." % name)
-        if known[name] < 1:
-            raise IlqgError("policy_rollout: params: '%s' has one value per time step; per-time-step parameters stay shared by all roll-outs" % name)
-        sizes.append(known[name])
+    if name not in known:
+        raise IlqgError("%s: %s: Parameter name '%s' is not member of parameters struct." % (who, what, name))
+    return known[name]
+
+
+def _named_sizes(who, problem, params, shared_by):
+    """the sizes of the fixed-size parameters the dict `params` names, in dict order; refused here as the library refuses
+    them: a name that is no parameter, and one with a value per time step (those stay shared by `shared_by`)"""
+    sizes = [_param_size(problem, who, "params", name) for name in params]
+    for name, size in zip(params, sizes):
+        if size < 1:
+            raise IlqgError("%s: params: '%s' has one value per time step; per-time-step parameters stay shared by %s" % (who, name, shared_by))
     return sizes
 
 
-def _policy_param_form(name, shape, size, B, R):
-    """True for a [R, size] array (one table for every trajectory), False for [B, R, size]; the last axis may be left out
-    for size 1"""
-    shape = tuple(int(n) for n in shape)
-    if shape == (B, R, size) or (size == 1 and shape == (B, R) and shape != (R, size)):
-        return False
-    if shape == (R, size) or (size == 1 and shape == (R,)):
-        return True
-    raise IlqgError("policy_rollout: params['%s'] has shape %s, expected (%d, %d, %d) or (%d, %d)%s, with R = %d as in x0"
-                    % (name, shape, B, R, size, R, size, " (the last axis may be left out)" if size == 1 else "", R))
+def _host_numbers(who, what, a):
+    """a host array argument as doubles, whatever its dtype and strides; refused: a tensor on the device"""
+    if _is_cuda(a):
+        raise IlqgError("%s: %s is a tensor on the device: pass device=True" % (who, what))
+    return np.asarray(a, dtype=np.float64)
 
 
-def _policy_param_names(params):
-    return (C.c_char_p * len(params))(*[name.encode() for name in params])
-
-
-def _policy_param_rows(problem, params, B, R):
-    """(names, values, shared) for ilqg_batch_policy_rollout_params from host arrays: values [B, R, W] or, where every
-    array is [R, size], [R, W], C-contiguous doubles, the named parameters one behind the other in dict order"""
-    sizes = _policy_param_sizes(problem, params)
-    cols, forms = [], []
-    for (name, a), size in zip(params.items(), sizes):
-        if _is_cuda(a):
-            raise IlqgError("policy_rollout: params['%s'] is a tensor on the device: pass device=True" % name)
-        a = np.asarray(a, dtype=np.float64)
-        forms.append(_policy_param_form(name, a.shape, size, B, R))
-        cols.append(a.reshape((R, size) if forms[-1] else (B, R, size)))
-    if len(set(forms)) != 1:
-        raise IlqgError("policy_rollout: params mixes [R, size] arrays (%s) with [B, R, size] arrays (%s): every array in one form"
-                        % (", ".join(n for n, f in zip(params, forms) if f), ", ".join(n for n, f in zip(params, forms) if not f)))
-    return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1)), 1 if forms[0] else 0
-
-
-def _policy_param_tensors(problem, params, B, R, device):
-    """the same checks for float64 torch tensors on the solver's GPU: [(tensor, its shape with the last axis)], shared"""
-    sizes = _policy_param_sizes(problem, params)
-    cols, forms = [], []
-    for (name, a), size in zip(params.items(), sizes):
-        what = "policy_rollout: params['%s']" % name
-        if not _is_cuda(a):
-            raise IlqgError("%s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % what)
-        forms.append(_policy_param_form(name, a.shape, size, B, R))
-        _cuda_address(a, a.shape, device, what)
-        cols.append((a, (R, size) if forms[-1] else (B, R, size)))
-    if len(set(forms)) != 1:
-        raise IlqgError("policy_rollout: params mixes [R, size] tensors (%s) with [B, R, size] tensors (%s): every tensor in one form"
-                        % (", ".join(n for n, f in zip(params, forms) if f), ", ".join(n for n, f in zip(params, forms) if not f)))
-    return cols, 1 if forms[0] else 0
+def _plant_numbers(who, what, a):
+    """a host array argument of receding_plant, which has no device form; refused too: a dtype that is no real number"""
+    if _is_cuda(a):
+        raise IlqgError("%s: %s is a tensor on the device: the loop takes host memory (numpy arrays)" % (who, what))
+    a = np.asarray(a)
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise IlqgError("%s: %s has dtype %s, expected real numbers (float64)" % (who, what, a.dtype))
+    return a.astype(np.float64, copy=False)
 
 
 def _plant_array(a, shape, what):
-    """a host array argument of receding_plant as C-contiguous doubles of that shape; refused: a tensor on the device, a
-    dtype that is no real number, another shape"""
-    if _is_cuda(a):
-        raise IlqgError("receding_plant: %s is a tensor on the device: the loop takes host memory (numpy arrays)" % what)
-    a = np.asarray(a)
-    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
-        raise IlqgError("receding_plant: %s has dtype %s, expected real numbers (float64)" % (what, a.dtype))
+    """a host array argument of receding_plant as C-contiguous doubles of that shape"""
+    a = _plant_numbers("receding_plant", what, a)
     if tuple(a.shape) != tuple(shape):
         raise IlqgError("receding_plant: %s has shape %s, expected %s" % (what, tuple(a.shape), tuple(shape)))
-    return np.ascontiguousarray(a, dtype=np.float64)
+    return np.ascontiguousarray(a)
 
 
-def _plant_param_rows(problem, params, B):
-    """(names, values [B, W]) for ilqg_batch_receding_plant: the named parameters one behind the other in dict order, each
-    array [B, size] (the last axis may be left out for size 1); refused here as the library refuses them: a name that is
-    no parameter, and one with a value per time step"""
-    if not isinstance(params, dict) or not params:
-        raise IlqgError("receding_plant: params must be a non-empty dict of parameter name -> array [B, size], or None for a plant that is the model")
-    known = dict(problem.params)
-    cols = []
-    for name, a in params.items():
-        if name not in known:
-            raise IlqgError("receding_plant: params: Parameter name '%s' is not member of parameters struct." % name)
-        if known[name] < 1:
-            raise IlqgError("receding_plant: params: '%s' has one value per time step; per-time-step parameters stay shared by planner and plant" % name)
-        size, what = known[name], "params['%s']" % name
-        if size == 1 and not _is_cuda(a) and np.ndim(a) == 1:
-            a = np.asarray(a)[:, None]
-        cols.append(_plant_array(a, (B, size), what))
-    return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1))
+def _param_names(params):
+    return (C.c_char_p * len(params))(*[name.encode() for name in params])
 
 
-def _params_batch_sizes(problem, params):
-    """the sizes of the parameters set_params_batch names, in dict order; refused here as the library refuses them"""
-    known = dict(problem.params)
-    sizes = []
-    for name in params:
-        if name not in known:
-            raise IlqgError("set_params_batch: params: Parameter name '%s' is not member of parameters struct." % name)
-        if known[name] < 1:
-            raise IlqgError("set_params_batch: params: '%s' has one value per time step; per-time-step parameters stay shared by all trajectories" % name)
-        sizes.append(known[name])
-    return sizes
-
-
-def _params_batch_rows(problem, params, B):
-    """(names, values [B, W]) for ilqg_batch_set_params_batch from host arrays: the named parameters one behind the other in
-    dict order, each array [B, size] (the last axis may be left out for size 1), copied as C-contiguous doubles whatever
-    their dtype and strides"""
-    cols = []
-    for (name, a), size in zip(params.items(), _params_batch_sizes(problem, params)):
-        if _is_cuda(a):
-            raise IlqgError("set_params_batch: params['%s'] is a tensor on the device: pass device=True" % name)
-        a = np.asarray(a, dtype=np.float64)
-        if tuple(a.shape) != (B, size) and not (size == 1 and tuple(a.shape) == (B,)):
-            raise IlqgError("set_params_batch: params['%s'] has shape %s, expected (%d, %d)%s"
-                            % (name, tuple(a.shape), B, size, " or (%d,)" % B if size == 1 else ""))
-        cols.append(a.reshape(B, size))
-    return _policy_param_names(params), np.ascontiguousarray(np.concatenate(cols, axis=-1))
-
-
-def _params_batch_tensors(problem, params, B, device):
-    """the same checks for float64 torch tensors on the solver's GPU: [(tensor, (B, size))]"""
-    cols = []
-    for (name, a), size in zip(params.items(), _params_batch_sizes(problem, params)):
-        what = "set_params_batch: params['%s']" % name
-        if not _is_cuda(a):
-            raise IlqgError("%s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % what)
+def _named_rows(who, problem, params, leads, shared_by, hint, column):
+    """The table of rows a call gives by name, params = {name: array}: (names, [(array, its shape in the table)], form).
+    `leads` are the admissible leading shapes — (B, R) or (R,) for roll-outs, (B,) for the planner's and the plant's tables —
+    and every array is leads[form] + (size,), all in ONE form; the last axis may be left out for size 1.  column(who, what,
+    a) makes of an argument what has a shape, or refuses it.  The named parameters stand one behind the other in dict order."""
+    cols, forms = [], []
+    for (name, a), size in zip(params.items(), _named_sizes(who, problem, params, shared_by)):
+        what = "params['%s']" % name
+        a = column(who, what, a)
         shape = tuple(int(n) for n in a.shape)
-        if shape != (B, size) and not (size == 1 and shape == (B,)):
-            raise IlqgError("%s has shape %s, expected (%d, %d)%s" % (what, shape, B, size, " or (%d,)" % B if size == 1 else ""))
-        _cuda_address(a, shape, device, what)
-        cols.append((a, (B, size)))
-    return cols
+        full, short = [lead + (size,) for lead in leads], list(leads) if size == 1 else []
+        if shape not in full + short:
+            raise IlqgError("%s: %s has shape %s, expected %s%s" % (who, what, shape, " or ".join(str(f) for f in full + short), hint))
+        forms.append((full + short).index(shape) % len(leads))
+        cols.append((a, full[forms[-1]]))
+    if len(set(forms)) != 1:
+        raise IlqgError("%s: params mixes %s: every array in one form"
+                        % (who, " with ".join("[%s] (%s)" % (", ".join([str(n) for n in leads[f]] + ["size"]), ", ".join(n for n, g in zip(params, forms) if g == f))
+                                              for f in sorted(set(forms), reverse=True))))
+    return _param_names(params), cols, forms[0]
+
+
+def _pack_arrays(who, problem, params, leads, shared_by, hint="", column=_host_numbers):
+    """_named_rows of host arrays: (names, the table [leads[form] + (W,)] as C-contiguous doubles, form)"""
+    names, cols, form = _named_rows(who, problem, params, leads, shared_by, hint, column)
+    return names, np.ascontiguousarray(np.concatenate([a.reshape(shape) for a, shape in cols], axis=-1)), form
+
+
+def _pack_tensors(who, problem, params, leads, shared_by, device, hint=""):
+    """_named_rows of contiguous float64 torch tensors on the solver's GPU, checked and not yet packed (_tensor_table)"""
+    def column(who, what, a):
+        if not _is_cuda(a):
+            raise IlqgError("%s: %s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % (who, what))
+        _cuda_address(a, a.shape, device, "%s: %s" % (who, what))
+        return a
+    return _named_rows(who, problem, params, leads, shared_by, hint, column)
+
+
+def _tensor_table(torch, dev, cols):
+    """the address of the table of _pack_tensors, packed with torch.cat on torch's current stream; a single tensor is the
+    table as it lies ([B] and [B, 1] are the same memory).  (address, what must outlive the call)"""
+    with torch.cuda.device(dev):
+        values = cols[0][0] if len(cols) == 1 else torch.cat([a.reshape(shape) for a, shape in cols], dim=-1)
+    return C.c_void_p(values.data_ptr() or None), values
+
+
+def _rollout_params(solver, params, R, device=None):
+    """(names, table or tensor columns, shared) of policy_rollout(params=...)"""
+    who, B = "policy_rollout", solver.B
+    if not isinstance(params, dict) or not params:
+        raise IlqgError("policy_rollout: params must be a non-empty dict of parameter name -> array ([B, R, size], or [R, size] for every trajectory)")
+    args = (who, solver.problem, params, ((B, R), (R,)), "all roll-outs")
+    hint = ", with R = %d as in x0" % R
+    return _pack_arrays(*args, hint=hint) if device is None else _pack_tensors(*args, device, hint=hint)
 
 
 def _param_steps_name(problem, who, name):
     """the name of a per-time-step parameter for set_param_steps_batch / shift_param_batch; refused here as the library refuses it"""
-    known = dict(problem.params)
-    if name not in known:
-        raise IlqgError("%s: name: Parameter name '%s' is not member of parameters struct." % (who, name))
-    if known[name] != -1:
+    size = _param_size(problem, who, "name", name)
+    if size != -1:
         raise IlqgError("%s: name: '%s' has a fixed size of %d, not one value per time step: fixed-size parameters per trajectory "
-                        "are set by set_params_batch" % (who, name, known[name]))
+                        "are set by set_params_batch" % (who, name, size))
     return name.encode()
 
 
@@ -288,9 +267,7 @@ def _param_steps_rows(who, what, a, shape, device, gpu):
     Host arrays are copied as C-contiguous doubles whatever their dtype and strides; with device=True a contiguous float64
     torch tensor on the solver's GPU is read where it is."""
     if not device:
-        if _is_cuda(a):
-            raise IlqgError("%s: %s is a tensor on the device: pass device=True" % (who, what))
-        a = np.asarray(a, dtype=np.float64)
+        a = _host_numbers(who, what, a)
         if tuple(a.shape) != tuple(shape):
             raise IlqgError("%s: %s has shape %s, expected %s" % (who, what, tuple(a.shape), tuple(shape)))
         a = np.ascontiguousarray(a)
@@ -309,12 +286,27 @@ def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant,
     r, n = max(int(rounds), 0), max(int(rounds), 0) * max(int(steps), 0)
     xp = None if x_plant is None else _plant_array(x_plant, (B, nx), "x_plant").copy()
     dist = None if disturbance is None else _plant_array(disturbance, (B, n, nx), "disturbance")
-    names, values = (None, None) if params is None else _plant_param_rows(solver.problem, params, B)
+    if params is not None and (not isinstance(params, dict) or not params):
+        raise IlqgError("receding_plant: params must be a non-empty dict of parameter name -> array [B, size], or None for a plant that is the model")
+    names, values, _ = (None, None, 0) if params is None else _pack_arrays("receding_plant", solver.problem, params, ((B,),), "planner and plant",
+                                                                           column=_plant_numbers)
     out = dict(x=np.zeros((B, n, nx)), u=np.zeros((B, n, nu)), cost=np.zeros((B, r)), plan_cost=np.zeros((B, r)), ok=np.zeros(B, dtype=np.int32),
                x_plant=xp)
     solver._ck(_receding_entry(solver.lib, entry)(solver.h, int(rounds), int(steps), int(iterations), 1 if feedback else 0, _address(xp),
                                                   0 if names is None else len(names), names, _address(values), _address(dist),
                                                   *[_address(out[k]) for k in ("x", "u", "cost", "plan_cost", "ok")]))
+    return out
+
+
+def _policy_rollout(solver, entry, x0, alpha, feedback, trajectories, params):
+    """BatchSolver.policy_rollout / MultiSolver.policy_rollout in host memory: the checks, the arrays and the one library call"""
+    x0 = _policy_starts(x0, solver.B, solver.problem.nx)
+    R, named = x0.shape[1], ()
+    out, ptr = _rollout_outputs(solver, R, trajectories)
+    if params is not None:
+        names, values, shared = _rollout_params(solver, params, R)
+        entry, named = entry + "_params", (len(names), names, _address(values), shared)
+    solver._ck(_receding_entry(solver.lib, entry)(solver.h, R, _address(x0), *named, float(alpha), 1 if feedback else 0, *ptr))
     return out
 
 
@@ -351,13 +343,15 @@ def _share_hip_runtime():
             pass
 
 
-def _torch_on_gpu():
-    """torch, for the device forms of head() / shift(): imported here and nowhere else"""
+def _torch_stream(device):
+    """(torch, the solver's GPU as torch names it, torch's current stream there as the library takes it) for the device
+    forms: torch is imported here and nowhere else"""
     import torch
     if not torch.cuda.is_available():
         raise IlqgError("torch sees no GPU in this process: torch and the solver must share one HIP runtime, which they do "
                         "when torch is first imported after the first solver has been made (see ilqg._share_hip_runtime)")
-    return torch
+    dev = torch.device("cuda", device)
+    return torch, dev, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)
 
 
 def load_library(problem="carparking", full_ddp=0, strict=False):
@@ -557,18 +551,16 @@ class BatchSolver:
         if not params:
             self._ck(_receding_entry(self.lib, "ilqg_batch_set_params_batch")(self.h, 0, None, None))
             return
+        args = ("set_params_batch", self.problem, params, ((self.B,),), "all trajectories")
         if not device:
-            names, values = _params_batch_rows(self.problem, params, self.B)
+            names, values, _ = _pack_arrays(*args)
             self._ck(_receding_entry(self.lib, "ilqg_batch_set_params_batch")(self.h, len(names), names, _address(values)))
             return
-        cols = _params_batch_tensors(self.problem, params, self.B, self.device)
+        names, cols, _ = _pack_tensors(*args, self.device)
         entry = _receding_entry(self.lib, "ilqg_batch_set_params_batch_device")
-        torch = _torch_on_gpu()
-        dev = torch.device("cuda", self.device)
-        with torch.cuda.device(dev):  # (a single tensor is the table as it lies: [B] and [B, 1] are the same memory)
-            values = cols[0][0] if len(cols) == 1 else torch.cat([a.reshape(shape) for a, shape in cols], dim=-1)
-        names = _policy_param_names(params)
-        self._ck(entry(self.h, len(names), names, C.c_void_p(values.data_ptr() or None), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+        torch, dev, stream = _torch_stream(self.device)
+        ptr, keep = _tensor_table(torch, dev, cols)
+        self._ck(entry(self.h, len(names), names, ptr, stream))
 
     def params_batch(self, name):
         """[B,size]: what trajectory b sees of fixed-size parameter `name` (ilqg_batch_get_params_batch) — its row of
@@ -596,8 +588,7 @@ class BatchSolver:
             self._ck(_receding_entry(self.lib, "ilqg_batch_set_param_steps_batch")(self.h, cname, ptr))
             return
         entry = _receding_entry(self.lib, "ilqg_batch_set_param_steps_batch_device")
-        torch = _torch_on_gpu()
-        self._ck(entry(self.h, cname, ptr, C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream or None)))
+        self._ck(entry(self.h, cname, ptr, _torch_stream(self.device)[2]))
 
     def param_steps_batch(self, name):
         """[B, n_hor+1]: what trajectory b sees of per-time-step parameter `name` (ilqg_batch_get_param_steps_batch) — its
@@ -623,8 +614,7 @@ class BatchSolver:
             self._ck(_receding_entry(self.lib, "ilqg_batch_shift_param_batch")(self.h, cname, int(steps), ptr))
             return
         entry = _receding_entry(self.lib, "ilqg_batch_shift_param_batch_device")
-        torch = _torch_on_gpu()
-        self._ck(entry(self.h, cname, int(steps), ptr, C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream or None)))
+        self._ck(entry(self.h, cname, int(steps), ptr, _torch_stream(self.device)[2]))
 
     def init(self, x0, u0):
         """x0 [B,nx], u0 [B,N,nu]: initial roll-out (clamps u) and solver entry state"""
@@ -654,9 +644,7 @@ class BatchSolver:
                     raise IlqgError("shift: %s is in host memory and the other argument on the device: pass both the same way" % what)
             px, pt = _cuda_address(x0, (self.B, nx), self.device, "x0"), _cuda_address(u_tail, (self.B, n, nu), self.device, "u_tail")
             entry = _receding_entry(self.lib, "ilqg_batch_shift_device")
-            torch = _torch_on_gpu()
-            stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-            self._ck(entry(self.h, int(steps), px, pt, C.c_void_p(stream or None)))
+            self._ck(entry(self.h, int(steps), px, pt, _torch_stream(self.device)[2]))
             return
         x0, u_tail = _optional(x0, (self.B, nx)), _optional(u_tail, (self.B, n, nu))
         self._ck(_receding_entry(self.lib, "ilqg_batch_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
@@ -667,20 +655,14 @@ class BatchSolver:
         L [B,steps,nu*nx] (each step column-major, as gains()).  numpy arrays (ilqg_batch_head), or with device=True
         float64 torch tensors on the solver's GPU, filled in the order of torch's current stream without a host wait
         (ilqg_batch_head_device)."""
-        nx, nu = self.problem.nx, self.problem.nu
         if not device:
-            out = _head_arrays(self.B, steps, nx, nu, gains)
-            self._ck(_receding_entry(self.lib, "ilqg_batch_head")(self.h, int(steps), *[_address(out.get(k)) for k in ("x", "u", "l", "L", "cost")]))
+            out, ptr = _head_outputs(self, steps, gains)
+            self._ck(_receding_entry(self.lib, "ilqg_batch_head")(self.h, int(steps), *ptr))
             return out
         entry = _receding_entry(self.lib, "ilqg_batch_head_device")
-        torch = _torch_on_gpu()
-        dev, n = torch.device("cuda", self.device), max(int(steps), 0)
-        shapes = dict(x=(self.B, n, nx), u=(self.B, n, nu), cost=(self.B,))
-        if gains:
-            shapes.update(l=(self.B, n, nu), L=(self.B, n, nu * nx))
-        out = {k: torch.empty(shape, dtype=torch.float64, device=dev) for k, shape in shapes.items()}
-        ptr = [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in ("x", "u", "l", "L", "cost")]
-        self._ck(entry(self.h, int(steps), *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+        torch, dev, stream = _torch_stream(self.device)
+        out, ptr = _head_outputs(self, steps, gains, torch, dev)
+        self._ck(entry(self.h, int(steps), *ptr, stream))
         return out
 
     def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False, params=None):
@@ -698,24 +680,11 @@ class BatchSolver:
         its gains were computed under the batch's parameters.  Per-time-step parameters stay shared and cannot be named;
         the batch's parameters do not change.  With device=True contiguous float64 torch tensors on the solver's GPU,
         packed with torch.cat on torch's current stream (a single tensor is read where it is)."""
-        nx, nu, B, N = self.problem.nx, self.problem.nu, self.B, self.N
-        order = ("cost", "ok", "x_end", "x", "u")
+        nx, B, named = self.problem.nx, self.B, ()
         if not device:
             if _is_cuda(x0):
                 raise IlqgError("policy_rollout: x0 is a tensor on the device: pass device=True")
-            x0 = _policy_starts(x0, B, nx)
-            R = x0.shape[1]
-            out = dict(cost=np.zeros((B, R)), ok=np.zeros((B, R), dtype=np.int32), x_end=np.zeros((B, R, nx)))
-            if trajectories:
-                out.update(x=np.zeros((B, R, N + 1, nx)), u=np.zeros((B, R, N, nu)))
-            if params is not None:
-                names, values, shared = _policy_param_rows(self.problem, params, B, R)
-                self._ck(_receding_entry(self.lib, "ilqg_batch_policy_rollout_params")(self.h, R, _address(x0), len(names), names, _address(values), shared,
-                                                                                       float(alpha), 1 if feedback else 0, *[_address(out.get(k)) for k in order]))
-                return out
-            self._ck(_receding_entry(self.lib, "ilqg_batch_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
-                                                                            *[_address(out.get(k)) for k in order]))
-            return out
+            return _policy_rollout(self, "ilqg_batch_policy_rollout", x0, alpha, feedback, trajectories, params)
         if not _is_cuda(x0):
             raise IlqgError("policy_rollout: device=True and x0 is in host memory: pass a float64 torch tensor on the solver's GPU")
         if len(x0.shape) != 3 or int(x0.shape[1]) < 1:
@@ -723,23 +692,14 @@ class BatchSolver:
         R = int(x0.shape[1])
         px = _cuda_address(x0, (B, R, nx), self.device, "x0")
         if params is not None:
-            cols, shared = _policy_param_tensors(self.problem, params, B, R, self.device)
+            names, cols, shared = _rollout_params(self, params, R, self.device)
         entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_device" if params is None else "ilqg_batch_policy_rollout_params_device")
-        torch = _torch_on_gpu()
-        dev = torch.device("cuda", self.device)
-        out = dict(cost=torch.empty((B, R), dtype=torch.float64, device=dev), ok=torch.empty((B, R), dtype=torch.int32, device=dev),
-                   x_end=torch.empty((B, R, nx), dtype=torch.float64, device=dev))
-        if trajectories:
-            out.update(x=torch.empty((B, R, N + 1, nx), dtype=torch.float64, device=dev), u=torch.empty((B, R, N, nu), dtype=torch.float64, device=dev))
-        ptr = [C.c_void_p(out[k].data_ptr() or None) if k in out else None for k in order]
+        torch, dev, stream = _torch_stream(self.device)
+        out, ptr = _rollout_outputs(self, R, trajectories, torch, dev)
         if params is not None:
-            with torch.cuda.device(dev):  # (a single tensor is the table as it lies: [B, R] and [B, R, 1] are the same memory)
-                values = cols[0][0] if len(cols) == 1 else torch.cat([a.reshape(shape) for a, shape in cols], dim=-1)
-            names = _policy_param_names(params)
-            self._ck(entry(self.h, R, px, len(names), names, C.c_void_p(values.data_ptr() or None), shared, float(alpha), 1 if feedback else 0, *ptr,
-                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
-            return out
-        self._ck(entry(self.h, R, px, float(alpha), 1 if feedback else 0, *ptr, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream or None)))
+            values, keep = _tensor_table(torch, dev, cols)
+            named = (len(names), names, values, shared)
+        self._ck(entry(self.h, R, px, *named, float(alpha), 1 if feedback else 0, *ptr, stream))
         return out
 
     def shift_param(self, name, steps, tail=None):
@@ -1010,7 +970,7 @@ class MultiSolver:
         if not params:
             self._ck(entry(self.h, 0, None, None))
             return
-        names, values = _params_batch_rows(self.problem, params, self.B)
+        names, values, _ = _pack_arrays("set_params_batch", self.problem, params, ((self.B,),), "all trajectories")
         self._ck(entry(self.h, len(names), names, _address(values)))
 
     def set_param_steps_batch(self, name, values):
@@ -1035,28 +995,14 @@ class MultiSolver:
 
     def head(self, steps, gains=False):
         """BatchSolver.head of every shard (ilqg_multi_head), numpy arrays"""
-        out = _head_arrays(self.B, steps, self.problem.nx, self.problem.nu, gains)
-        self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *[_address(out.get(k)) for k in ("x", "u", "l", "L", "cost")]))
+        out, ptr = _head_outputs(self, steps, gains)
+        self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *ptr))
         return out
 
     def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, params=None):
         """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout, with params ilqg_multi_policy_rollout_params),
         numpy arrays"""
-        nx, nu, B, N = self.problem.nx, self.problem.nu, self.B, self.N
-        x0 = _policy_starts(x0, B, nx)
-        R = x0.shape[1]
-        out = dict(cost=np.zeros((B, R)), ok=np.zeros((B, R), dtype=np.int32), x_end=np.zeros((B, R, nx)))
-        if trajectories:
-            out.update(x=np.zeros((B, R, N + 1, nx)), u=np.zeros((B, R, N, nu)))
-        if params is not None:
-            names, values, shared = _policy_param_rows(self.problem, params, B, R)
-            self._ck(_receding_entry(self.lib, "ilqg_multi_policy_rollout_params")(self.h, R, _address(x0), len(names), names, _address(values), shared,
-                                                                                   float(alpha), 1 if feedback else 0,
-                                                                                   *[_address(out.get(k)) for k in ("cost", "ok", "x_end", "x", "u")]))
-            return out
-        self._ck(_receding_entry(self.lib, "ilqg_multi_policy_rollout")(self.h, R, _address(x0), float(alpha), 1 if feedback else 0,
-                                                                        *[_address(out.get(k)) for k in ("cost", "ok", "x_end", "x", "u")]))
-        return out
+        return _policy_rollout(self, "ilqg_multi_policy_rollout", x0, alpha, feedback, trajectories, params)
 
     def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None):
         """BatchSolver.receding_plant of every shard, one shard after the other (ilqg_multi_receding_plant), numpy arrays"""

@@ -16,7 +16,7 @@ from param_steps_cases import BUILDS, SLOTS, STEP_NAME, B, StepCase, dict_of, or
 from params_batch_cases import rows as fixed_rows
 from policy_cases import perturbed_starts, reference_rollout
 from policy_param_cases import draws, params_of
-from test_gpu_params_batch import close_inf, launches, states_equal
+from test_gpu_params_batch import close_inf, launches, refused, states_equal
 from test_gpu_policy_rollout import close, ilqg, torch, worst  # noqa: F401 (fixtures)
 from test_gpu_receding_plant import full_state
 
@@ -397,17 +397,6 @@ def test_a_nan_in_one_row_fails_its_own_slot_only(ilqg):
 # ---------------------------------------------------------------------------
 # 10. refusals: the error text, an untouched batch, no launch
 # ---------------------------------------------------------------------------
-def refused(ilqg, s, call, words):
-    before = full_state(s)
-    s.timing(True)
-    n = launches(s)
-    with pytest.raises(ilqg.IlqgError) as e:
-        call()
-    assert all(w in str(e.value) for w in words), str(e.value)
-    assert launches(s) == n, "a refused call launched a kernel"
-    states_equal(full_state(s), before, "a refused call changed the batch")
-
-
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
