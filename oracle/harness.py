@@ -143,6 +143,8 @@ def lib_path(kind, problem="carparking", full_ddp=0):
     stand-in, no generated file)"""
     if kind == "pure":
         return os.path.join(HERE, "_ref", "libref_pure.so")
+    if kind == "ref_contract":  # the reference sources as 'ref' builds them but with FMA contraction (synth10hx FULL_DDP=1 only)
+        return os.path.join(HERE, "_ref", "libref_%s_fd%d_contract.so" % (problem, full_ddp))
     if kind == "ref_fma":
         return os.path.join(HERE, "_ref", "libref_%s_fd%d_fma.so" % (problem, full_ddp))
     if kind == "ref":

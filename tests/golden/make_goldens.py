@@ -475,8 +475,20 @@ def vsref_goldens():
     np.savez_compressed(os.path.join(HERE, "oracle_vs_ref.npz"), **out)
 
 
+def regtype2_case_goldens():
+    """tests/regtype2_cases.py: the reference build's sweeps under regType 2 on every line of that module's TABLE (start
+    state, rc, value changes, gradient norm, completed steps and their gains), collected by the module's own functions"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import regtype2_cases as R
+    with quiet():
+        out = R.golden_of("ref")
+    np.savez_compressed(R.GOLDEN, **out)
+    print("regType 2 cases: %d lines, %d bytes" % (len(R.TABLE), os.path.getsize(R.GOLDEN)))
+
+
 def main(argv):
-    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 synth synthp console vsref"""
+    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases synth synthp console
+    vsref"""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     groups = {
         "brachi": brachi_goldens,
@@ -486,6 +498,7 @@ def main(argv):
         "lockstep": lambda: lockstep_goldens(0),
         "hx": lambda: [hx_goldens(fd) for fd in (0, 1)],
         "regtype2": regtype2_goldens,
+        "regtype2cases": regtype2_case_goldens,
         "synth": lambda: [synth_goldens(fd) for fd in (0, 1)],
         "synthp": lambda: synth_goldens(1, N=12, problem="synth16p", SYN_PARAMS=SYNP_PARAMS_TIGHT),
         "console": console_goldens,

@@ -650,6 +650,8 @@ def check_hxtest_golden(ilqg, problem, fd):
 
 @pytest.mark.parametrize("fd", [0, 1])
 def test_regtype2_golden(ilqg, fd):
+    # (at FULL_DDP = 1 the reference abandons this sweep — fd1_rc == 1 — and only the return code is compared here: the
+    # gains of completed and of abandoned regType-2 sweeps, in every mapping, are held by tests/test_gpu_regtype2.py)
     g = golden("car_regtype2.npz")
     s = ilqg.BatchSolver("carparking", fd, batch=1, n_hor=500, params=ilqg.CAR_PARAMS, opts=dict(regType=2))
     s.init(g["x0"][None], g["u0"][None])
