@@ -931,6 +931,30 @@ struct ParamValues {
 struct ParamTable {
     double *ptr[ILQG_NP + ILQG_HOOK_SLOTS];  // the problem's parameters, then the hooks (see ilqg_hooks)
 };
+//
+// VECTOR = true: the copies are made lane values (an empty asm statement the optimiser cannot look through), i.e. they
+// live in vector registers as the rows of a per-trajectory table do (trajectory_params).  The shared lane-mapped sweep and
+// searches hold more wave-uniform values than there are scalar registers; what does not fit travels through
+// v_writelane / v_readlane — vector instructions with wait states, inside the step loops — while vector registers are
+// to spare there.  Per kernel, where that kernel's launch time gained by it (profiles/r14_vector_params.txt), and only for
+// a problem with few parameter doubles: each costs two vector registers.  -DILQG_VECTOR_PARAMS=0: scalar everywhere, as before.
+#ifndef ILQG_VECTOR_PARAMS
+#define ILQG_VECTOR_PARAMS 1
+#endif
+#ifndef ILQG_VECTOR_PARAMS_MAX  // parameter doubles up to which a kernel may hold them per lane (CarParking: 20)
+#define ILQG_VECTOR_PARAMS_MAX 24
+#endif
+#ifndef ILQG_VECTOR_PARAMS_BACKWARD  // k_backward<2>
+#define ILQG_VECTOR_PARAMS_BACKWARD 1
+#endif
+#ifndef ILQG_VECTOR_PARAMS_SEARCH0  // k_search<0, true>
+#define ILQG_VECTOR_PARAMS_SEARCH0 1
+#endif
+#ifndef ILQG_VECTOR_PARAMS_SEARCH1  // k_search<1, true>
+#define ILQG_VECTOR_PARAMS_SEARCH1 1
+#endif
+constexpr bool VECTOR_PARAMS = ILQG_VECTOR_PARAMS && !ILQG_WAVE_MAP && ILQG_PTOTAL <= ILQG_VECTOR_PARAMS_MAX;
+template <bool VECTOR = false>
 __device__ __forceinline__ void load_params(ParamValues &V, ParamTable &T, ilqg_hooks &H, const ParamValues &A,
                                             double **p) {
     constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
@@ -939,7 +963,11 @@ __device__ __forceinline__ void load_params(ParamValues &V, ParamTable &T, ilqg_
     for(int i = 0; i < ILQG_NP; i++) {
         if(sizes[i] > 0) {
 #pragma unroll
-            for(int j = 0; j < sizes[i]; j++) V.v[offs[i] + j] = A.v[offs[i] + j];
+            for(int j = 0; j < sizes[i]; j++) {
+                double v = A.v[offs[i] + j];
+                if(VECTOR) asm volatile("" : "+v"(v));
+                V.v[offs[i] + j] = v;
+            }
             T.ptr[i] = &V.v[offs[i]];
         } else {
             T.ptr[i] = p[i];
@@ -966,9 +994,10 @@ struct Callbacks {
     tOptSet o;   // what the callbacks see as `o` (p, n_hor, penalty weights)
     tOptSet o1;  // the same with n_hor = 1: init_running loops over n_hor elements
 };
+template <bool VECTOR = false>
 __device__ __forceinline__ void make_callbacks(Callbacks &C, ParamTable &T, ParamValues &V, ilqg_hooks &H,
                                                const DevPtrs &P, const ilqg_dev_opts_t &O, const ParamValues &A) {
-    load_params(V, T, H, A, P.p);
+    load_params<VECTOR>(V, T, H, A, P.p);
     tOptSet &o = C.o;
     o.p = T.ptr;
     o.n_hor = P.N;
@@ -997,12 +1026,14 @@ __device__ __forceinline__ void load_penalty_weights_der(Callbacks &C, const Dev
     if(HAS_MUL) set_penalty_weights(C, P.f[ILQG_F_WPEN_L_DER][b], P.f[ILQG_F_WPEN_F_DER][b]);
 }
 // declares the callback context C and the lane's hooks H of a kernel with arguments (P, O, A)
-#define ILQG_CALLBACKS(C, H) \
-    ParamValues C##_values;  \
-    ParamTable C##_table;    \
-    ilqg_hooks H;            \
-    Callbacks C;             \
-    make_callbacks(C, C##_table, C##_values, H, P, O, A)
+#define ILQG_CALLBACKS(C, H) ILQG_CALLBACKS_IN(C, H, false)
+// the same with the fixed-size parameters in vector registers where VECTOR_ holds (see load_params)
+#define ILQG_CALLBACKS_IN(C, H, VECTOR_) \
+    ParamValues C##_values;              \
+    ParamTable C##_table;                \
+    ilqg_hooks H;                        \
+    Callbacks C;                         \
+    make_callbacks<(VECTOR_)>(C, C##_table, C##_values, H, P, O, A)
 
 // ---------------------------------------------------------------------------
 // host layout [b][k][f]  <->  device layout [k][b/64][f][b%64] of the lane mapping (the wave mapping's

@@ -407,7 +407,8 @@ __global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P,
         P.i[ILQG_I_STATUS][b] = ILQG_ST_DERIVS_FAILED;
         return;
     }
-    ILQG_CALLBACKS(C, H);
+    // (the shared fused sweep: parameters per lane, where measured faster — load_params)
+    ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && mode == 2 && ILQG_VECTOR_PARAMS_BACKWARD);
     if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
     load_penalty_weights_der(C, P, b);
     double lambda = P.f[ILQG_F_LAMBDA][b], dlambda = P.f[ILQG_F_DLAMBDA][b];

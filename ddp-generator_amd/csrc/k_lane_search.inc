@@ -59,7 +59,8 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
     const double alpha = O.alpha[ai];
     const bool feedback = (alpha != 0.0);  // alpha == 0.0: u = u_nom without feedback (iLQG_func.tem:156-158)
 
-    ILQG_CALLBACKS(C, H);
+    // (the shared kernels with the records through LDS: parameters per lane, where measured faster — load_params)
+    ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && DMA && (stage ? ILQG_VECTOR_PARAMS_SEARCH1 : ILQG_VECTOR_PARAMS_SEARCH0));
     // (b = pending[ee] or ee: lanes beyond the end repeat the last entry, and read its row)
     if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
     load_penalty_weights(C, P, b);
