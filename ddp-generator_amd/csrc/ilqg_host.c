@@ -600,20 +600,116 @@ static int no_step_params(ilqg_batch_t *c, const char *who) {
     return 0;
 }
 
-static int iterate_groups(ilqg_batch_t *c, int n);
-int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, double *x_applied, double *u_applied, double *cost) {
-    int g, r;
-    if(rounds < 1 || iterations < 0) return fail_msg(c, "ilqg_batch_receding: need rounds >= 1 and iterations >= 0");
-    if(steps < 1 || steps >= c->N) {
-        snprintf(c->err, sizeof(c->err), "ilqg_batch_receding: steps = %d, must be in 1 .. n_hor - 1 = %d", steps, c->N - 1);
+/* The windows of the resident loops (ilqg_batch_receding_windows, ilqg_batch_receding_plant_windows).  window_names resolves
+ * the caller's names to per-time-step parameters and makes every refusal, before a group is touched: by_param[i] = the future
+ * of parameter i of paramdesc[], NULL for a parameter that is not named or whose window holds its last value. */
+#define WINDOW_MAX_PARAMS 64 /* as many as push_config allows parameters */
+static int window_names(ilqg_batch_t *c, const char *who, int n_windows, const char *const *names, const double *const *future,
+                        const double **by_param) {
+    int i, j, k, any = 0, taken[WINDOW_MAX_PARAMS];
+    for(i = 0; i < WINDOW_MAX_PARAMS; i++) by_param[i] = NULL;
+    if(n_windows < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: n_windows = %d, must not be negative (0: every window holds its last value)", who, n_windows);
         return 1;
     }
-    if(no_step_params(c, "ilqg_batch_receding")) return 1;
+    if(n_windows == 0) return 0;
+    if(!names) {
+        snprintf(c->err, sizeof(c->err), "%s: window_names is NULL (n_windows parameter names)", who);
+        return 1;
+    }
+    if(!future) {
+        snprintf(c->err, sizeof(c->err), "%s: future is NULL (n_windows pointers, each the values beyond a window or NULL)", who);
+        return 1;
+    }
+    for(i = 0; i < n_params; i++) any |= paramdesc[i]->size == -1;
+    if(!any) {
+        snprintf(c->err, sizeof(c->err), "%s: n_windows = %d, but this problem has no parameter with one value per time step (size -1): "
+                 "there is no window to move, n_windows must be 0", who, n_windows);
+        return 1;
+    }
+    for(i = 0; i < n_windows; i++) {
+        if(i >= WINDOW_MAX_PARAMS) {
+            snprintf(c->err, sizeof(c->err), "%s: n_windows = %d, more than %d names", who, n_windows, WINDOW_MAX_PARAMS);
+            return 1;
+        }
+        if(!names[i]) {
+            snprintf(c->err, sizeof(c->err), "%s: window_names[%d] is NULL", who, i);
+            return 1;
+        }
+        k = find_param(names[i]);
+        if(k < 0) {
+            snprintf(c->err, sizeof(c->err), "%s: window_names[%d]: Parameter name '%s' is not member of parameters struct.", who, i, names[i]);
+            return 1;
+        }
+        if(paramdesc[k]->size != -1) {
+            snprintf(c->err, sizeof(c->err), "%s: window_names[%d]: parameter '%s' has a fixed size of %d, not one value per time step "
+                     "(size -1): it has no window to move", who, i, names[i], paramdesc[k]->size);
+            return 1;
+        }
+        if(k >= WINDOW_MAX_PARAMS) {
+            snprintf(c->err, sizeof(c->err), "%s: window_names[%d]: more than %d problem parameters", who, i, WINDOW_MAX_PARAMS);
+            return 1;
+        }
+        for(j = 0; j < i; j++)
+            if(taken[j] == k) {
+                snprintf(c->err, sizeof(c->err), "%s: window_names[%d]: parameter '%s' is named twice (a duplicate of window_names[%d])", who, i,
+                         names[i], j);
+                return 1;
+            }
+        taken[i] = k;
+        by_param[k] = future[i];
+    }
+    return 0;
+}
+/* the futures go up once, every group its rows of a parameter that has rows (ilqg_dev_windows_begin) */
+static int windows_begin(ilqg_batch_t *c, const char *who, int rounds, int steps, const double *const *by_param) {
+    const size_t per = (size_t)rounds * (size_t)steps;
+    const double *of_group[WINDOW_MAX_PARAMS];
+    int g, i;
+    EACH_GROUP(g) {
+        for(i = 0; i < WINDOW_MAX_PARAMS; i++) of_group[i] = (by_param[i] && c->ps_on[i]) ? by_param[i] + (size_t)c->first[g] * per : by_param[i];
+        if(ilqg_dev_windows_begin(c->dev[g], rounds, steps, of_group)) return fail(c, who);
+    }
+    return 0;
+}
+/* round r: every window moves `steps` on, on the device in one launch per group, and the host mirror of a shared window with
+ * it (a later ilqg_batch_set_param of another parameter re-pushes from that mirror) */
+static int windows_move(ilqg_batch_t *c, const char *who, int r, int steps, const double *const *by_param) {
+    int g, i, k;
+    const int n = c->N + 1;
+    EACH_GROUP(g) if(ilqg_dev_windows_move(c->dev[g], r)) return fail(c, who);
+    for(i = 0; i < n_params && i < WINDOW_MAX_PARAMS; i++)
+        if(paramdesc[i]->size == -1 && !c->ps_on[i]) {
+            const double *tail = by_param[i] ? by_param[i] + (size_t)r * (size_t)steps : NULL;
+            for(k = 0; k < n; k++) c->p[i][k] = k + steps < n ? c->p[i][k + steps] : (tail ? tail[k + steps - n] : c->p[i][n - 1]);
+        }
+    return 0;
+}
+
+static int iterate_groups(ilqg_batch_t *c, int n);
+/* ilqg_batch_receding (windowed = 0: a per-time-step problem is refused) and ilqg_batch_receding_windows */
+static int receding(ilqg_batch_t *c, const char *who, int windowed, int rounds, int steps, int iterations, int n_windows,
+                    const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied, double *cost) {
+    const double *by_param[WINDOW_MAX_PARAMS];
+    int g, r;
+    if(rounds < 1 || iterations < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: need rounds >= 1 and iterations >= 0", who);
+        return 1;
+    }
+    if(steps < 1 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", who, steps, c->N - 1);
+        return 1;
+    }
+    if(!windowed && no_step_params(c, who)) return 1;
+    if(windowed && window_names(c, who, n_windows, window_names_, future, by_param)) return 1;
     if(push_config(c)) return 1;
     EACH_GROUP(g) if(ilqg_dev_log_begin(c->dev[g], rounds, steps)) return fail(c, "receding: log");
+    if(windowed && windows_begin(c, "receding: windows", rounds, steps, by_param)) return 1;
     for(r = 0; r < rounds; r++) {
         if(iterate_groups(c, iterations)) return 1;
         EACH_GROUP(g) if(ilqg_dev_log_append(c->dev[g], r)) return fail(c, "receding: log");
+        /* the windows move before the shift: its initial roll-out reads them */
+        if(windowed && windows_move(c, "receding: windows", r, steps, by_param)) return 1;
         if(ilqg_batch_shift(c, steps, NULL, NULL)) return 1;
     }
     EACH_GROUP(g) {
@@ -623,6 +719,16 @@ int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, 
             return fail(c, "receding: log");
     }
     return 0;
+}
+
+int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, double *x_applied, double *u_applied, double *cost) {
+    return receding(c, "ilqg_batch_receding", 0, rounds, steps, iterations, 0, NULL, NULL, x_applied, u_applied, cost);
+}
+
+int ilqg_batch_receding_windows(ilqg_batch_t *c, int rounds, int steps, int iterations, int n_windows, const char *const *window_names_,
+                                const double *const *future, double *x_applied, double *u_applied, double *cost) {
+    if(!c) return 1;
+    return receding(c, "ilqg_batch_receding_windows", 1, rounds, steps, iterations, n_windows, window_names_, future, x_applied, u_applied, cost);
 }
 
 /* The control interval of a caller with its own plant: {iterate; head; the caller's plant step; shift}.  The heads are read
@@ -981,10 +1087,11 @@ int ilqg_batch_shift_param_batch_device(ilqg_batch_t *c, const char *name, int s
  * `steps` steps from their own states under the plans' policies and the plants' parameters; the plans shift and start again
  * from the plants' states }.  Everything is refused before anything is launched or allocated; values, disturbance and
  * x_plant go up once (ilqg_dev_plant_begin), the logs come down once (ilqg_dev_plant_read), and nothing waits in between. */
-int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
-                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
-                              double *cost_applied, double *plan_cost, int *ok) {
-    static const char who[] = "ilqg_batch_receding_plant";
+static int receding_plant(ilqg_batch_t *c, const char *who, int windowed, int rounds, int steps, int iterations, int feedback, double *x_plant,
+                          int n_names, const char *const *names, const double *values, const double *disturbance, int n_windows,
+                          const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
+                          double *cost_applied, double *plan_cost, int *ok) {
+    const double *by_param[WINDOW_MAX_PARAMS];
     int g, r, named[POLICY_MAX_NAMES], W = 0;
     if(rounds < 1) {
         snprintf(c->err, sizeof(c->err), "%s: rounds = %d, must be at least 1", who, rounds);
@@ -998,12 +1105,13 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
         snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", who, steps, c->N - 1);
         return 1;
     }
-    if(no_step_params(c, who)) return 1;
+    if(!windowed && no_step_params(c, who)) return 1;
     if(n_names < 0) {
         snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0: the plant is the model)", who, n_names);
         return 1;
     }
     if(n_names > 0 && policy_names(c, who, n_names, names, values, named, &W)) return 1;
+    if(windowed && window_names(c, who, n_windows, window_names_, future, by_param)) return 1;
     if(push_config(c)) return 1;
     {
         const size_t per = (size_t)rounds * (size_t)steps;
@@ -1013,10 +1121,13 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
                                     n_names > 0 ? values + first * (size_t)W : NULL, disturbance ? disturbance + first * per * N_X : NULL))
                 return fail(c, "receding_plant");
         }
+        if(windowed && windows_begin(c, "receding_plant: windows", rounds, steps, by_param)) return 1;
         for(r = 0; r < rounds; r++) {
             if(iterate_groups(c, iterations)) return 1;
             /* the plants read the plans the shift moves: k_plant is enqueued in front of k_shift_* on every group's stream */
             EACH_GROUP(g) if(ilqg_dev_plant_advance(c->dev[g], r, feedback)) return fail(c, "receding_plant: plant");
+            /* the plants have read the round's windows where they stood; they move before the shift, whose initial roll-out reads them */
+            if(windowed && windows_move(c, "receding_plant: windows", r, steps, by_param)) return 1;
             /* ilqg_batch_shift(c, steps, x0_new = the plants' states, NULL), the states being on the device already */
             EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, 0)) return fail(c, "shift");
             EACH_GROUP(g) if(ilqg_dev_plant_put_x0(c->dev[g])) return fail(c, "shift: x0_new");
@@ -1031,6 +1142,22 @@ int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterat
         }
     }
     return 0;
+}
+
+int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
+                              double *cost_applied, double *plan_cost, int *ok) {
+    return receding_plant(c, "ilqg_batch_receding_plant", 0, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, 0,
+                          NULL, NULL, x_applied, u_applied, cost_applied, plan_cost, ok);
+}
+
+int ilqg_batch_receding_plant_windows(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                                      const char *const *names, const double *values, const double *disturbance, int n_windows,
+                                      const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
+                                      double *cost_applied, double *plan_cost, int *ok) {
+    if(!c) return 1;
+    return receding_plant(c, "ilqg_batch_receding_plant_windows", 1, rounds, steps, iterations, feedback, x_plant, n_names, names, values,
+                          disturbance, n_windows, window_names_, future, x_applied, u_applied, cost_applied, plan_cost, ok);
 }
 
 /* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param), and in the host
@@ -2113,6 +2240,34 @@ int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterat
                                      values ? values + at * W : NULL, disturbance ? disturbance + at * per * N_X : NULL,
                                      x_applied ? x_applied + at * per * N_X : NULL, u_applied ? u_applied + at * per * N_U : NULL,
                                      cost_applied ? cost_applied + at * rn : NULL, plan_cost ? plan_cost + at * rn : NULL, ok ? ok + at : NULL))
+            return multi_fail(m, g);
+    }
+    return 0;
+}
+/* ilqg_batch_receding_plant_windows per shard.  A future is offset by the shard's first trajectory where its name has rows in the
+ * shard; what the shard would refuse (a name that is no per-time-step parameter, too many names) passes as it is, and the
+ * shard refuses */
+int ilqg_multi_receding_plant_windows(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                                      const char *const *names, const double *values, const double *disturbance, int n_windows,
+                                      const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
+                                      double *cost_applied, double *plan_cost, int *ok) {
+    const size_t W = values ? rows_width(n_names, names) : 0;
+    const size_t rn = rounds > 0 ? (size_t)rounds : 0, per = rn * (steps > 0 ? (size_t)steps : 0);
+    const double *of_shard[WINDOW_MAX_PARAMS];
+    const int offset = window_names_ && future && n_windows > 0 && n_windows <= WINDOW_MAX_PARAMS;
+    int g, i, k;
+    if(!m) return 1;
+    EACH_SHARD(g) {
+        const size_t at = (size_t)m->first[g];
+        for(i = 0; offset && i < n_windows; i++) {
+            k = window_names_[i] ? find_param(window_names_[i]) : -1;
+            of_shard[i] = (future[i] && k >= 0 && k < WINDOW_MAX_PARAMS && m->shard[g]->ps_on[k]) ? future[i] + at * per : future[i];
+        }
+        if(ilqg_batch_receding_plant_windows(m->shard[g], rounds, steps, iterations, feedback, x_plant ? x_plant + at * N_X : NULL, n_names, names,
+                                             values ? values + at * W : NULL, disturbance ? disturbance + at * per * N_X : NULL, n_windows,
+                                             window_names_, offset ? of_shard : future, x_applied ? x_applied + at * per * N_X : NULL,
+                                             u_applied ? u_applied + at * per * N_U : NULL, cost_applied ? cost_applied + at * rn : NULL,
+                                             plan_cost ? plan_cost + at * rn : NULL, ok ? ok + at : NULL))
             return multi_fail(m, g);
     }
     return 0;

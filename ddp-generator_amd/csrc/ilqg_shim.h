@@ -123,6 +123,7 @@ enum {
     ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout with a table) */
     ILQG_K_PLANT,    /* k_plant (ilqg_dev_plant_advance) */
     ILQG_K_SHIFT_PARAM_ROWS, /* k_shift_param_rows (ilqg_dev_shift_param_batch) */
+    ILQG_K_SHIFT_WINDOWS, /* k_shift_windows (ilqg_dev_windows_move) */
     ILQG_K_COUNT
 };
 
@@ -265,6 +266,18 @@ int ilqg_dev_check_device_ptr(ilqg_dev_t *d, const void *ptr, const char *what);
  * ilqg_dev_set_params marks them; no wave-mapped problem with such a parameter is built in this tree, so that path is
  * untested.) */
 int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail);
+/* The windows of a resident closed loop: `rounds` times { ...; ilqg_dev_windows_move(d, round); ilqg_dev_shift; ... } behind one
+ * ilqg_dev_windows_begin.  begin: future[i], i an index into paramdesc[] (n_params entries; those of fixed-size parameters
+ * are not read), is HOST memory holding the values beyond parameter i's window for the whole loop: [batch][rounds * steps]
+ * where the parameter has rows in this context (ilqg_dev_set_param_steps_batch), [rounds * steps] where it is the shared
+ * window, NULL: the window holds its last value, per row.  future itself may be NULL (every window holds).  The futures go up
+ * once, into buffers of the context that only grow; waits once.  rounds >= 1, 1 <= steps < n_hor.
+ * move: every size -1 parameter's window moves `steps` on, its tail columns [round * steps, (round + 1) * steps) of its
+ * future, in ONE launch (k_shift_windows) on the context's stream; waits for nothing, copies nothing.  Wave mapping: the
+ * constant record entries are marked stale as ilqg_dev_shift_param marks them.  A library whose problem has no per-time-step
+ * parameter launches nothing in either. */
+int ilqg_dev_windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *const *future);
+int ilqg_dev_windows_move(ilqg_dev_t *d, int round);
 int ilqg_dev_derivs(ilqg_dev_t *d);           /* calc_derivs for trajectories that need it */
 /* back_pass.  mode 0: records from HBM + lambda retry loop + gradient test; 1: records from HBM, one
  * sweep (drop-in back_pass()); 2: as 0 with the derivatives evaluated on the fly (no k_derivs needed) */

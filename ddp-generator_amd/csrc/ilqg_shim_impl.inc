@@ -101,6 +101,12 @@ struct ilqg_dev {
     double *sr_rows[SR];
     size_t sr_bytes[SR];
     bool sr_on[SR];
+    // the futures of a resident loop's windows (ilqg_dev_windows_begin): per slot the values beyond the window, [B][win_per] for
+    // a parameter with rows, [win_per] for the shared window; grow-only; win_given[s]: the slot has a future (else it holds)
+    double *win_future[SR];
+    size_t win_bytes[SR];
+    bool win_given[SR];
+    int win_rounds, win_steps;  // 0: no loop open
     // what LAUNCH_PV hands the rows twins: rows_on = pb_on or some sr_on; rows_map = pb_map (empty without a table) with the
     // step rows in use (rows_refresh, after every change of either set)
     bool rows_on;
@@ -396,7 +402,8 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_rollout[winner]", "k_update", "k_rollout[cost]", "k_rollout[init]",
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
-                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant", "k_shift_param_rows"};
+                                              "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant", "k_shift_param_rows",
+                                              "k_shift_windows"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -451,7 +458,11 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
         d->sr_rows[s] = nullptr;
         d->sr_bytes[s] = 0;
         d->sr_on[s] = false;
+        d->win_future[s] = nullptr;
+        d->win_bytes[s] = 0;
+        d->win_given[s] = false;
     }
+    d->win_rounds = d->win_steps = 0;
     d->rows_on = false;
     d->P.B = d->B;
     d->P.Bp = d->Bp;
@@ -670,6 +681,8 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
     if(d->pb_values) hipFree(d->pb_values);
     for(int s = 0; s < ilqg_dev::SR; s++)
         if(d->sr_rows[s]) hipFree(d->sr_rows[s]);
+    for(int s = 0; s < ilqg_dev::SR; s++)
+        if(d->win_future[s]) hipFree(d->win_future[s]);
     for(double *p : d->param_bufs) hipFree(p);
     if(d->P.p) hipFree(d->P.p);
     if(d->staging) hipFree(d->staging);
@@ -1731,6 +1744,87 @@ int ilqg_dev_shift_param_batch(ilqg_dev_t *d, int index, int steps, const double
     }
     HIP_TRY(hipGetLastError());
     return (tail && !on_device) ? io_done(d) : 0;
+}
+
+// The windows of a resident loop (ilqg_batch_receding_windows / _receding_plant_windows).  begin: the futures of the loop's
+// `rounds` rounds of `steps` steps go up ONCE, into buffers of the context that only grow; future[i], i an index into
+// paramdesc[], is host memory [B][rounds * steps] where parameter i has rows in this context, [rounds * steps] where it is the
+// shared window, or NULL: that window holds its last value, per row (entries of fixed-size parameters are not read).  Waits
+// once.  move: EVERY size -1 parameter's window moves `steps` on in one launch of k_shift_windows, its tail the columns of
+// round `round` of its future — on the context's stream: behind the log or the plant step of the round (both hand back to
+// it) and in front of ilqg_dev_shift and the initial roll-out that reads the moved windows.  A library without a per-time-step
+// parameter has nothing to move: both return 0 and launch nothing.
+static int slot_index(int s) {  // the paramdesc[] index of the s-th size -1 parameter
+    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
+    for(int i = 0; i < ILQG_NP; i++)
+        if(sizes[i] == -1 && s-- == 0) return i;
+    return -1;
+}
+}  // extern "C"
+// (templates on the slot count: the discarded branch, and with it the kernel, is not instantiated where there is no slot)
+template <int n_slots>
+static int windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *const *future) {
+    if constexpr(n_slots > 0) {
+        NEED_PARAMS(d);
+        const size_t per = (size_t)rounds * (size_t)steps;
+        bool sent = false;
+        for(int s = 0; s < n_slots; s++) {
+            const double *f = future ? future[slot_index(s)] : nullptr;
+            d->win_given[s] = f != nullptr;
+            if(!f) continue;
+            const size_t bytes = (d->sr_on[s] ? (size_t)d->B : (size_t)1) * per * sizeof(double);
+            if(ensure_buffer(d, &d->win_future[s], &d->win_bytes[s], bytes, d->stream)) return 1;
+            HIP_TRY(hipMemcpyAsync(d->win_future[s], f, bytes, hipMemcpyHostToDevice, d->stream));
+            sent = true;
+        }
+        if(sent) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
+    }
+    return 0;
+}
+template <int n_slots>
+static int windows_move(ilqg_dev_t *d, int round) {
+    if constexpr(n_slots > 0) {
+        NEED_PARAMS(d);
+        WindowSet<n_slots> S;
+        int most = 1;
+        for(int s = 0; s < n_slots; s++) {
+            const bool rows = d->sr_on[s];
+            S.w[s].base = rows ? d->sr_rows[s] : d->param_bufs[slot_index(s)];
+            S.w[s].rows = rows ? d->B : 1;
+            S.w[s].future = d->win_given[s] ? d->win_future[s] : nullptr;
+            S.w[s].stride = rows ? (size_t)d->win_rounds * (size_t)d->win_steps : 0;
+            if(S.w[s].rows > most) most = S.w[s].rows;
+        }
+        {
+            Timed t(d, ILQG_K_SHIFT_WINDOWS);
+            hipLaunchKernelGGL(k_shift_windows<n_slots>, dim3(most, n_slots), dim3(PARAM_BLOCK), 0, d->stream, S, d->N + 1, d->win_steps,
+                               round * d->win_steps);
+        }
+        HIP_TRY(hipGetLastError());
+        d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
+    }
+    return 0;
+}
+extern "C" {
+int ilqg_dev_windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *const *future) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(rounds < 1 || steps < 1 || steps >= d->N) {
+        g_err = "ilqg_dev_windows_begin: need rounds >= 1 and 1 <= steps < n_hor";
+        return 1;
+    }
+    if(windows_begin<N_STEP_PARAMS>(d, rounds, steps, future)) return 1;
+    d->win_rounds = rounds;
+    d->win_steps = steps;
+    return 0;
+}
+
+int ilqg_dev_windows_move(ilqg_dev_t *d, int round) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(round < 0 || round >= d->win_rounds) {
+        g_err = "ilqg_dev_windows_move: no such round (ilqg_dev_windows_begin)";
+        return 1;
+    }
+    return windows_move<N_STEP_PARAMS>(d, round);
 }
 
 #if ILQG_WAVE_MAP

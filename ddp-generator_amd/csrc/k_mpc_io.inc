@@ -88,3 +88,38 @@ __global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param_rows(double *__rest
         if(k < n) p[k] = v;
     }
 }
+
+// ALL windows of a context move with the horizon in ONE launch, fed from futures that already lie on the device
+// (ilqg_dev_windows_move: the resident loops ilqg_batch_receding_windows / _receding_plant_windows).  Per size -1 parameter of
+// the problem — its slot, grid.y — a descriptor by value: the window's base, its row count (B for a parameter with rows per
+// trajectory, 1 for the shared window), the base of its future or null (hold the last value, per row) and the future's row
+// stride (rounds * steps, or 0 for a shared future).  grid.x is the row; the workgroups beyond a slot's row count return at
+// once.  The tail of this round is columns [col, col + steps) of the row's future, col = round * steps.  Within a row the
+// ascending blocks of k_shift_param_rows, the same barrier, the same argument for moving in place; no other workgroup touches
+// the row.  Index arithmetic over B n and B rounds steps in size_t.  Plain loads and stores, no LDS.  A template on the number
+// of slots, so that it exists only in libraries whose problem has a per-time-step parameter.
+struct WindowDesc {
+    double *base;
+    const double *future;
+    size_t stride;
+    int rows;
+};
+template <int n_slots>
+struct WindowSet {
+    WindowDesc w[n_slots];
+};
+template <int n_slots>
+__global__ void __launch_bounds__(PARAM_BLOCK) k_shift_windows(WindowSet<n_slots> S, int n, int steps, int col) {
+    const int t = (int)threadIdx.x;
+    const WindowDesc w = S.w[blockIdx.y];
+    if(steps <= 0 || (int)blockIdx.x >= w.rows) return;  // (uniform over the workgroup: nobody is left at the barrier)
+    double *p = w.base + (size_t)blockIdx.x * (size_t)n;
+    const double *tl = w.future ? w.future + (size_t)blockIdx.x * w.stride + (size_t)col : nullptr;
+    for(int k0 = 0; k0 < n; k0 += PARAM_BLOCK) {
+        const int k = k0 + t, from = k + steps;
+        double v = 0.0;
+        if(k < n) v = from < n ? p[from] : (tl ? tl[from - n] : p[n - 1]);
+        __syncthreads();
+        if(k < n) p[k] = v;
+    }
+}

@@ -277,7 +277,43 @@ def _param_steps_rows(who, what, a, shape, device, gpu):
     return _cuda_address(a, shape, gpu, "%s: %s" % (who, what)), a
 
 
-def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant, params, disturbance):
+def _windows(solver, who, windows, rounds, steps):
+    """the windows of receding(windows=...) / receding_plant(windows=...): (n_windows, the array of names, the array of
+    pointers to the futures, what must outlive the call).  windows = {name: array or None}: every name a per-time-step
+    parameter, its future [B, rounds*steps] where the name currently has rows (set_param_steps_batch), [rounds*steps] where it
+    is shared, None: the window holds its last value.  Checked here, before any library call."""
+    if not isinstance(windows, dict):
+        raise IlqgError("%s: windows must be a dict of per-time-step parameter name -> future array (or None: hold the last value); "
+                        "{} moves every window holding its last value, windows=None calls the loop without windows" % who)
+    n = max(int(rounds), 0) * max(int(steps), 0)
+    rows = getattr(solver, "_step_rows", ())
+    names, keep = [], []
+    for name, a in windows.items():
+        names.append(_param_steps_name(solver.problem, who, name))
+        if a is None:
+            keep.append(None)
+            continue
+        what = "windows['%s']" % name
+        a = _plant_numbers(who, what, a)
+        shape = (solver.B, n) if name in rows else (n,)
+        if tuple(a.shape) != shape:
+            raise IlqgError("%s: %s has shape %s, expected %s = %s: the name %s" % (
+                who, what, tuple(a.shape), shape, "(B, rounds*steps)" if name in rows else "(rounds*steps,)",
+                "currently has rows per trajectory (set_param_steps_batch)" if name in rows else "is currently shared by all trajectories"))
+        keep.append(np.ascontiguousarray(a))
+    if not names:
+        return 0, None, None, keep
+    return (len(names), (C.c_char_p * len(names))(*names), (C.c_void_p * len(names))(*[None if a is None else a.ctypes.data for a in keep]), keep)
+
+
+def _note_step_rows(solver, name, on):
+    """the solver remembers which per-time-step names have rows per trajectory (the shape of a window's future depends on it)"""
+    rows = set(getattr(solver, "_step_rows", ()))
+    (rows.add if on else rows.discard)(name)
+    solver._step_rows = rows
+
+
+def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant, params, disturbance, windows=None):
     """BatchSolver.receding_plant / MultiSolver.receding_plant: the checks, the arrays and the one library call"""
     B, nx, nu = solver.B, solver.problem.nx, solver.problem.nu
     for what, v in (("rounds", rounds), ("steps", steps), ("iterations", iterations)):
@@ -290,10 +326,14 @@ def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant,
         raise IlqgError("receding_plant: params must be a non-empty dict of parameter name -> array [B, size], or None for a plant that is the model")
     names, values, _ = (None, None, 0) if params is None else _pack_arrays("receding_plant", solver.problem, params, ((B,),), "planner and plant",
                                                                            column=_plant_numbers)
+    moving = ()
+    if windows is not None:
+        n_windows, window_names, futures, keep = _windows(solver, "receding_plant", windows, rounds, steps)
+        entry, moving = entry + "_windows", (n_windows, window_names, futures)
     out = dict(x=np.zeros((B, n, nx)), u=np.zeros((B, n, nu)), cost=np.zeros((B, r)), plan_cost=np.zeros((B, r)), ok=np.zeros(B, dtype=np.int32),
                x_plant=xp)
     solver._ck(_receding_entry(solver.lib, entry)(solver.h, int(rounds), int(steps), int(iterations), 1 if feedback else 0, _address(xp),
-                                                  0 if names is None else len(names), names, _address(values), _address(dist),
+                                                  0 if names is None else len(names), names, _address(values), _address(dist), *moving,
                                                   *[_address(out[k]) for k in ("x", "u", "cost", "plan_cost", "ok")]))
     return out
 
@@ -422,6 +462,11 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
     if hasattr(lib, "ilqg_batch_receding_plant"):  # (and for the closed loop of planner and plant)
         lib.ilqg_batch_receding_plant.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, v, v, v, v, v, v]
         lib.ilqg_multi_receding_plant.argtypes = lib.ilqg_batch_receding_plant.argtypes
+    if hasattr(lib, "ilqg_batch_receding_windows"):  # (and for the windows that move inside the resident loops)
+        lib.ilqg_batch_receding_windows.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(v), v, v, v]
+        lib.ilqg_batch_receding_plant_windows.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, v,
+                                                          C.c_int, C.POINTER(C.c_char_p), C.POINTER(v), v, v, v, v, v]
+        lib.ilqg_multi_receding_plant_windows.argtypes = lib.ilqg_batch_receding_plant_windows.argtypes
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -582,13 +627,16 @@ class BatchSolver:
         cname = _param_steps_name(self.problem, who, name)
         if values is None:
             self._ck(_receding_entry(self.lib, "ilqg_batch_set_param_steps_batch")(self.h, cname, None))
+            _note_step_rows(self, name, False)
             return
         ptr, keep = _param_steps_rows(who, "values", values, (self.B, self.N + 1), device, self.device)
         if not device:
             self._ck(_receding_entry(self.lib, "ilqg_batch_set_param_steps_batch")(self.h, cname, ptr))
+            _note_step_rows(self, name, True)
             return
         entry = _receding_entry(self.lib, "ilqg_batch_set_param_steps_batch_device")
         self._ck(entry(self.h, cname, ptr, _torch_stream(self.device)[2]))
+        _note_step_rows(self, name, True)
 
     def param_steps_batch(self, name):
         """[B, n_hor+1]: what trajectory b sees of per-time-step parameter `name` (ilqg_batch_get_param_steps_batch) — its
@@ -712,16 +760,26 @@ class BatchSolver:
                 raise IlqgError("shift_param: tail has shape %s, expected (%d,) = (steps,)" % (tail.shape, max(int(steps), 0)))
         self._ck(_receding_entry(self.lib, "ilqg_batch_shift_param")(self.h, name.encode(), int(steps), _address(tail)))
 
-    def receding(self, rounds, steps, iterations):
+    def receding(self, rounds, steps, iterations, windows=None):
         """rounds x { iterate(iterations); record the first `steps` (x, u) of every plan and its cost; shift(steps) }
-        (ilqg_batch_receding): dict(x [B,rounds*steps,nx], u [B,rounds*steps,nu], cost [B,rounds]), copied to the host once"""
+        (ilqg_batch_receding): dict(x [B,rounds*steps,nx], u [B,rounds*steps,nu], cost [B,rounds]), copied to the host once.
+        A problem with a per-time-step parameter is refused unless windows is given: windows = {name: future or None}
+        (ilqg_batch_receding_windows) moves EVERY per-time-step parameter's window `steps` on each round, between the record
+        and the shift, on the device: future [B, rounds*steps] for a name that currently has rows (set_param_steps_batch),
+        [rounds*steps] for a shared name — the values beyond the current window, sent once —, None or a name left out: the
+        window holds its last value.  {} is valid.  Afterwards the windows have moved rounds*steps on (param_steps_batch)."""
         n = max(int(rounds), 0) * max(int(steps), 0)
+        entry, moving = "ilqg_batch_receding", ()
+        if windows is not None:
+            n_windows, window_names, futures, keep = _windows(self, "receding", windows, rounds, steps)
+            entry, moving = "ilqg_batch_receding_windows", (n_windows, window_names, futures)
         out = dict(x=np.zeros((self.B, n, self.problem.nx)), u=np.zeros((self.B, n, self.problem.nu)),
                    cost=np.zeros((self.B, max(int(rounds), 0))))
-        self._ck(_receding_entry(self.lib, "ilqg_batch_receding")(self.h, int(rounds), int(steps), int(iterations), out["x"], out["u"], out["cost"]))
+        ptr = (out["x"], out["u"], out["cost"]) if windows is None else tuple(_address(out[k]) for k in ("x", "u", "cost"))
+        self._ck(_receding_entry(self.lib, entry)(self.h, int(rounds), int(steps), int(iterations), *moving, *ptr))
         return out
 
-    def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None):
+    def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None, windows=None):
         """the closed loop of planner and plant on the GPU for `rounds` control intervals (ilqg_batch_receding_plant):
         rounds x { iterate(iterations); every trajectory's plant advances `steps` steps from ITS OWN state under the plan's
         policy, u = u_nom_k [+ L_k (x_plant - x_nom_k) if feedback], clamped, through the problem's dynamics and cost under
@@ -736,8 +794,11 @@ class BatchSolver:
         plan_cost [B,rounds] the cost of the plan the round applied, ok [B] int32 (0: a step of that plant met NaN / Inf; it
         stayed at its last finite state and its later entries are unspecified), x_plant [B,nx] the plants' states behind
         the last round, or None where x_plant was None).  The gains behind an accepted step are those about the previous
-        nominal trajectory (see policy_rollout)."""
-        return _receding_plant(self, "ilqg_batch_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance)
+        nominal trajectory (see policy_rollout).
+        windows = {name: future or None} as in receding() (ilqg_batch_receding_plant_windows): the plant's step k reads
+        p[name][k] of the round's not yet moved window (trajectory b's row where the name has rows), then every window moves
+        `steps` on, then the plans shift; without it a problem with a per-time-step parameter is refused."""
+        return _receding_plant(self, "ilqg_batch_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance, windows)
 
     def solve_stream(self, x0, u0, with_trajectories=False):
         """a stream of len(x0) starts through this batch's slots (ilqg_batch_solve_stream): dict of cost, status, iterations
@@ -980,6 +1041,7 @@ class MultiSolver:
         cname = _param_steps_name(self.problem, who, name)
         ptr, keep = (None, None) if values is None else _param_steps_rows(who, "values", values, (self.B, self.N + 1), False, None)
         self._ck(_receding_entry(self.lib, "ilqg_multi_set_param_steps_batch")(self.h, cname, ptr))
+        _note_step_rows(self, name, values is not None)
 
     def shift_param_batch(self, name, steps, tail=None):
         """BatchSolver.shift_param_batch on every shard, each with the tails of its trajectories (ilqg_multi_shift_param_batch)"""
@@ -1004,9 +1066,10 @@ class MultiSolver:
         numpy arrays"""
         return _policy_rollout(self, "ilqg_multi_policy_rollout", x0, alpha, feedback, trajectories, params)
 
-    def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None):
-        """BatchSolver.receding_plant of every shard, one shard after the other (ilqg_multi_receding_plant), numpy arrays"""
-        return _receding_plant(self, "ilqg_multi_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance)
+    def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None, windows=None):
+        """BatchSolver.receding_plant of every shard, one shard after the other (ilqg_multi_receding_plant, with windows
+        ilqg_multi_receding_plant_windows: a future [B, rounds*steps] is sharded by rows), numpy arrays"""
+        return _receding_plant(self, "ilqg_multi_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance, windows)
 
     def solve(self):
         self._ck(self.lib.ilqg_multi_solve(self.h))

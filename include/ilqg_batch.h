@@ -333,6 +333,57 @@ int ilqg_batch_get_param_steps_batch(ilqg_batch_t *c, const char *name, double *
 int ilqg_batch_shift_param_batch(ilqg_batch_t *c, const char *name, int steps, const double *tail /* [B][steps] host, or NULL */);
 int ilqg_batch_shift_param_batch_device(ilqg_batch_t *c, const char *name, int steps, const double *tail /* device or NULL */, void *stream);
 
+/* MOVING WINDOWS INSIDE THE RESIDENT LOOPS: tracking MPC that stays on the device.  ilqg_batch_receding and
+ * ilqg_batch_receding_plant refuse a problem that has a per-time-step parameter (size -1), because its window has to move with
+ * the horizon.  The two _windows entries below are the way round that limitation: the same loops, in which EVERY size -1
+ * parameter's window moves `steps` values on each round, fed from futures that sit on the device from before round 0.  The old
+ * entries keep every behaviour, their refusal included.
+ *
+ * window_names: n_windows host strings, each a parameter of size -1 of paramdesc[], in any order, none twice.  future[i] is HOST
+ * memory holding the values of window_names[i] BEYOND its current window, for the whole call:
+ *     [B][rounds*steps]  where the name currently has per-trajectory rows (ilqg_batch_set_param_steps_batch), row b for trajectory b;
+ *     [rounds*steps]     where the name is shared;
+ *     NULL               the window holds its last value, p[n_hor], per row.
+ * Every size -1 parameter of the problem moves, named or not: one that is not named holds its last value.  n_windows = 0 is
+ * allowed (window_names and future are then not read).  On a problem without a per-time-step parameter n_windows must be 0, and
+ * the call is ilqg_batch_receding / ilqg_batch_receding_plant bit for bit.
+ *
+ * ORDER WITHIN A ROUND r.  ilqg_batch_receding_windows:
+ *   (1) ilqg_batch_iterate(c, iterations);
+ *   (2) record, as ilqg_batch_receding does;
+ *   (3) every window moves `steps` on: p'[k] = p[k + steps], its last `steps` values columns [r*steps, (r+1)*steps) of its
+ *       future (what ilqg_batch_shift_param / ilqg_batch_shift_param_batch do with that tail, for all windows in one launch
+ *       per group of trajectories);
+ *   (4) ilqg_batch_shift(c, steps, NULL, NULL).
+ * ilqg_batch_receding_plant_windows:
+ *   (1) ilqg_batch_iterate(c, iterations);
+ *   (2) the plants advance `steps` steps as in ilqg_batch_receding_plant; the plant's step k reads p[name][k] of the round's
+ *       NOT YET MOVED window — trajectory b's row where the name has rows.  The plant has no window of its own, and a
+ *       per-time-step name among the plant's `names` stays refused;
+ *   (3) the windows move, as above;
+ *   (4) the plans shift onto the plants' states.
+ * THE WINDOWS MOVE BEFORE THE SHIFT, because the shift's initial roll-out reads them.
+ *
+ * Afterwards every window has moved rounds*steps on, on the device; the host copy of a shared window has moved with it (a
+ * later ilqg_batch_set_param of another parameter re-sends from that copy); ilqg_batch_get_param_steps_batch returns the moved
+ * rows; a following ilqg_batch_iterate continues as the caller's own loop over iterate / shift_param* / shift would.  Every
+ * other argument, the logs, the per-trajectory failure of the plant loop and its ok are those of the old entries.
+ * Memory: the futures go up once, before round 0, into buffers of the context that only grow; between rounds the host copies
+ * nothing and waits for nothing.  Wave-mapped libraries have no rows, so every name is shared there and takes a shared future.
+ *
+ * REFUSED, with the argument named in the error text and before anything is launched, allocated or changed: everything
+ * ilqg_batch_receding / ilqg_batch_receding_plant refuse except the per-time-step problem itself; a name that is no parameter
+ * ("Parameter name '%s' is not member of parameters struct."); a fixed-size name; a name given twice; n_windows < 0;
+ * n_windows > 0 with window_names or future NULL; n_windows > 0 on a problem without per-time-step parameters.
+ * Not supported: windows of the plant that differ from the planner's; futures in device memory. */
+int ilqg_batch_receding_windows(ilqg_batch_t *c, int rounds, int steps, int iterations,
+                                int n_windows, const char *const *window_names, const double *const *future,
+                                double *x_applied, double *u_applied, double *cost);
+int ilqg_batch_receding_plant_windows(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant,
+                                      int n_names, const char *const *names, const double *values, const double *disturbance,
+                                      int n_windows, const char *const *window_names, const double *const *future,
+                                      double *x_applied, double *u_applied, double *cost_applied, double *plan_cost, int *ok);
+
 /* n lock-step iterations of { calc_derivs, back_pass (+ lambda retries),
  * line_search over all alpha, accept/reject } for every still-active trajectory */
 int ilqg_batch_iterate(ilqg_batch_t *c, int n);
@@ -435,6 +486,12 @@ int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double
 int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
                               double *cost_applied, double *plan_cost, int *ok);
+/* ilqg_batch_receding_plant_windows per shard: a future of a name that has rows is [batch][rounds*steps], sharded by rows like
+ * every other [B]... array; a shared future goes to every shard as it is */
+int ilqg_multi_receding_plant_windows(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                                      const char *const *names, const double *values, const double *disturbance, int n_windows,
+                                      const char *const *window_names, const double *const *future, double *x_applied, double *u_applied,
+                                      double *cost_applied, double *plan_cost, int *ok);
 int ilqg_multi_iterate(ilqg_multi_t *m, int n);   /* asynchronous on every device; the devices are served in turn */
 int ilqg_multi_solve(ilqg_multi_t *m);
 int ilqg_multi_sync(ilqg_multi_t *m);

@@ -1,0 +1,211 @@
+"""ilqg.py's side of receding(windows=...) / receding_plant(windows=...) of BatchSolver and MultiSolver, where no GPU is needed:
+the futures reach ilqg_batch_receding_windows / ilqg_batch_receding_plant_windows / ilqg_multi_receding_plant_windows as
+documented, per name and per form ([B, rounds*steps] for a name the solver has given rows, [rounds*steps] for a shared name,
+None as a NULL entry, {} as n_windows = 0 with both arrays NULL; single precision and strided inputs copied) with the matching
+names; windows=None reaches the OLD entry with the old argument list; wrong shapes, names and types are refused before any
+library call; a library built before the entries existed says "rebuild"; and the public header declares the three entries in
+a block of its own that states their refusals and the order within a round.  Modelled on tests/test_param_steps_binding.py."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_package
+from test_policy_rollout_binding import FakeCudaTensor, OldLibrary
+from test_policy_rollout_params_binding import NU, NX, B, N, solver
+
+NEW = ["ilqg_batch_receding_windows", "ilqg_batch_receding_plant_windows", "ilqg_multi_receding_plant_windows"]
+OLD = ["ilqg_batch_receding", "ilqg_batch_receding_plant", "ilqg_multi_receding_plant"]
+SETTERS = ["ilqg_batch_set_param_steps_batch", "ilqg_multi_set_param_steps_batch"]
+
+
+def doubles(address, shape):
+    if not address:
+        return None
+    return np.ctypeslib.as_array(C.cast(address, C.POINTER(C.c_double)), shape=(int(np.prod(shape)),)).reshape(shape).copy()
+
+
+class Recorder:
+    """a library with the old and the new entries: remembers what each was called with, the futures as values.  `rows`: the
+    names whose futures are [B, rounds*steps] (what the test gave rows before)"""
+
+    def __init__(self, rows=()):
+        self.calls, self.rows = [], set(rows)
+        for name in SETTERS:
+            setattr(self, name, lambda h, name, values: 0)
+        setattr(self, NEW[0], self._windows(NEW[0], plant=False))
+        for name in NEW[1:]:
+            setattr(self, name, self._windows(name, plant=True))
+        setattr(self, OLD[0], lambda h, rounds, steps, iterations, x, u, cost: self.calls.append((OLD[0], dict(h=h, n=3))) or 0)
+        for name in OLD[1:]:
+            setattr(self, name, self._old_plant(name))
+
+    def _old_plant(self, entry):
+        def call(h, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, x, u, cost, plan_cost, ok):
+            self.calls.append((entry, dict(h=h, n=10)))
+            return 0
+        return call
+
+    def _windows(self, entry, plant):
+        def call(h, rounds, steps, iterations, *rest):
+            if plant:
+                feedback, x_plant, n_names, names, values, disturbance, n_windows, window_names, future = rest[:9]
+                out = rest[9:]
+                assert len(out) == 5
+            else:
+                n_windows, window_names, future = rest[:3]
+                out = rest[3:]
+                assert len(out) == 3
+            got = [window_names[i].decode() for i in range(n_windows)]
+            futures = [doubles(future[i], (B, rounds * steps) if got[i] in self.rows else (rounds * steps,)) for i in range(n_windows)]
+            self.calls.append((entry, dict(h=h, rounds=rounds, steps=steps, iterations=iterations, names=got, futures=futures,
+                                           names_arg=window_names, future_arg=future, out=out)))
+            return 0
+        return call
+
+
+@pytest.fixture(scope="module")
+def ilqg():
+    return load_package().ilqg
+
+
+def test_futures_reach_the_entries_as_documented(ilqg):
+    lib = Recorder(rows=("vref",))
+    s, m = solver(ilqg, lib), solver(ilqg, lib, ilqg.MultiSolver)
+    rng = np.random.default_rng(1)
+    rows, per, shared = np.zeros((B, N + 1)), rng.standard_normal((B, 6)), rng.standard_normal(6)
+    for q in (s, m):
+        q.set_param_steps_batch("vref", rows)  # the solver remembers: vref has rows from here on
+    outs = [s.receding(3, 2, 4, windows=dict(vref=per)),
+            s.receding(3, 2, 4, windows=dict(vref=per.astype(np.float32))),                  # single precision: converted
+            s.receding(3, 2, 4, windows=dict(vref=np.zeros((B, 12))[:, ::2] + per)),         # strided: copied
+            s.receding(3, 2, 4, windows=dict(vref=None)),                                    # hold: a NULL entry
+            s.receding(3, 2, 4, windows={}),                                                 # every window holds
+            s.receding_plant(3, 2, 4, windows=dict(vref=per)),
+            m.receding_plant(3, 2, 4, windows=dict(vref=per.tolist()))]
+    assert [c[0] for c in lib.calls] == [NEW[0]] * 5 + [NEW[1], NEW[2]]
+    want = [per, per.astype(np.float32).astype(np.float64), per, None, None, per, per]
+    for (entry, c), w, i in zip(lib.calls, want, range(7)):
+        assert c["h"] == 1 and (c["rounds"], c["steps"], c["iterations"]) == (3, 2, 4), entry
+        assert c["names"] == ([] if i == 4 else ["vref"]), (entry, c["names"])
+        if i == 4:
+            assert c["names_arg"] is None and c["future_arg"] is None
+        elif w is None:
+            assert c["futures"] == [None]
+        else:
+            assert np.array_equal(c["futures"][0], w), (entry, i)
+        assert all(p is not None for p in c["out"])
+    assert outs[0]["x"].shape == (B, 6, NX) and outs[0]["u"].shape == (B, 6, NU) and outs[0]["cost"].shape == (B, 3)
+    assert sorted(outs[5]) == ["cost", "ok", "plan_cost", "u", "x", "x_plant"]
+    # a name made shared again takes a shared future; a name that never had rows as well
+    lib.rows.clear()
+    for q in (s, m):
+        q.set_param_steps_batch("vref", None)
+    del lib.calls[:]
+    s.receding(3, 2, 4, windows=dict(vref=shared))
+    s.receding_plant(3, 2, 4, feedback=False, windows=dict(vref=shared.astype(np.float32)))
+    m.receding_plant(3, 2, 4, windows=dict(vref=shared))
+    fresh = solver(ilqg, lib)
+    fresh.receding(1, 6, 0, windows=dict(vref=shared))
+    assert [c[0] for c in lib.calls] == [NEW[0], NEW[1], NEW[2], NEW[0]]
+    for (entry, c), w in zip(lib.calls, [shared, shared.astype(np.float32).astype(np.float64), shared, shared]):
+        assert c["names"] == ["vref"] and np.array_equal(c["futures"][0], w), entry
+
+
+def test_windows_none_reaches_the_old_entries(ilqg):
+    lib = Recorder()
+    s, m = solver(ilqg, lib), solver(ilqg, lib, ilqg.MultiSolver)
+    # (the old model loop's outputs go through numpy's argument types, which a stand-in does not have: only the name counts)
+    s.receding_plant(3, 2, 4)
+    s.receding_plant(3, 2, 4, windows=None)
+    m.receding_plant(3, 2, 4, windows=None)
+    assert [c[0] for c in lib.calls] == [OLD[1], OLD[1], OLD[2]]
+    s.receding(3, 2, 4)
+    s.receding(3, 2, 4, windows=None)
+    assert [c[0] for c in lib.calls[3:]] == [OLD[0], OLD[0]]
+
+
+def test_wrong_arguments_are_refused_before_any_library_call(ilqg):
+    lib = Recorder(rows=("vref",))
+    s, m = solver(ilqg, lib), solver(ilqg, lib, ilqg.MultiSolver)
+    shared_s, shared_m = solver(ilqg, lib), solver(ilqg, lib, ilqg.MultiSolver)
+    for q in (s, m):
+        q.set_param_steps_batch("vref", np.zeros((B, N + 1)))
+    bad_rows = [(dict(vref=np.zeros(6)), ("windows['vref']", "shape", "(5, 6)", "rows per trajectory")),     # a shared future for a name with rows
+                (dict(vref=np.zeros((B, 5))), ("windows['vref']", "shape", "(5, 6)")),
+                (dict(vref=np.zeros((6, B))), ("windows['vref']", "shape")),
+                (dict(vref=np.zeros((B, 6), dtype=complex)), ("windows['vref']", "dtype")),
+                (dict(vref=FakeCudaTensor((B, 6))), ("windows['vref']", "device", "host memory")),
+                (dict(nope=np.zeros((B, 6))), ("Parameter name 'nope' is not member of parameters struct.",)),
+                (dict(cf=np.zeros((B, 6))), ("cf", "fixed size of 4")),
+                ([("vref", np.zeros((B, 6)))], ("windows", "dict"))]
+    bad_shared = [(dict(vref=np.zeros((B, 6))), ("windows['vref']", "shape", "(6,)", "shared")),             # rows for a shared name
+                  (dict(vref=np.zeros(5)), ("windows['vref']", "shape", "(6,)")),
+                  (dict(d=None), ("d", "fixed size of 1"))]
+    for solvers, cases in (((s, m), bad_rows), ((shared_s, shared_m), bad_shared)):
+        for windows, words in cases:
+            for q in solvers:
+                calls = [lambda: q.receding_plant(3, 2, 4, windows=windows)] + ([lambda: q.receding(3, 2, 4, windows=windows)] if q in (s, shared_s) else [])
+                for call in calls:
+                    with pytest.raises(ilqg.IlqgError) as e:
+                        call()
+                    assert "receding" in str(e.value) and all(w in str(e.value) for w in words), str(e.value)
+    assert lib.calls == []
+
+
+def test_methods_of_an_old_library_say_rebuild(ilqg):
+    s, m = solver(ilqg, OldLibrary()), solver(ilqg, OldLibrary(), ilqg.MultiSolver)
+    for call, name in ((lambda: s.receding(3, 2, 4, windows={}), NEW[0]), (lambda: s.receding(3, 2, 4, windows=dict(vref=np.zeros(6))), NEW[0]),
+                       (lambda: s.receding_plant(3, 2, 4, windows={}), NEW[1]), (lambda: m.receding_plant(3, 2, 4, windows=dict(vref=None)), NEW[2])):
+        with pytest.raises(ilqg.IlqgError) as e:
+            call()
+        assert name in str(e.value) and "rebuild" in str(e.value)
+
+
+def test_the_multi_entry_offsets_a_future_with_rows_by_the_shards_first_trajectory():
+    """read off the C source: the host code cannot run without a GPU"""
+    text = open(os.path.join(ROOT, "ddp-generator_amd", "csrc", "ilqg_host.c")).read()
+    body = text[text.index("int ilqg_multi_receding_plant_windows("):]
+    body = " ".join(body[:body.index("\nint ilqg_multi_init(")].split())
+    assert "at = (size_t)m->first[g]" in body and "per = rn * (steps > 0 ? (size_t)steps : 0)" in body
+    assert "m->shard[g]->ps_on[k]) ? future[i] + at * per : future[i]" in body
+    for piece in ("x_plant ? x_plant + at * N_X : NULL", "values ? values + at * W : NULL", "disturbance ? disturbance + at * per * N_X : NULL",
+                  "x_applied ? x_applied + at * per * N_X : NULL", "u_applied ? u_applied + at * per * N_U : NULL",
+                  "cost_applied ? cost_applied + at * rn : NULL", "plan_cost ? plan_cost + at * rn : NULL", "ok ? ok + at : NULL"):
+        assert piece in body, piece
+    assert "ilqg_batch_receding_plant_windows(m->shard[g], rounds, steps, iterations, feedback," in body
+
+
+def test_public_header_declares_the_entries_and_states_refusals_and_order():
+    text = open(os.path.join(ROOT, "include", "ilqg_batch.h")).read()
+    for entry in NEW:
+        assert re.search(r"\bint %s\(" % entry, text), entry
+    flat = " ".join(re.sub(r"\n \*", "\n", text).split()).lower()  # (comment lines joined)
+    block = flat[flat.index("moving windows inside the resident loops"):flat.index("int ilqg_batch_receding_windows(")]
+    assert "the way round that limitation" in block
+    for words in ("[b][rounds*steps] where the name currently has per-trajectory rows", "[rounds*steps] where the name is shared",
+                  "the window holds its last value", "every size -1 parameter of the problem moves, named or not", "n_windows = 0 is allowed",
+                  "bit for bit"):
+        assert words in block, words
+    # the order within a round, for both loops
+    order = [block.index(w) for w in ("(1) ilqg_batch_iterate(c, iterations)", "(2) record", "(3) every window moves `steps` on",
+                                      "(4) ilqg_batch_shift(c, steps, null, null)")]
+    assert order == sorted(order)
+    plant = block[block.index("ilqg_batch_receding_plant_windows: (1)"):]
+    order = [plant.index(w) for w in ("(1) ilqg_batch_iterate", "(2) the plants advance", "not yet moved window", "(3) the windows move",
+                                      "(4) the plans shift onto the plants' states")]
+    assert order == sorted(order)
+    assert "the windows move before the shift, because the shift's initial roll-out reads them" in block
+    for refusal in ("a name that is no parameter", "a fixed-size name", "a name given twice", "n_windows < 0",
+                    "n_windows > 0 with window_names or future null", "n_windows > 0 on a problem without per-time-step parameters",
+                    "before anything is launched, allocated or changed"):
+        assert refusal in block, refusal
+    for memory in ("the futures go up once, before round 0", "between rounds the host copies nothing and waits for nothing"):
+        assert memory in block, memory
+    # the block of the entries these complement is as it was: its limitation stays true of the two old entries
+    assert "receding / receding_plant for problems with per-time-step parameters (moving windows inside those loops)" in flat
+    ilqg = load_package().ilqg
+    for f in (ilqg.BatchSolver.receding, ilqg.BatchSolver.receding_plant, ilqg.MultiSolver.receding_plant):
+        assert "windows" in " ".join(f.__doc__.split())

@@ -4,6 +4,7 @@
     python tools/receding_profile.py [--config headline|config5|both] [--repeats 10] [--steps 10] [--warmup 20]
     python tools/receding_profile.py --loop external [--config ...] [--repeats 10] [--steps 1] [--iterations 2]
     python tools/receding_profile.py --loop plant [--config ...] [--repeats 10] [--steps 1] [--iterations 2] [--rounds 5]
+    python tools/receding_profile.py --loop windows [--batch 65536] [--repeats 10] [--steps 1] [--iterations 2] [--rounds 10]
 
 One process per invocation.  After `--warmup` iterations the two re-plans ALTERNATE; each is timed by the host clock
 between two device synchronisations, and two solver iterations run between re-plans so that every one of them finds the
@@ -27,6 +28,17 @@ Per form and repeat two host-clock figures between two device synchronisations, 
 with `--iterations` solver iterations per round, and the loop with 0 iterations per round behind one iterate() — what a
 round costs behind its iterations (the overhead).  receding_plant's figures include its one upload of the tables and its one
 download of the logs, receding's its one download.  k_plant's own time is HIP events.
+
+--loop windows: tracking MPC, the model loop of a problem whose per-time-step parameter has a window per trajectory (almix
+FULL_DDP 1, `vref`, rows; --config is not read), `--rounds` control intervals per loop, in three forms that ALTERNATE in one
+process:
+    resident         BatchSolver.receding(windows=...): one call, every window moved on the device by k_shift_windows from a
+                     future sent once
+    hand, device     the loop from Python with the tails on the GPU: iterate; head(device=True); shift_param_batch(device=True)
+                     with the round's columns of a torch tensor; shift
+    hand, host       the same with host tails: iterate; head; shift_param_batch(numpy columns); shift
+Figures as for --loop plant: per round the whole loop, and the loop with 0 iterations per round behind one iterate() (the
+overhead behind iterate).  The resident form's figures include its one upload of the future and its one download of the log.
 """
 import argparse
 import os
@@ -272,26 +284,107 @@ def run_plant(ilqg, synth, config, repeats, steps, warmup, iterations, rounds):
     s.close()
 
 
+def run_windows(ilqg, repeats, steps, warmup, iterations, rounds, batch):
+    import torch
+    from oracle.harness import almix_case
+    name, B = "vref", batch
+    params, opts, x0, u0 = almix_case(batch=B)
+    N = u0.shape[1]
+    s = ilqg.BatchSolver("almix", 1, batch=B, n_hor=N, params=params, opts=dict(opts, max_iter=1 << 20))
+    print("== almix FULL_DDP=1, %d trajectories, N = %d, a window of `vref` per trajectory, %d round(s) per loop, %d step(s) applied and %d iteration(s) "
+          "per round, %d stream group(s)" % (B, N, rounds, steps, iterations, s.groups()))
+    rng = np.random.default_rng(59)
+    per = rounds * steps
+    T = (0.8 + 0.4 * np.sin(0.2 * np.arange(N + 1 + per)))[None, :] * (1.0 + 0.05 * rng.standard_normal((B, N + 1 + per)))
+    rows, future = np.ascontiguousarray(T[:, :N + 1]), np.ascontiguousarray(T[:, N + 1:])
+    tails = [np.ascontiguousarray(future[:, r * steps:(r + 1) * steps]) for r in range(rounds)]
+    tails_t = [torch.from_numpy(t).cuda() for t in tails]
+    kept = {}
+
+    def resident(k):
+        kept["log"] = s.receding(rounds, steps, k, windows={name: future})
+
+    def hand_device(k):
+        for r in range(rounds):
+            s.iterate(k)
+            kept["head"] = s.head(steps, device=True)
+            s.shift_param_batch(name, steps, tails_t[r], device=True)
+            s.shift(steps)
+
+    def hand_host(k):
+        for r in range(rounds):
+            s.iterate(k)
+            kept["head"] = s.head(steps)
+            s.shift_param_batch(name, steps, tails[r])
+            s.shift(steps)
+
+    forms = (("resident: receding(windows=...), one call", resident), ("hand loop, tails on the GPU", hand_device), ("hand loop, tails on the host", hand_host))
+
+    def sync():
+        torch.cuda.synchronize()
+        s.sync()
+
+    s.set_param_steps_batch(name, rows)
+    s.init(x0, u0)
+    s.iterate(warmup)
+    for _, f in forms:  # once untimed: the logs', futures' and staging buffers, torch's allocator
+        f(iterations)
+    sync()
+    s.timing(True)
+    whole, over = {n: [] for n, _ in forms}, {n: [] for n, _ in forms}
+    for r in range(repeats):
+        for label, f in forms:
+            sync()
+            t0 = time.perf_counter()
+            f(iterations)
+            sync()
+            whole[label].append(1e3 * (time.perf_counter() - t0) / rounds)
+            s.iterate(iterations)  # the first round of the overhead loop finds the batch as a round behind its iterations does
+            sync()
+            t0 = time.perf_counter()
+            f(0)
+            sync()
+            over[label].append(1e3 * (time.perf_counter() - t0) / rounds)
+    kt = s.kernel_times()
+    s.timing(False)
+    for label, _ in forms:
+        print("%-48s per round  %s" % (label, spread(whole[label])))
+        print("%-48s overhead   %s" % ("", spread(over[label])))
+    res, dev, host = (np.median(over[n]) for n, _ in forms)
+    print("overhead per round behind iterate, medians: resident %.3f ms, hand loop with device tails %.3f ms (%.2f x), with host tails %.3f ms (%.2f x)" % (
+        res, dev, dev / res, host, host / res))
+    for k in ("k_shift_windows", "k_shift_param_rows", "k_shift", "k_log_steps", "k_head", "k_rollout[init]"):
+        n, ms = kt[k]
+        print("%s: %d launches, %.4f ms per launch" % (k, n, ms / max(n, 1)))
+    print("a window is %d doubles per trajectory; per round and trajectory %d of them come from the future" % (N + 1, steps))
+    s.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="both", choices=("headline", "config5", "both"))
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--steps", type=int, default=None, help="steps per shift (default 10; 1 with --loop external / plant)")
-    ap.add_argument("--loop", default="replan", choices=("replan", "external", "plant"),
-                    help="external: the control interval of a caller with its own plant; plant: the closed loop of planner and plant on the device")
+    ap.add_argument("--loop", default="replan", choices=("replan", "external", "plant", "windows"),
+                    help="external: the control interval of a caller with its own plant; plant: the closed loop of planner and plant on the device; "
+                         "windows: the model loop with a moving window per trajectory (almix)")
+    ap.add_argument("--batch", type=int, default=65536, help="--loop windows: trajectories")
     ap.add_argument("--iterations", type=int, default=2, help="--loop external / plant: solver iterations per control interval")
-    ap.add_argument("--rounds", type=int, default=5, help="--loop plant: control intervals per timed loop")
+    ap.add_argument("--rounds", type=int, default=None, help="--loop plant / windows: control intervals per timed loop (default 5; 10 with --loop windows)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--between", type=int, default=2, help="solver iterations between two re-plans")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.load_package()
     from ddp_generator_amd import ilqg, synth
+    if a.loop == "windows":
+        run_windows(ilqg, a.repeats, a.steps or 1, a.warmup, a.iterations, a.rounds or 10, a.batch)
+        return
     for config in (("headline", "config5") if a.config == "both" else (a.config,)):
         if a.loop == "external":
             run_external(ilqg, synth, config, a.repeats, a.steps or 1, a.warmup, a.iterations)
         elif a.loop == "plant":
-            run_plant(ilqg, synth, config, a.repeats, a.steps or 1, a.warmup, a.iterations, a.rounds)
+            run_plant(ilqg, synth, config, a.repeats, a.steps or 1, a.warmup, a.iterations, a.rounds or 5)
         else:
             run(ilqg, synth, config, a.repeats, a.steps or 10, a.warmup, a.between)
 
