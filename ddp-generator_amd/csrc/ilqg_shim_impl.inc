@@ -11,6 +11,8 @@
 // context's pass starts when the first one's has finished — which is also the schedule that pays: the backward pass
 // fills the chip, the roll-outs (one lane per trajectory and step size) cannot, so with the batch advancing as two
 // groups of trajectories the roll-outs of one run beside the backward pass of the other.
+// (Reference-counted and process-wide, allocated by a loop that halves the request until the device has it: the one device
+// allocation of a context that is NOT a Buffer below.)
 struct SharedWork {
     trajEl_t *buf;
     size_t bytes;
@@ -28,32 +30,137 @@ struct SharedWork;
 
 constexpr int QUEUE_CELL = 32;  // ints between two counters: a cache line each
 
-struct ilqg_dev {
+namespace {  // (internal linkage: the libraries export the C entries, no symbol of these types)
+
+// The ONE owner of memory the shim allocates: device memory, or with PinnedMem as the second argument pinned host memory.
+// Move-only; the destructor frees.  The acquiring calls return the shim's 0 / 1 with g_err set (HIP_TRY) and leave the
+// buffer empty, bytes() == 0, when the allocation fails.  `drain`: the stream whose queued work may still read the old
+// memory, synchronised before it is freed (nullptr: nothing can).
+struct DeviceMem {
+    static hipError_t take(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t give(void *p) { return hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t take(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static hipError_t give(void *p) { return hipHostFree(p); }
+};
+template <class T, class Mem = DeviceMem>
+class Buffer {
+    T *p_ = nullptr;
+    size_t bytes_ = 0;
+
+  public:
+    Buffer() = default;
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    Buffer(Buffer &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+    Buffer &operator=(Buffer &&o) noexcept {
+        if(this != &o) {
+            (void)release();
+            p_ = o.p_, bytes_ = o.bytes_;
+            o.p_ = nullptr, o.bytes_ = 0;
+        }
+        return *this;
+    }
+    ~Buffer() {
+        if(p_) (void)Mem::give(p_);
+    }
+    T *get() const { return p_; }
+    size_t bytes() const { return bytes_; }
+    // frees and forgets (also where the free fails)
+    int release() {
+        T *old = p_;
+        p_ = nullptr, bytes_ = 0;
+        if(old) HIP_TRY(Mem::give(old));
+        return 0;
+    }
+    // frees, then allocates exactly `bytes`
+    int renew(size_t bytes) {
+        if(release()) return 1;
+        const hipError_t allocation = Mem::take((void **)&p_, bytes);
+        if(allocation != hipSuccess) p_ = nullptr;
+        HIP_TRY(allocation);
+        bytes_ = bytes;
+        return 0;
+    }
+    // grow-only: nothing if the buffer holds `bytes`; else drain, free, allocate
+    int reserve(size_t bytes, hipStream_t drain = nullptr) {
+        if(bytes <= bytes_) return 0;
+        if(drain) HIP_TRY(hipStreamSynchronize(drain));
+        return renew(bytes);
+    }
+    // the same for a buffer the caller can do without: 2 = the device does not have the memory (the error is cleared)
+    int try_reserve(size_t bytes, hipStream_t drain) {
+        if(bytes <= bytes_) return 0;
+        HIP_TRY(hipStreamSynchronize(drain));
+        if(release()) return 1;
+        // (ILQG_TEST_NO_PLANES: the tests' way to a device that is out of memory)
+        if(getenv("ILQG_TEST_NO_PLANES") || Mem::take((void **)&p_, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p_ = nullptr;
+            return 2;
+        }
+        bytes_ = bytes;
+        return 0;
+    }
+};
+// A view in DevPtrs follows its owner in the statement that acquires, grows or releases it: `rc` is that call's result
+template <class T>
+static int repoint(T *&view, const Buffer<T> &owner, int rc) {
+    view = owner.get();
+    return rc;
+}
+
+// Everything a context allocates.  DevPtrs P holds plain views of these for the kernels; sizes live here, in bytes().
+// ilqg_dev_destroy releases all of it in one statement; a new buffer is a member here and a reserve() where it is used.
+struct DevBuffers {
+    Buffer<double> f[ILQG_F_COUNT], nom;   // P.f[], P.nom
+    Buffer<int> i[ILQG_I_COUNT], derivs_failed, pending_list, n_pending;  // P.i[], P.derivs_failed, P.pending, P.n_pending
+    Buffer<trajEl_t> work;                 // P.work of stage-by-stage calls (own_work)
+    Buffer<double *> param_table;          // P.p: the table of the pointers below
+    std::vector<Buffer<double>> param_bufs;
+    Buffer<int> counter;
+    Buffer<int> queues;    // wave mapping: the backward kernel's trajectory counters (DevPtrs::queue), QUEUE_CELL ints apart
+    Buffer<double> cand, cand1;            // P.cand, P.cand1
+    Buffer<double> xpl, upl;               // P.xpl, P.upl (ls_keep = 2)
+    Buffer<unsigned> spec_ints;            // quad mapping with speculative retries: the protocol's words
+    Buffer<double> spec_doubles;           //   ... the rows' results and gains
+    Buffer<double> log_x, log_u, log_c;    // receding horizon: the applied steps of every round (ilqg_dev_log_begin), host layout
+    // the plants of a closed loop (ilqg_dev_plant_begin): their states [B][NX], failure flags [B], the sums of the applied
+    // running costs [B][rounds] (the applied steps and the plans' costs go to the log above), and what the caller sent:
+    // the parameter rows [B][W] with their map, the disturbances [B][rounds * steps][NX]
+    Buffer<double> plant_xp, plant_cost, plant_values, plant_dist;
+    Buffer<int> plant_failed;
+    // per-trajectory problem parameters (ilqg_dev_set_params_batch): the rows [B][W]; the buffer only grows and outlives a cleared set
+    Buffer<double> pb_values;
+    // per-time-step parameters per trajectory (ilqg_dev_set_param_steps_batch): for the s-th parameter of size -1 its rows
+    // [Bp][N + 1] (trajectory-major; rows B .. Bp - 1 are zero and belong to nobody); grow-only like pb_values
+    static constexpr int SR = N_STEP_PARAMS > 0 ? N_STEP_PARAMS : 1;
+    Buffer<double> sr_rows[SR];
+    // the futures of a resident loop's windows (ilqg_dev_windows_begin): per slot the values beyond the window, [B][win_per] for
+    // a parameter with rows, [win_per] for the shared window; grow-only
+    Buffer<double> win_future[SR];
+    Buffer<double> staging;                // see io_deferred
+    Buffer<char, PinnedMem> pinned;
+};
+
+}  // namespace
+
+struct ilqg_dev : DevBuffers {
     int device, B, Bp, N;
     hipStream_t stream;
     DevPtrs P;
     ilqg_dev_opts_t O;
-    std::vector<double *> param_bufs;
     ParamValues pv;       // fixed-size parameters, passed to the kernels by value
-    double *staging;
-    size_t staging_bytes;
     // Deferred transfers (ilqg_dev_io_begin .. ilqg_dev_io_end): every write / read takes its own slice of the device
     // staging buffer and of a pinned host buffer and nothing waits; the stream is synchronised once, at the end, and
     // the reads are handed to the caller then.  (The drop-in back_pass() / line_search() move two dozen small arrays
     // per call: one wait instead of one per array.)
     bool io_deferred;
     size_t io_off;
-    char *pinned;
-    size_t pinned_bytes;
     struct PendingRead { void *dst; const void *src; size_t bytes; int transpose_w; };
     std::vector<PendingRead> pending;
-    int *counter;
-    size_t cand_bytes;    // size of P.cand
-    size_t cand1_bytes;   // size of P.cand1
-    double *spec_ints, *spec_doubles;  // quad mapping with speculative retries: the protocol's words / the rows' results and gains
-    size_t spec_ints_bytes, spec_doubles_bytes;
     bool keep_first;      // the roll-out launch in progress keeps the first stage's roll-outs in P.cand1
-    size_t xpl_bytes, upl_bytes;  // sizes of P.xpl / P.upl (ls_keep = 2)
     size_t roll_lds;              // wave mapping: dynamic LDS asked for by the second-stage roll-outs (one workgroup per CU)
     size_t roll_pad;              //   ... on top of the records' buffer when the records go through LDS
     bool roll_dma;                // wave mapping: k_rollout_parts fetches the nominal records through LDS
@@ -61,7 +168,6 @@ struct ilqg_dev {
     bool defer_commit, commit_pending, pending_zero;  // ls_keep = 2: k_update commits / clears the pending counter
     int commit_s1, commit_set;
     bool winner_done;     // the last search ended with the accepted trajectories in place (two-stage search)
-    int *queues;          // wave mapping: the backward kernel's trajectory counters (DevPtrs::queue), QUEUE_CELL ints apart
     int cus;              // compute units of the device
     int chunk;            // wave mapping: trajectories whose derivative records fit the work buffer
     bool work_consts;     // wave mapping: constant entries of the records written (init_running)
@@ -79,33 +185,15 @@ struct ilqg_dev {
     struct SharedWork *shared;  // wave mapping: the device's derivative work buffer (see SharedWork)
     int own_chunk;              // trajectories whose records fit the context's private buffer P.work (stage-by-stage calls)
     bool per_step_params;       // some problem parameter has one value per time step
-    double *log_x, *log_u, *log_c;  // receding horizon: the applied steps of every round (ilqg_dev_log_begin), host layout
-    int log_rounds, log_steps;
-    // the plants of a closed loop (ilqg_dev_plant_begin): their states [B][NX], failure flags [B], the sums of the applied
-    // running costs [B][rounds] (the applied steps and the plans' costs go to the log above), and what the caller sent:
-    // the parameter rows [B][W] with their map, the disturbances [B][rounds * steps][NX]
-    double *plant_xp, *plant_cost, *plant_values, *plant_dist;
-    int *plant_failed;
-    bool plant_named;
+    int log_rounds, log_steps;  // the log's shape (log_x, log_u, log_c)
+    bool plant_named;           // the plants run under plant_values and this map
     PolicyParamMap plant_map;
-    // per-trajectory problem parameters (ilqg_dev_set_params_batch): the rows [B][W] with their map; the buffer only grows
-    // and outlives a cleared set.  pb_on: the lane-mapped kernels that take ParamValues run as the instantiation whose pack is this table and
-    // its map (LAUNCH_PV)
-    double *pb_values;
-    size_t pb_bytes;
+    // pb_on: the lane-mapped kernels that take ParamValues run as the instantiation whose pack is the table pb_values and its map
+    // (LAUNCH_PV)
     bool pb_on;
     PolicyParamMap pb_map;
-    // per-time-step parameters per trajectory (ilqg_dev_set_param_steps_batch): for the s-th parameter of size -1 its rows
-    // [Bp][N + 1] (trajectory-major; rows B .. Bp - 1 are zero and belong to nobody); grow-only like pb_values, sr_on[s]: in use
-    static constexpr int SR = N_STEP_PARAMS > 0 ? N_STEP_PARAMS : 1;
-    double *sr_rows[SR];
-    size_t sr_bytes[SR];
-    bool sr_on[SR];
-    // the futures of a resident loop's windows (ilqg_dev_windows_begin): per slot the values beyond the window, [B][win_per] for
-    // a parameter with rows, [win_per] for the shared window; grow-only; win_given[s]: the slot has a future (else it holds)
-    double *win_future[SR];
-    size_t win_bytes[SR];
-    bool win_given[SR];
+    bool sr_on[SR];             // sr_rows[s] is in use
+    bool win_given[SR];         // the slot has a future in win_future[s] (else its window holds)
     int win_rounds, win_steps;  // 0: no loop open
     // what LAUNCH_PV hands the rows twins: rows_on = pb_on or some sr_on; rows_map = pb_map (empty without a table) with the
     // step rows in use (rows_refresh, after every change of either set)
@@ -180,16 +268,6 @@ int field_steps(const ilqg_dev *d, int f) {
 
 int int_field_width(int f) { return f == ILQG_I_ALPHA_OK ? ILQG_MAX_ALPHA : 1; }
 
-int ensure_staging(ilqg_dev *d, size_t bytes) {
-    if(bytes <= d->staging_bytes) return 0;
-    if(d->staging) HIP_TRY(hipFree(d->staging));
-    d->staging = nullptr;
-    d->staging_bytes = 0;
-    HIP_TRY(hipMalloc((void **)&d->staging, bytes));
-    d->staging_bytes = bytes;
-    return 0;
-}
-
 // end of a deferred batch (or of a part of it): wait once, deliver the reads
 int io_flush(ilqg_dev *d) {
     HIP_TRY(hipStreamSynchronize(d->stream));
@@ -212,24 +290,19 @@ int io_flush(ilqg_dev *d) {
 // pinned host buffer (nullptr otherwise: the transfer then uses the caller's memory and is waited for at once).
 int stage(ilqg_dev *d, size_t bytes, void **dev, void **pin) {
     if(!d->io_deferred) {
-        if(ensure_staging(d, bytes)) return 1;
-        *dev = d->staging;
+        if(d->staging.reserve(bytes)) return 1;
+        *dev = d->staging.get();
         *pin = nullptr;
         return 0;
     }
     bytes = (bytes + 255) & ~(size_t)255;
-    if(d->io_off + bytes > d->staging_bytes || d->io_off + bytes > d->pinned_bytes) {
+    if(d->io_off + bytes > d->staging.bytes() || d->io_off + bytes > d->pinned.bytes()) {
         if(io_flush(d)) return 1;  // what is in flight uses the old buffers
-        const size_t want = (bytes > (1u << 20) ? bytes : (1u << 20)) + 2 * d->pinned_bytes;
-        if(ensure_staging(d, want)) return 1;
-        if(d->pinned) HIP_TRY(hipHostFree(d->pinned));
-        d->pinned = nullptr;
-        d->pinned_bytes = 0;
-        HIP_TRY(hipHostMalloc((void **)&d->pinned, want, hipHostMallocDefault));
-        d->pinned_bytes = want;
+        const size_t want = (bytes > (1u << 20) ? bytes : (1u << 20)) + 2 * d->pinned.bytes();
+        if(d->staging.reserve(want) || d->pinned.reserve(want)) return 1;
     }
-    *dev = (char *)d->staging + d->io_off;
-    *pin = d->pinned + d->io_off;
+    *dev = (char *)d->staging.get() + d->io_off;
+    *pin = d->pinned.get() + d->io_off;
     d->io_off += bytes;
     return 0;
 }
@@ -316,15 +389,9 @@ int drain_spans(ilqg_dev *d) {
 inline dim3 grid1(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 
 // the plants' buffers (ilqg_dev_plant_begin makes them anew for every loop; the caller has synchronised)
-void plant_release(ilqg_dev *d) {
-    if(d->plant_xp) hipFree(d->plant_xp);
-    if(d->plant_cost) hipFree(d->plant_cost);
-    if(d->plant_values) hipFree(d->plant_values);
-    if(d->plant_dist) hipFree(d->plant_dist);
-    if(d->plant_failed) hipFree(d->plant_failed);
-    d->plant_xp = d->plant_cost = d->plant_values = d->plant_dist = nullptr;
-    d->plant_failed = nullptr;
+int plant_release(ilqg_dev *d) {
     d->plant_named = false;
+    return d->plant_xp.release() | d->plant_cost.release() | d->plant_values.release() | d->plant_dist.release() | d->plant_failed.release();
 }
 
 }  // namespace
@@ -364,7 +431,7 @@ static bool step_rows_into(Map &m, const ilqg_dev_t *d) {  // (a template: the m
     bool any = false;
     if constexpr(N_STEP_PARAMS > 0) {
         for(int s = 0; s < N_STEP_PARAMS; s++) {
-            m.rows[s] = d->sr_on[s] ? d->sr_rows[s] : nullptr;
+            m.rows[s] = d->sr_on[s] ? d->sr_rows[s].get() : nullptr;
             any = any || d->sr_on[s];
         }
     }
@@ -421,7 +488,7 @@ int ilqg_dev_create(ilqg_dev_t **out, int device, int batch, int n_hor) {
         return 1;
     }
     HIP_TRY(hipSetDevice(device));
-    ilqg_dev *d = new ilqg_dev();  // value-initialised: every pointer and handle is null until it is acquired
+    ilqg_dev *d = new ilqg_dev();  // value-initialised: every handle, view, flag and count is null until dev_fill or a call sets it
     if(dev_fill(d, device, batch, n_hor)) {
         const std::string why = g_err;
         ilqg_dev_destroy(d);  // releases whatever the failed attempt had acquired
@@ -437,33 +504,7 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
     d->B = batch;
     d->Bp = (batch + WAVE - 1) / WAVE * WAVE;
     d->N = n_hor;
-    d->staging = nullptr;
-    d->staging_bytes = 0;
-    d->io_deferred = false;
-    d->io_off = 0;
-    d->pinned = nullptr;
-    d->pinned_bytes = 0;
-    d->timing = false;
     d->loc_set = -1;
-    memset(d->t_ms, 0, sizeof(d->t_ms));
-    memset(d->t_n, 0, sizeof(d->t_n));
-    memset(d->t_busy, 0, sizeof(d->t_busy));
-    memset(&d->P, 0, sizeof(d->P));
-    memset(&d->O, 0, sizeof(d->O));
-    memset(&d->pv, 0, sizeof(d->pv));
-    d->pb_values = nullptr;
-    d->pb_bytes = 0;
-    d->pb_on = false;
-    for(int s = 0; s < ilqg_dev::SR; s++) {
-        d->sr_rows[s] = nullptr;
-        d->sr_bytes[s] = 0;
-        d->sr_on[s] = false;
-        d->win_future[s] = nullptr;
-        d->win_bytes[s] = 0;
-        d->win_given[s] = false;
-    }
-    d->win_rounds = d->win_steps = 0;
-    d->rows_on = false;
     d->P.B = d->B;
     d->P.Bp = d->Bp;
     d->P.N = d->N;
@@ -480,7 +521,6 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
     d->env.no_dma = getenv("ILQG_NO_DMA") != nullptr;
     d->env.no_rollout_parts = getenv("ILQG_NO_ROLLOUT_PARTS") != nullptr;
     d->env.quad_spec = !(getenv("ILQG_QUAD_SPEC") != nullptr && atoi(getenv("ILQG_QUAD_SPEC")) == 0);  // on unless ILQG_QUAD_SPEC=0
-    memset(&d->scratch, 0, sizeof(d->scratch));
 #if ILQG_WAVE_MAP
     d->scratch.derivs_f = uses_scratch(k_derivs_wave<FACTORED>);
     d->scratch.derivs_g = uses_scratch(k_derivs_wave<false>);
@@ -527,16 +567,8 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
 #endif
-    d->chunk = 0;
-    d->own_chunk = 0;
-    d->shared = nullptr;
-    d->per_step_params = false;
-    d->work_consts = false;
-    d->work_factored = false;
-    d->half_consts[0] = d->half_consts[1] = false;
     // (the second stream is the wave mapping's chunk pipeline; the lane mapping does not make one: the streams of a process
     // share four hardware queues, and with two streams per context the four groups of a batch sit on two of them in pairs)
-    d->stream2 = nullptr;
     if(WAVE_MAP || getenv("ILQG_SECOND_STREAM")) HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d->fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d->join, hipEventDisableTiming));
@@ -599,42 +631,37 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
             }
             d->chunk = (int)(c > (size_t)d->B ? (size_t)d->B : c);
 #endif
-            d->P.f[f] = nullptr;
             continue;
         }
-        if(nom_column(f) >= 0 && !has_tiled_copy(f) && !has_tiled_scratch(f)) {  // columns of the packed records only
-            d->P.f[f] = nullptr;
-            continue;
-        }
+        if(nom_column(f) >= 0 && !has_tiled_copy(f) && !has_tiled_scratch(f)) continue;  // columns of the packed records only
         const FieldInfo fi = field_info(f);
         const size_t bytes = (size_t)field_steps(d, f) * fi.wd * d->Bp * sizeof(double);
-        HIP_TRY(hipMalloc((void **)&d->P.f[f], bytes));
+        if(repoint(d->P.f[f], d->f[f], d->f[f].reserve(bytes))) return 1;
         HIP_TRY(hipMemsetAsync(d->P.f[f], 0, bytes, d->stream));
     }
     {
         const size_t bytes = (size_t)d->Bp * (d->N + 1) * RN * sizeof(double);
-        HIP_TRY(hipMalloc((void **)&d->P.nom, bytes));
+        if(repoint(d->P.nom, d->nom, d->nom.reserve(bytes))) return 1;
         HIP_TRY(hipMemsetAsync(d->P.nom, 0, bytes, d->stream));
     }
     for(int f = 0; f < ILQG_I_COUNT; f++) {
         const size_t bytes = (size_t)int_field_width(f) * d->Bp * sizeof(int);
-        HIP_TRY(hipMalloc((void **)&d->P.i[f], bytes));
+        if(repoint(d->P.i[f], d->i[f], d->i[f].reserve(bytes))) return 1;
         HIP_TRY(hipMemsetAsync(d->P.i[f], 0, bytes, d->stream));
     }
-    HIP_TRY(hipMalloc((void **)&d->P.derivs_failed, d->Bp * sizeof(int)));
+    if(repoint(d->P.derivs_failed, d->derivs_failed, d->derivs_failed.reserve(d->Bp * sizeof(int)))) return 1;
     HIP_TRY(hipMemsetAsync(d->P.derivs_failed, 0, d->Bp * sizeof(int), d->stream));
-    HIP_TRY(hipMalloc((void **)&d->counter, sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&d->queues, 2 * QUEUE_CELL * sizeof(int)));  // one cell per stream of the chunk pipeline
+    if(d->counter.reserve(sizeof(int))) return 1;
+    if(d->queues.reserve(2 * QUEUE_CELL * sizeof(int))) return 1;  // one cell per stream of the chunk pipeline
     {
         int cus = 0;
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         d->cus = cus > 0 ? cus : 256;
     }
-    HIP_TRY(hipMalloc((void **)&d->P.pending, d->Bp * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&d->P.n_pending, sizeof(int)));
+    if(repoint(d->P.pending, d->pending_list, d->pending_list.reserve(d->Bp * sizeof(int)))) return 1;
+    if(repoint(d->P.n_pending, d->n_pending, d->n_pending.reserve(sizeof(int)))) return 1;
     HIP_TRY(hipMemsetAsync(d->P.n_pending, 0, sizeof(int), d->stream));
     d->P.n_pending_next = d->P.n_pending;
-    d->P.p = nullptr;
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
@@ -649,9 +676,9 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
         hipEventDestroy(s.b);
     }
     for(hipEvent_t e : d->event_pool) hipEventDestroy(e);
-    for(int f = 0; f < ILQG_F_COUNT; f++)
-        if(d->P.f[f]) hipFree(d->P.f[f]);
-    if(d->P.work) hipFree(d->P.work);
+    // Memory goes HERE, in front of the streams, in this one statement — not in the members' destructors, which run at the
+    // `delete` below, behind hipStreamDestroy: the order of this function is part of what it does.
+    static_cast<DevBuffers &>(*d) = DevBuffers();
 #if ILQG_WAVE_MAP
     if(d->shared && --d->shared->refs == 0) {  // the last context on the device: release the shared work buffer
         hipFree(d->shared->buf);
@@ -659,34 +686,7 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
         memset(d->shared, 0, sizeof(SharedWork));
     }
 #endif
-    if(d->P.nom) hipFree(d->P.nom);
-    for(int f = 0; f < ILQG_I_COUNT; f++)
-        if(d->P.i[f]) hipFree(d->P.i[f]);
-    if(d->P.derivs_failed) hipFree(d->P.derivs_failed);
-    if(d->counter) hipFree(d->counter);
-    if(d->queues) hipFree(d->queues);
     if(g_spec_last == d) g_spec_last = nullptr;
-    if(d->spec_ints) hipFree(d->spec_ints);
-    if(d->spec_doubles) hipFree(d->spec_doubles);
-    if(d->P.cand) hipFree(d->P.cand);
-    if(d->P.cand1) hipFree(d->P.cand1);
-    if(d->P.xpl) hipFree(d->P.xpl);
-    if(d->P.upl) hipFree(d->P.upl);
-    if(d->P.pending) hipFree(d->P.pending);
-    if(d->P.n_pending) hipFree(d->P.n_pending);
-    if(d->log_x) hipFree(d->log_x);
-    if(d->log_u) hipFree(d->log_u);
-    if(d->log_c) hipFree(d->log_c);
-    plant_release(d);
-    if(d->pb_values) hipFree(d->pb_values);
-    for(int s = 0; s < ilqg_dev::SR; s++)
-        if(d->sr_rows[s]) hipFree(d->sr_rows[s]);
-    for(int s = 0; s < ilqg_dev::SR; s++)
-        if(d->win_future[s]) hipFree(d->win_future[s]);
-    for(double *p : d->param_bufs) hipFree(p);
-    if(d->P.p) hipFree(d->P.p);
-    if(d->staging) hipFree(d->staging);
-    if(d->pinned) hipHostFree(d->pinned);
     if(d->stream) hipStreamDestroy(d->stream);
     if(d->stream2) hipStreamDestroy(d->stream2);
     if(d->fork) hipEventDestroy(d->fork);
@@ -703,10 +703,8 @@ void ilqg_dev_destroy(ilqg_dev_t *d) {
 int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const double *const *values) {
     HIP_TRY(hipSetDevice(d->device));
     HIP_TRY(hipStreamSynchronize(d->stream));
-    for(double *p : d->param_bufs) hipFree(p);
     d->param_bufs.clear();
-    if(d->P.p) hipFree(d->P.p);
-    d->P.p = nullptr;
+    if(repoint(d->P.p, d->param_table, d->param_table.release())) return 1;
     std::vector<double *> ptrs(n_params > 0 ? n_params : 1, nullptr);
     {
         constexpr int want[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
@@ -727,13 +725,13 @@ int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const dou
     }
     for(int i = 0; i < n_params; i++) {
         const int sz = sizes[i] == -1 ? d->N + 1 : sizes[i];
-        double *buf = nullptr;
-        HIP_TRY(hipMalloc((void **)&buf, sz * sizeof(double)));
-        HIP_TRY(hipMemcpy(buf, values[i], sz * sizeof(double), hipMemcpyHostToDevice));
-        d->param_bufs.push_back(buf);
-        ptrs[i] = buf;
+        Buffer<double> buf;
+        if(buf.reserve(sz * sizeof(double))) return 1;
+        HIP_TRY(hipMemcpy(buf.get(), values[i], sz * sizeof(double), hipMemcpyHostToDevice));
+        ptrs[i] = buf.get();
+        d->param_bufs.push_back(std::move(buf));
     }
-    HIP_TRY(hipMalloc((void **)&d->P.p, ptrs.size() * sizeof(double *)));
+    if(repoint(d->P.p, d->param_table, d->param_table.reserve(ptrs.size() * sizeof(double *)))) return 1;
     HIP_TRY(hipMemcpy(d->P.p, ptrs.data(), ptrs.size() * sizeof(double *), hipMemcpyHostToDevice));
     d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
     return 0;
@@ -755,6 +753,14 @@ static void rows_refresh(ilqg_dev_t *d) {
     d->rows_map = m;
     d->rows_on = d->pb_on || steps;
 }
+// the table's buffer holds `bytes`; one that has to grow is out of use, and no longer described, before it is released
+// (launches in flight read the old buffer: reserve drains the context's stream)
+static int table_buffer(ilqg_dev_t *d, size_t bytes) {
+    if(bytes <= d->pb_values.bytes()) return 0;
+    d->pb_on = false;
+    rows_refresh(d);
+    return d->pb_values.reserve(bytes, d->stream);
+}
 int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, const double *values, int on_device) {
     HIP_TRY(hipSetDevice(d->device));
     if(WAVE_MAP) {
@@ -774,17 +780,8 @@ int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, cons
     PolicyParamMap map;
     if(!policy_param_map(n_named, named, values, map)) return 1;
     const size_t bytes = (size_t)d->B * (size_t)map.W * sizeof(double);
-    if(bytes > d->pb_bytes) {
-        HIP_TRY(hipStreamSynchronize(d->stream));  // (launches in flight read the old buffer)
-        if(d->pb_values) HIP_TRY(hipFree(d->pb_values));
-        d->pb_values = nullptr;
-        d->pb_bytes = 0;
-        d->pb_on = false;
-        rows_refresh(d);
-        HIP_TRY(hipMalloc((void **)&d->pb_values, bytes));
-        d->pb_bytes = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(d->pb_values, values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+    if(table_buffer(d, bytes)) return 1;
+    HIP_TRY(hipMemcpyAsync(d->pb_values.get(), values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
     if(!on_device) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's array is its own again
     d->pb_map = map;
     d->pb_on = true;
@@ -805,18 +802,13 @@ static int step_slot(int index) {
 // the buffer of slot s holds Bp rows, the rows beyond B zero (no lane reads them; a stray one would read zeros, not beyond)
 static int step_rows_buffer(ilqg_dev_t *d, int s) {
     const size_t n = (size_t)d->N + 1, bytes = (size_t)d->Bp * n * sizeof(double);
-    if(bytes > d->sr_bytes[s]) {
-        HIP_TRY(hipStreamSynchronize(d->stream));  // (launches in flight read the old buffer)
-        if(d->sr_rows[s]) HIP_TRY(hipFree(d->sr_rows[s]));
-        d->sr_rows[s] = nullptr;
-        d->sr_bytes[s] = 0;
+    if(bytes > d->sr_rows[s].bytes()) {  // (as table_buffer)
         d->sr_on[s] = false;
         rows_refresh(d);
-        HIP_TRY(hipMalloc((void **)&d->sr_rows[s], bytes));
-        d->sr_bytes[s] = bytes;
+        if(d->sr_rows[s].reserve(bytes, d->stream)) return 1;
     }
     if(!d->sr_on[s] && d->Bp > d->B)
-        HIP_TRY(hipMemsetAsync(d->sr_rows[s] + (size_t)d->B * n, 0, (size_t)(d->Bp - d->B) * n * sizeof(double), d->stream));
+        HIP_TRY(hipMemsetAsync(d->sr_rows[s].get() + (size_t)d->B * n, 0, (size_t)(d->Bp - d->B) * n * sizeof(double), d->stream));
     return 0;
 }
 int ilqg_dev_set_param_steps_batch(ilqg_dev_t *d, int index, const double *values, int on_device) {
@@ -838,7 +830,7 @@ int ilqg_dev_set_param_steps_batch(ilqg_dev_t *d, int index, const double *value
     }
     if(step_rows_buffer(d, s)) return 1;
     const size_t bytes = (size_t)d->B * ((size_t)d->N + 1) * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(d->sr_rows[s], values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->sr_rows[s].get(), values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d->stream));
     if(!on_device) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's array is its own again
     d->sr_on[s] = true;
     rows_refresh(d);
@@ -852,7 +844,7 @@ int ilqg_dev_get_param_steps_batch(ilqg_dev_t *d, int index, double *rows) {
         g_err = "get_param_steps_batch: the parameter has no rows per trajectory in this context";
         return 1;
     }
-    HIP_TRY(hipMemcpyAsync(rows, d->sr_rows[s], (size_t)d->B * ((size_t)d->N + 1) * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(rows, d->sr_rows[s].get(), (size_t)d->B * ((size_t)d->N + 1) * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
@@ -863,7 +855,7 @@ int ilqg_dev_get_params_batch(ilqg_dev_t *d, double *rows) {
         g_err = "get_params_batch: the context has no per-trajectory parameters";
         return 1;
     }
-    HIP_TRY(hipMemcpyAsync(rows, d->pb_values, (size_t)d->B * (size_t)d->pb_map.W * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(rows, d->pb_values.get(), (size_t)d->B * (size_t)d->pb_map.W * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
@@ -947,7 +939,7 @@ static int own_work(ilqg_dev *d) {
                 "record transfers need a smaller batch; ilqg_dev_iterate / ilqg_dev_backward(mode 2) work in chunks";
         return 1;
     }
-    HIP_TRY(hipMalloc((void **)&d->P.work, (size_t)d->B * per_traj));
+    if(repoint(d->P.work, d->work, d->work.reserve((size_t)d->B * per_traj))) return 1;
     HIP_TRY(hipMemsetAsync(d->P.work, 0, (size_t)d->B * per_traj, d->stream));
     d->own_chunk = d->B;
     d->work_consts = false;
@@ -1126,7 +1118,7 @@ int ilqg_dev_io_end(ilqg_dev_t *d) {
 #define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...)                                                                    \
     do {                                                                                                                                \
         if((d)->rows_on)                                                                                                                \
-            hipLaunchKernelGGL((ILQG_OPEN_NAME ROWS), grid, block, lds, stream, __VA_ARGS__, (const double *)(d)->pb_values, (d)->rows_map); \
+            hipLaunchKernelGGL((ILQG_OPEN_NAME ROWS), grid, block, lds, stream, __VA_ARGS__, (const double *)(d)->pb_values.get(), (d)->rows_map); \
         else                                                                                                                            \
             hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__);                                         \
     } while(0)
@@ -1134,35 +1126,6 @@ int ilqg_dev_io_end(ilqg_dev_t *d) {
 #define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...) hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__)
 #endif
 #define LAUNCH_PV(d, K, ...) LAUNCH_PV_AS(d, (ILQG_OPEN_NAME K>), (ILQG_OPEN_NAME K, ILQG_PV_ROWS>), __VA_ARGS__)
-
-// (re)allocates a device buffer that must hold `need` bytes; what is queued on `rs` may still use the old one
-static int ensure_buffer(ilqg_dev_t *d, double **buf, size_t *have, size_t need, hipStream_t rs) {
-    if(*have >= need) return 0;
-    HIP_TRY(hipStreamSynchronize(rs));
-    if(*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc((void **)buf, need));
-    *have = need;
-    return 0;
-}
-
-// the same for a buffer the caller can do without: 2 = the device does not have the memory (the error is cleared)
-static int try_buffer(ilqg_dev_t *d, double **buf, size_t *have, size_t need, hipStream_t rs) {
-    if(*have >= need) return 0;
-    HIP_TRY(hipStreamSynchronize(rs));
-    if(*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    // (ILQG_TEST_NO_PLANES: the tests' way to a device that is out of memory)
-    if(getenv("ILQG_TEST_NO_PLANES") || hipMalloc((void **)buf, need) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        return 2;
-    }
-    *have = need;
-    return 0;
-}
 
 // ls_keep = 2: every current trajectory back into the arrays X / U (the host is about to read or write them, an
 // initial roll-out is about to store there, or a search that does not keep its roll-outs follows)
@@ -1295,15 +1258,12 @@ int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps) {
         return 1;
     }
     HIP_TRY(hipStreamSynchronize(d->stream));
-    if(d->log_x) HIP_TRY(hipFree(d->log_x));
-    if(d->log_u) HIP_TRY(hipFree(d->log_u));
-    if(d->log_c) HIP_TRY(hipFree(d->log_c));
-    d->log_x = d->log_u = d->log_c = nullptr;
     d->log_rounds = d->log_steps = 0;
     const size_t per = (size_t)d->B * rounds * steps;
-    HIP_TRY(hipMalloc((void **)&d->log_x, per * NX * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&d->log_u, per * NU * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&d->log_c, (size_t)d->B * rounds * sizeof(double)));
+    if(d->log_x.renew(per * NX * sizeof(double)) || d->log_u.renew(per * NU * sizeof(double)) || d->log_c.renew((size_t)d->B * rounds * sizeof(double))) {
+        (void)(d->log_x.release() | d->log_u.release() | d->log_c.release());  // all or none: no log, as before the first begin
+        return 1;
+    }
     d->log_rounds = rounds;
     d->log_steps = steps;
     return 0;
@@ -1311,14 +1271,14 @@ int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps) {
 
 int ilqg_dev_log_append(ilqg_dev_t *d, int round) {
     HIP_TRY(hipSetDevice(d->device));
-    if(!d->log_x || round < 0 || round >= d->log_rounds) {
+    if(!d->log_x.get() || round < 0 || round >= d->log_rounds) {
         g_err = "ilqg_dev_log_append: no such round in the log (ilqg_dev_log_begin)";
         return 1;
     }
     {
         Timed t(d, ILQG_K_LOG);
-        hipLaunchKernelGGL(k_log_steps, grid1((size_t)d->B * d->log_steps * (NX + NU), 256), dim3(256), 0, d->stream, d->P, d->log_x,
-                           d->log_u, d->log_c, round, d->log_rounds, d->log_steps);
+        hipLaunchKernelGGL(k_log_steps, grid1((size_t)d->B * d->log_steps * (NX + NU), 256), dim3(256), 0, d->stream, d->P, d->log_x.get(),
+                           d->log_u.get(), d->log_c.get(), round, d->log_rounds, d->log_steps);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1326,14 +1286,14 @@ int ilqg_dev_log_append(ilqg_dev_t *d, int round) {
 
 int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost) {
     HIP_TRY(hipSetDevice(d->device));
-    if(!d->log_x) {
+    if(!d->log_x.get()) {
         g_err = "ilqg_dev_log_read: no log (ilqg_dev_log_begin)";
         return 1;
     }
     const size_t per = (size_t)d->B * d->log_rounds * d->log_steps;
-    if(x) HIP_TRY(hipMemcpyAsync(x, d->log_x, per * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(u) HIP_TRY(hipMemcpyAsync(u, d->log_u, per * NU * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(cost) HIP_TRY(hipMemcpyAsync(cost, d->log_c, (size_t)d->B * d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(x) HIP_TRY(hipMemcpyAsync(x, d->log_x.get(), per * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(u) HIP_TRY(hipMemcpyAsync(u, d->log_u.get(), per * NU * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(cost) HIP_TRY(hipMemcpyAsync(cost, d->log_c.get(), (size_t)d->B * d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
@@ -1450,11 +1410,11 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
     if(d->rows_on && !map) {
         Timed t(d, ILQG_K_POLICY, roll_stream(d));
         hipLaunchKernelGGL((k_policy<false, const double *, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0,
-                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values, d->rows_map);
+                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values.get(), d->rows_map);
     } else if(d->rows_on) {
         Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
         hipLaunchKernelGGL((k_policy<true, const double *, PolicyParamMap, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0,
-                           roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values,
+                           roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values.get(),
                            d->rows_map, values, shared ? 1 : 0, *map);
     } else
 #endif
@@ -1561,28 +1521,26 @@ int ilqg_dev_plant_begin(ilqg_dev_t *d, int rounds, int steps, const double *x_p
     }
     if(ilqg_dev_log_begin(d, rounds, steps)) return 1;  // (synchronises the context's stream)
     if(d->roll) HIP_TRY(hipStreamSynchronize(d->roll));
-    plant_release(d);
+    if(plant_release(d)) return 1;
     const size_t B = (size_t)d->B, per = B * (size_t)rounds * (size_t)steps;
-    HIP_TRY(hipMalloc((void **)&d->plant_xp, B * NX * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&d->plant_failed, B * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&d->plant_cost, B * (size_t)rounds * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(d->plant_failed, 0, B * sizeof(int), d->stream));
+    if(d->plant_xp.renew(B * NX * sizeof(double)) || d->plant_failed.renew(B * sizeof(int)) || d->plant_cost.renew(B * (size_t)rounds * sizeof(double)) ||
+       (n_named > 0 && d->plant_values.renew(B * (size_t)map.W * sizeof(double))) || (disturbance && d->plant_dist.renew(per * NX * sizeof(double)))) {
+        (void)plant_release(d);  // all or none: no plants, as before the first begin
+        return 1;
+    }
+    HIP_TRY(hipMemsetAsync(d->plant_failed.get(), 0, B * sizeof(int), d->stream));
     // (what a failed plant leaves unwritten reaches the host as zeros)
-    HIP_TRY(hipMemsetAsync(d->log_x, 0, per * NX * sizeof(double), d->stream));
-    HIP_TRY(hipMemsetAsync(d->log_u, 0, per * NU * sizeof(double), d->stream));
-    HIP_TRY(hipMemsetAsync(d->plant_cost, 0, B * (size_t)rounds * sizeof(double), d->stream));
+    HIP_TRY(hipMemsetAsync(d->log_x.get(), 0, per * NX * sizeof(double), d->stream));
+    HIP_TRY(hipMemsetAsync(d->log_u.get(), 0, per * NU * sizeof(double), d->stream));
+    HIP_TRY(hipMemsetAsync(d->plant_cost.get(), 0, B * (size_t)rounds * sizeof(double), d->stream));
     if(n_named > 0) {
         d->plant_map = map;
         d->plant_named = true;
-        HIP_TRY(hipMalloc((void **)&d->plant_values, B * (size_t)map.W * sizeof(double)));
-        HIP_TRY(hipMemcpyAsync(d->plant_values, values, B * (size_t)map.W * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        HIP_TRY(hipMemcpyAsync(d->plant_values.get(), values, B * (size_t)map.W * sizeof(double), hipMemcpyHostToDevice, d->stream));
     }
-    if(disturbance) {
-        HIP_TRY(hipMalloc((void **)&d->plant_dist, per * NX * sizeof(double)));
-        HIP_TRY(hipMemcpyAsync(d->plant_dist, disturbance, per * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    }
-    if(x_plant) HIP_TRY(hipMemcpyAsync(d->plant_xp, x_plant, B * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    else if(launch_head(d, 1, d->plant_xp, nullptr, nullptr, nullptr, nullptr)) return 1;  // x_0 of every plan, where it lives
+    if(disturbance) HIP_TRY(hipMemcpyAsync(d->plant_dist.get(), disturbance, per * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    if(x_plant) HIP_TRY(hipMemcpyAsync(d->plant_xp.get(), x_plant, B * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    else if(launch_head(d, 1, d->plant_xp.get(), nullptr, nullptr, nullptr, nullptr)) return 1;  // x_0 of every plan, where it lives
     HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
     return 0;
 }
@@ -1590,7 +1548,7 @@ int ilqg_dev_plant_begin(ilqg_dev_t *d, int rounds, int steps, const double *x_p
 int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
     HIP_TRY(hipSetDevice(d->device));
     NEED_PARAMS(d);
-    if(!d->plant_xp || !d->log_x || round < 0 || round >= d->log_rounds) {
+    if(!d->plant_xp.get() || !d->log_x.get() || round < 0 || round >= d->log_rounds) {
         g_err = "ilqg_dev_plant_advance: no such round (ilqg_dev_plant_begin)";
         return 1;
     }
@@ -1601,46 +1559,46 @@ int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
 #if !ILQG_WAVE_MAP  // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
         if(d->rows_on && d->plant_named)
             hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK),
-                               dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed,
-                               (const double *)d->plant_dist, round * steps, rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c,
-                               (const double *)d->pb_values, d->rows_map, (const double *)d->plant_values, d->plant_map);
+                               dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(),
+                               (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get(),
+                               (const double *)d->pb_values.get(), d->rows_map, (const double *)d->plant_values.get(), d->plant_map);
         else if(d->rows_on)
             hipLaunchKernelGGL((k_plant<false, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d),
-                               d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps,
-                               rounds * steps, round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c, (const double *)d->pb_values, d->rows_map);
+                               d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(), (const double *)d->plant_dist.get(), round * steps,
+                               rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get(), (const double *)d->pb_values.get(), d->rows_map);
         else
 #endif
         if(d->plant_named)
             hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
-                               d->pv, steps, feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps, rounds * steps,
-                               round, rounds, d->log_x, d->log_u, d->plant_cost, d->log_c, (const double *)d->plant_values, d->plant_map);
+                               d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(), (const double *)d->plant_dist.get(), round * steps, rounds * steps,
+                               round, rounds, d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get(), (const double *)d->plant_values.get(), d->plant_map);
         else
             hipLaunchKernelGGL(k_plant<false>, grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps,
-                               feedback ? 1 : 0, d->plant_xp, d->plant_failed, (const double *)d->plant_dist, round * steps, rounds * steps, round, rounds,
-                               d->log_x, d->log_u, d->plant_cost, d->log_c);
+                               feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(), (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds,
+                               d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get());
     }
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
 }
 
 int ilqg_dev_plant_put_x0(ilqg_dev_t *d) {
-    if(!d->plant_xp) {
+    if(!d->plant_xp.get()) {
         g_err = "ilqg_dev_plant_put_x0: no plants (ilqg_dev_plant_begin)";
         return 1;
     }
-    return ilqg_dev_put_x0_device(d, d->plant_xp);
+    return ilqg_dev_put_x0_device(d, d->plant_xp.get());
 }
 
 int ilqg_dev_plant_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok) {
     HIP_TRY(hipSetDevice(d->device));
-    if(!d->plant_xp || !d->log_x) {
+    if(!d->plant_xp.get() || !d->log_x.get()) {
         g_err = "ilqg_dev_plant_read: no plants (ilqg_dev_plant_begin)";
         return 1;
     }
     const size_t B = (size_t)d->B;
-    if(x_plant) HIP_TRY(hipMemcpyAsync(x_plant, d->plant_xp, B * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(cost_applied) HIP_TRY(hipMemcpyAsync(cost_applied, d->plant_cost, B * (size_t)d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(ok) HIP_TRY(hipMemcpyAsync(ok, d->plant_failed, B * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    if(x_plant) HIP_TRY(hipMemcpyAsync(x_plant, d->plant_xp.get(), B * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(cost_applied) HIP_TRY(hipMemcpyAsync(cost_applied, d->plant_cost.get(), B * (size_t)d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(ok) HIP_TRY(hipMemcpyAsync(ok, d->plant_failed.get(), B * sizeof(int), hipMemcpyDeviceToHost, d->stream));
     if(ilqg_dev_log_read(d, x, u, plan_cost)) return 1;  // (waits for the context's stream)
     if(ok)
         for(size_t b = 0; b < B; b++) ok[b] = ok[b] ? 0 : 1;  // the device keeps failure flags
@@ -1710,7 +1668,7 @@ int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail
     }
     {
         Timed t(d, ILQG_K_SHIFT_PARAM);
-        hipLaunchKernelGGL(k_shift_param, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index], d->N + 1, steps, tail_dev);
+        hipLaunchKernelGGL(k_shift_param, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index].get(), d->N + 1, steps, tail_dev);
     }
     HIP_TRY(hipGetLastError());
     d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
@@ -1740,7 +1698,7 @@ int ilqg_dev_shift_param_batch(ilqg_dev_t *d, int index, int steps, const double
     }
     {
         Timed t(d, ILQG_K_SHIFT_PARAM_ROWS);
-        hipLaunchKernelGGL(k_shift_param_rows, dim3(d->B), dim3(PARAM_BLOCK), 0, d->stream, d->sr_rows[s], d->N + 1, steps, tail_dev);
+        hipLaunchKernelGGL(k_shift_param_rows, dim3(d->B), dim3(PARAM_BLOCK), 0, d->stream, d->sr_rows[s].get(), d->N + 1, steps, tail_dev);
     }
     HIP_TRY(hipGetLastError());
     return (tail && !on_device) ? io_done(d) : 0;
@@ -1773,8 +1731,8 @@ static int windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *con
             d->win_given[s] = f != nullptr;
             if(!f) continue;
             const size_t bytes = (d->sr_on[s] ? (size_t)d->B : (size_t)1) * per * sizeof(double);
-            if(ensure_buffer(d, &d->win_future[s], &d->win_bytes[s], bytes, d->stream)) return 1;
-            HIP_TRY(hipMemcpyAsync(d->win_future[s], f, bytes, hipMemcpyHostToDevice, d->stream));
+            if(d->win_future[s].reserve(bytes, d->stream)) return 1;
+            HIP_TRY(hipMemcpyAsync(d->win_future[s].get(), f, bytes, hipMemcpyHostToDevice, d->stream));
             sent = true;
         }
         if(sent) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
@@ -1789,9 +1747,9 @@ static int windows_move(ilqg_dev_t *d, int round) {
         int most = 1;
         for(int s = 0; s < n_slots; s++) {
             const bool rows = d->sr_on[s];
-            S.w[s].base = rows ? d->sr_rows[s] : d->param_bufs[slot_index(s)];
+            S.w[s].base = rows ? d->sr_rows[s].get() : d->param_bufs[slot_index(s)].get();
             S.w[s].rows = rows ? d->B : 1;
-            S.w[s].future = d->win_given[s] ? d->win_future[s] : nullptr;
+            S.w[s].future = d->win_given[s] ? d->win_future[s].get() : nullptr;
             S.w[s].stride = rows ? (size_t)d->win_rounds * (size_t)d->win_steps : 0;
             if(S.w[s].rows > most) most = S.w[s].rows;
         }
@@ -1918,7 +1876,7 @@ static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_
         DevPtrs P = d->P;
         P.work = reinterpret_cast<trajEl_t *>(work + (size_t)h * half_cap * d->N * stride);
         P.work_stride = stride;
-        P.queue = d->queues + h * QUEUE_CELL;
+        P.queue = d->queues.get() + h * QUEUE_CELL;
         if(do_derivs) {
             const bool derivs_scratch = fact ? d->scratch.derivs_f : d->scratch.derivs_g;
             const size_t total = (size_t)cnt * (d->N + 1);
@@ -1966,8 +1924,8 @@ static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_
             if(spec) {  // (a device that cannot spare the rows' gains buffers — 1.1 MB per row at N = 1 000 — sweeps without)
                 const int per_wg = 4 * QUAD_WAVES;
                 const int wgs = (cnt + per_wg - 1) / per_wg, rows = (wgs < d->cus ? wgs : d->cus) * per_wg;
-                const int ri = try_buffer(d, &d->spec_ints, &d->spec_ints_bytes, ((size_t)(3 + SPEC_ATTEMPTS) * d->B + rows) * sizeof(unsigned), st);
-                const int rd = ri ? ri : try_buffer(d, &d->spec_doubles, &d->spec_doubles_bytes, (size_t)rows * (SPEC_SLOTS + (size_t)d->N * SPEC_GW) * sizeof(double), st);
+                const int ri = d->spec_ints.try_reserve(((size_t)(3 + SPEC_ATTEMPTS) * d->B + rows) * sizeof(unsigned), st);
+                const int rd = ri ? ri : d->spec_doubles.try_reserve((size_t)rows * (SPEC_SLOTS + (size_t)d->N * SPEC_GW) * sizeof(double), st);
                 if(ri == 1 || rd == 1) return 1;
                 if(ri == 2 || rd == 2) spec = false;
             }
@@ -1982,15 +1940,15 @@ static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_
                        const int wgs = (cnt + per_wg - 1) / per_wg;  // one workgroup per CU at a time
                        if(spec) {  // rows whose queue is used up run other trajectories' next attempts (k_backward_quad, SPEC)
                            const int grid = wgs < d->cus ? wgs : d->cus, rows = grid * per_wg;
-                           unsigned *w = reinterpret_cast<unsigned *>(d->spec_ints);
+                           unsigned *w = d->spec_ints.get();
                            const size_t nb = (size_t)d->B;
                            P.spec_word = w;
                            P.spec_done = w + nb;
                            P.spec_out = w + 2 * nb;
                            P.spec_best = w + (2 + SPEC_ATTEMPTS) * nb;
                            P.spec_row_b = reinterpret_cast<int *>(w + (3 + SPEC_ATTEMPTS) * nb);
-                           P.spec_res = d->spec_doubles;
-                           P.spec_gains = d->spec_doubles + (size_t)rows * SPEC_SLOTS;
+                           P.spec_res = d->spec_doubles.get();
+                           P.spec_gains = d->spec_doubles.get() + (size_t)rows * SPEC_SLOTS;
                            P.spec_rows = rows;
                            g_spec_last = d;
                            (void)hipMemsetAsync(w, 0, (2 + SPEC_ATTEMPTS) * nb * sizeof(unsigned), q);
@@ -2108,13 +2066,11 @@ int ilqg_dev_search(ilqg_dev_t *d) {
             if(all_home(d)) return 1;
             d->P.plane_n = s1;
         }
-        const int rx = try_buffer(d, &d->P.xpl, &d->xpl_bytes, 2 * (size_t)s1 * xplane * sizeof(double), rs);
-        const int ru = rx ? rx : try_buffer(d, &d->P.upl, &d->upl_bytes, 2 * (size_t)s1 * uplane * sizeof(double), rs);
+        const int rx = repoint(d->P.xpl, d->xpl, d->xpl.try_reserve(2 * (size_t)s1 * xplane * sizeof(double), rs));
+        const int ru = rx ? rx : repoint(d->P.upl, d->upl, d->upl.try_reserve(2 * (size_t)s1 * uplane * sizeof(double), rs));
         if(rx == 1 || ru == 1) return 1;
         if(rx == 2 || ru == 2) {
-            if(d->P.xpl) HIP_TRY(hipFree(d->P.xpl));
-            d->P.xpl = nullptr;
-            d->xpl_bytes = 0;
+            if(repoint(d->P.xpl, d->xpl, d->xpl.release())) return 1;
             keep_all = false;  // (all_home() below: nothing lives in a plane any more — there are none)
             d->loc_set = -1;
             HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
@@ -2126,8 +2082,7 @@ int ilqg_dev_search(ilqg_dev_t *d) {
         const int n2 = A - s1, set = (d->loc_set == 0) ? 1 : 0;
         d->P.xplane = xplane;
         d->P.uplane = uplane;
-        if(n2 > 0 && ensure_buffer(d, &d->P.cand, &d->cand_bytes, (size_t)d->Bp * n2 * (d->N + 1) * CAND_W * sizeof(double), rs))
-            return 1;
+        if(n2 > 0 && repoint(d->P.cand, d->cand, d->cand.reserve((size_t)d->Bp * n2 * (d->N + 1) * CAND_W * sizeof(double), rs))) return 1;
         if(!d->pending_zero) HIP_TRY(hipMemsetAsync(d->P.n_pending, 0, sizeof(int), rs));
         d->pending_zero = false;
         {
@@ -2180,8 +2135,8 @@ int ilqg_dev_search(ilqg_dev_t *d) {
         // launch needed two rounds of workgroups, 50 ms; the second stage alone fits one).
         const int n2 = A - s1;
         const size_t row = (size_t)d->Bp * (d->N + 1) * CAND_W * sizeof(double);
-        if(ensure_buffer(d, &d->P.cand1, &d->cand1_bytes, row * s1, rs)) return 1;
-        if(n2 > 0 && ensure_buffer(d, &d->P.cand, &d->cand_bytes, row * n2, rs)) return 1;
+        if(repoint(d->P.cand1, d->cand1, d->cand1.reserve(row * s1, rs))) return 1;
+        if(n2 > 0 && repoint(d->P.cand, d->cand, d->cand.reserve(row * n2, rs))) return 1;
         d->keep_first = true;
         launch_rollout(d, ROLL_SEARCH, ILQG_K_ROLLOUT_SEARCH, 0, s1, rs);
         d->keep_first = false;
@@ -2222,15 +2177,7 @@ int ilqg_dev_search(ilqg_dev_t *d) {
         // Second stage and the winner pass of the trajectories the first stage settled in ONE launch (ROLL_SECOND);
         // the grid covers the worst case, blocks beyond the pending count return at once.
         const int n2 = A - s1;
-        const size_t need = (size_t)d->Bp * n2 * (d->N + 1) * CAND_W * sizeof(double);
-        if(d->cand_bytes < need) {
-            HIP_TRY(hipStreamSynchronize(rs));
-            if(d->P.cand) HIP_TRY(hipFree(d->P.cand));
-            d->P.cand = nullptr;
-            d->cand_bytes = 0;
-            HIP_TRY(hipMalloc((void **)&d->P.cand, need));
-            d->cand_bytes = need;
-        }
+        if(repoint(d->P.cand, d->cand, d->cand.reserve((size_t)d->Bp * n2 * (d->N + 1) * CAND_W * sizeof(double), rs))) return 1;
         launch_rollout(d, ROLL_SECOND, ILQG_K_ROLLOUT_SEARCH2, s1, n2 + 1, rs);
         {
             Timed t(d, ILQG_K_SELECT, rs);
@@ -2317,8 +2264,8 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
         }
     HIP_TRY(hipStreamSynchronize(src->stream));
     if(io_flush(dst)) return 1;
-    if(ensure_staging(dst, 2 * (size_t)count * sizeof(int))) return 1;
-    int *idx = reinterpret_cast<int *>(dst->staging);
+    if(dst->staging.reserve(2 * (size_t)count * sizeof(int))) return 1;
+    int *idx = reinterpret_cast<int *>(dst->staging.get());
     HIP_TRY(hipMemcpyAsync(idx, to, (size_t)count * sizeof(int), hipMemcpyHostToDevice, dst->stream));
     HIP_TRY(hipMemcpyAsync(idx + count, from, (size_t)count * sizeof(int), hipMemcpyHostToDevice, dst->stream));
     hipLaunchKernelGGL(k_move_traj, grid1((size_t)count * (src->N + 1), 256), dim3(256), 0, dst->stream, dst->P, src->P, idx, idx + count, count,
@@ -2329,21 +2276,13 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
         bool same = dst->pb_on && dst->pb_map.W == src->pb_map.W;
         for(int j = 0; same && j < ILQG_PTOTAL; j++) same = dst->pb_map.src[j] == src->pb_map.src[j];
         if(!same) {
-            if(bytes > dst->pb_bytes) {
-                HIP_TRY(hipStreamSynchronize(dst->stream));
-                if(dst->pb_values) HIP_TRY(hipFree(dst->pb_values));
-                dst->pb_values = nullptr;
-                dst->pb_bytes = 0;
-                dst->pb_on = false;
-                HIP_TRY(hipMalloc((void **)&dst->pb_values, bytes));
-                dst->pb_bytes = bytes;
-            }
-            HIP_TRY(hipMemsetAsync(dst->pb_values, 0, bytes, dst->stream));  // (rows nothing has moved into yet)
+            if(table_buffer(dst, bytes)) return 1;
+            HIP_TRY(hipMemsetAsync(dst->pb_values.get(), 0, bytes, dst->stream));  // (rows nothing has moved into yet)
             dst->pb_map = src->pb_map;
             dst->pb_on = true;
         }
         rows_refresh(dst);
-        hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->pb_values, (const double *)src->pb_values, idx,
+        hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->pb_values.get(), (const double *)src->pb_values.get(), idx,
                            idx + count, count, (int)W);
         HIP_TRY(hipGetLastError());
     }
@@ -2352,11 +2291,11 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
         const size_t W = (size_t)src->N + 1;
         if(!dst->sr_on[s]) {  // (rows nothing has moved into yet are zero)
             if(step_rows_buffer(dst, s)) return 1;
-            HIP_TRY(hipMemsetAsync(dst->sr_rows[s], 0, (size_t)dst->B * W * sizeof(double), dst->stream));
+            HIP_TRY(hipMemsetAsync(dst->sr_rows[s].get(), 0, (size_t)dst->B * W * sizeof(double), dst->stream));
             dst->sr_on[s] = true;
             rows_refresh(dst);
         }
-        hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->sr_rows[s], (const double *)src->sr_rows[s], idx,
+        hipLaunchKernelGGL(k_move_rows, grid1((size_t)count * W, 256), dim3(256), 0, dst->stream, dst->sr_rows[s].get(), (const double *)src->sr_rows[s].get(), idx,
                            idx + count, count, (int)W);
         HIP_TRY(hipGetLastError());
     }
@@ -2372,11 +2311,11 @@ int ilqg_dev_sync(ilqg_dev_t *d) {
 
 int ilqg_dev_count_active(ilqg_dev_t *d, int *n_active) {
     HIP_TRY(hipSetDevice(d->device));
-    HIP_TRY(hipMemsetAsync(d->counter, 0, sizeof(int), d->stream));
+    HIP_TRY(hipMemsetAsync(d->counter.get(), 0, sizeof(int), d->stream));
     hipLaunchKernelGGL(k_count_active, grid1(d->Bp, 256), dim3(256), 0, d->stream, d->P.i[ILQG_I_STATUS], d->B,
-                       d->counter);
+                       d->counter.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(n_active, d->counter, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(n_active, d->counter.get(), sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }
@@ -2416,10 +2355,10 @@ int ilqg_dev_spec_words(unsigned *out, size_t max_words, size_t *count) {
     if(!d) return 0;
     HIP_TRY(hipSetDevice(d->device));
     HIP_TRY(hipDeviceSynchronize());
-    if(!d->spec_ints) return 0;
-    size_t n = d->spec_ints_bytes / sizeof(unsigned);
+    if(!d->spec_ints.get()) return 0;
+    size_t n = d->spec_ints.bytes() / sizeof(unsigned);
     if(n > max_words) n = max_words;
-    HIP_TRY(hipMemcpy(out, d->spec_ints, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d->spec_ints.get(), n * sizeof(unsigned), hipMemcpyDeviceToHost));
     *count = n;
     return 0;
 }
@@ -2491,39 +2430,33 @@ int ilqg_dev_get_timing(ilqg_dev_t *d, int kernel, int *launches, double *total_
 int ilqg_dev_dense(int device, int op, int shape, const double *in0, int n_in0, const double *in1, int n_in1,
                    const double *in2, int n_in2, double *out, int n_out, int *flag) {
     HIP_TRY(hipSetDevice(device));
-    double *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *dout = nullptr;
-    int *dflag = nullptr;
-    HIP_TRY(hipMalloc((void **)&d0, (n_in0 > 0 ? n_in0 : 1) * 8));
-    HIP_TRY(hipMalloc((void **)&d1, (n_in1 > 0 ? n_in1 : 1) * 8));
-    HIP_TRY(hipMalloc((void **)&d2, (n_in2 > 0 ? n_in2 : 1) * 8));
-    HIP_TRY(hipMalloc((void **)&dout, (n_out > 0 ? n_out : 1) * 8));
-    HIP_TRY(hipMalloc((void **)&dflag, 4));
-    if(n_in0 > 0) HIP_TRY(hipMemcpy(d0, in0, n_in0 * 8, hipMemcpyHostToDevice));
-    if(n_in1 > 0) HIP_TRY(hipMemcpy(d1, in1, n_in1 * 8, hipMemcpyHostToDevice));
-    if(n_in2 > 0) HIP_TRY(hipMemcpy(d2, in2, n_in2 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dout, out, n_out * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dense_test, dim3(1), dim3(64), 0, 0, op, shape, 0, 0, d0, d1, d2, dout, dflag);
+    Buffer<double> d0, d1, d2, dout;
+    Buffer<int> dflag;
+    if(d0.reserve((n_in0 > 0 ? n_in0 : 1) * 8) || d1.reserve((n_in1 > 0 ? n_in1 : 1) * 8) || d2.reserve((n_in2 > 0 ? n_in2 : 1) * 8) ||
+       dout.reserve((n_out > 0 ? n_out : 1) * 8) || dflag.reserve(4))
+        return 1;
+    if(n_in0 > 0) HIP_TRY(hipMemcpy(d0.get(), in0, n_in0 * 8, hipMemcpyHostToDevice));
+    if(n_in1 > 0) HIP_TRY(hipMemcpy(d1.get(), in1, n_in1 * 8, hipMemcpyHostToDevice));
+    if(n_in2 > 0) HIP_TRY(hipMemcpy(d2.get(), in2, n_in2 * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dout.get(), out, n_out * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_dense_test, dim3(1), dim3(64), 0, 0, op, shape, 0, 0, d0.get(), d1.get(), d2.get(), dout.get(), dflag.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dout, n_out * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flag, dflag, 4, hipMemcpyDeviceToHost));
-    hipFree(d0); hipFree(d1); hipFree(d2); hipFree(dout); hipFree(dflag);
+    HIP_TRY(hipMemcpy(out, dout.get(), n_out * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flag, dflag.get(), 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int ilqg_dev_sincos_batch(int device, int n, const double *x, double *s, double *c) {
     HIP_TRY(hipSetDevice(device));
-    double *dx, *ds, *dc;
-    HIP_TRY(hipMalloc((void **)&dx, n * 8));
-    HIP_TRY(hipMalloc((void **)&ds, n * 8));
-    HIP_TRY(hipMalloc((void **)&dc, n * 8));
-    HIP_TRY(hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_sincos_test, grid1(n, 256), dim3(256), 0, 0, n, dx, ds, dc);
+    Buffer<double> dx, ds, dc;
+    if(dx.reserve(n * 8) || ds.reserve(n * 8) || dc.reserve(n * 8)) return 1;
+    HIP_TRY(hipMemcpy(dx.get(), x, n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_sincos_test, grid1(n, 256), dim3(256), 0, 0, n, dx.get(), ds.get(), dc.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(s, ds, n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(c, dc, n * 8, hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(ds); hipFree(dc);
+    HIP_TRY(hipMemcpy(s, ds.get(), n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, dc.get(), n * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2548,27 +2481,23 @@ static int boxqp_batch(int rows, int device, int n, int count, const double *H, 
     }
     HIP_TRY(hipSetDevice(device));
     const size_t T = n * (n + 1) / 2;
-    double *dH, *dg, *dlo, *dup, *dx, *dinv;
-    int *dcl, *dnf, *drc;
-    HIP_TRY(hipMalloc((void **)&dH, count * T * 8));
-    HIP_TRY(hipMalloc((void **)&dinv, count * T * 8));
-    HIP_TRY(hipMalloc((void **)&dg, count * n * 8));
-    HIP_TRY(hipMalloc((void **)&dlo, count * n * 8));
-    HIP_TRY(hipMalloc((void **)&dup, count * n * 8));
-    HIP_TRY(hipMalloc((void **)&dx, count * n * 8));
-    HIP_TRY(hipMalloc((void **)&dcl, count * n * 4));
-    HIP_TRY(hipMalloc((void **)&dnf, count * 4));
-    HIP_TRY(hipMalloc((void **)&drc, count * 4));
+    Buffer<double> oH, oinv, og, olo, oup, ox;
+    Buffer<int> ocl, onf, orc, oact;
+    if(oH.reserve(count * T * 8) || oinv.reserve(count * T * 8) || og.reserve(count * n * 8) || olo.reserve(count * n * 8) ||
+       oup.reserve(count * n * 8) || ox.reserve(count * n * 8) || ocl.reserve(count * n * 4) || onf.reserve(count * 4) || orc.reserve(count * 4))
+        return 1;
+    double *const dH = oH.get(), *const dinv = oinv.get(), *const dg = og.get(), *const dlo = olo.get(), *const dup = oup.get(), *const dx = ox.get();
+    int *const dcl = ocl.get(), *const dnf = onf.get(), *const drc = orc.get();
     HIP_TRY(hipMemcpy(dH, H, count * T * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dg, g, count * n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dlo, lower, count * n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dup, upper, count * n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dx, x, count * n * 8, hipMemcpyHostToDevice));
     const dim3 grid = rows == 1 ? dim3(count) : (rows == 3 ? grid1(count, 4) : grid1(count, 64)), block(64);
-    int *dact = nullptr;
 #if ILQG_WAVE_MAP
     if(rows == 3) {
-        HIP_TRY(hipMalloc((void **)&dact, count * 4));
+        if(oact.reserve(count * 4)) return 1;
+        int *const dact = oact.get();
         const std::vector<int> every(count, 1);
         HIP_TRY(hipMemcpy(dact, active ? active : every.data(), count * 4, hipMemcpyHostToDevice));
         if(n == NU)
@@ -2611,8 +2540,6 @@ static int boxqp_batch(int rows, int device, int n, int count, const double *H, 
     HIP_TRY(hipMemcpy(clamp, dcl, count * n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(n_free, dnf, count * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rc, drc, count * 4, hipMemcpyDeviceToHost));
-    hipFree(dH); hipFree(dinv); hipFree(dg); hipFree(dlo); hipFree(dup); hipFree(dx);
-    hipFree(dcl); hipFree(dnf); hipFree(drc); hipFree(dact);
     return 0;
 }
 
@@ -2640,6 +2567,7 @@ int ilqg_dev_boxqp_quad_batch(int device, int n, int count, const double *H, con
 // Several GPUs of one node in ONE process (SURVEY 8(e)): the trajectory batch is sharded, every device advances its
 // shard by itself, and the only exchange is one RCCL gather of a per-trajectory scalar (the costs) to a root device.
 // ---------------------------------------------------------------------------
+// (send[] and recv stay raw pointers: each is freed with ITS device current, which a Buffer does not remember)
 struct ilqg_comm {
     int n;
     std::vector<int> devices;
