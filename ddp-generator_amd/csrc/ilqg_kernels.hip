@@ -28,6 +28,7 @@
 
 #include <algorithm>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -762,6 +763,8 @@ __device__ __forceinline__ void drain_memory_ops() { __builtin_amdgcn_s_waitcnt(
 // "this value is needed HERE": keeps the optimiser from sinking its computation into a later block
 __device__ __forceinline__ void pin(double &v) { asm volatile("" : "+v"(v)); }
 
+#include "ilqg_params.inc"  // ParamValues, ILQG_CALLBACKS, PolicyParamMap, override_params, the packs of parameter rows (apply_rows)
+
 // Builds with wave-uniform guards (ILQG_UNIFORM_GUARDS): f() for all active lanes together; if that fails (for all
 // of them, see the guard), once more with one lane active at a time.  ONE call site for both, so that the repetition
 // is the same machine code and a healthy lane gets the same bits either way.
@@ -807,6 +810,23 @@ __device__ __forceinline__ int run_step(ilqg_hooks &H, int okc, Fn &&f) {
 #endif
     return r;
 }
+
+// The step of the template's forward pass (iLQG_func.tem:160-176) on the element ct from (xin, uin), as the lambda a
+// roll-out hands run_step: the ONE text of it, for k_rollout, k_search, k_policy and k_plant.  COST_ONLY: forward_pass with
+// cost_only = 1 (no clamp, no next state).  A macro and no function, so that the lambda stays AT the call site (see
+// run_step): as a function, forward_step<COST_ONLY>() is ONE caller of ddpf where the kernels were many, the inliner then
+// folds ddpf into it, and the n = 16 libraries' roll-outs double in size (profiles/README.md, profiles/r17_param_rows.txt).
+#define ILQG_FORWARD_STEP(COST_ONLY, ct, mp, k, N, C, xin, uin, xnext)               \
+    [&]() {                                                                          \
+        _Pragma("unroll") for(int i = 0; i < NX; i++) (ct).x[i] = (xin)[i];          \
+        _Pragma("unroll") for(int j = 0; j < NU; j++) (ct).u[j] = (uin)[j];          \
+        int r = calcXVariableAux(&(ct), mp, k, &(C).o);                              \
+        if(!(COST_ONLY)) clampU((ct).u, &(ct), k, (C).o.p, N);                       \
+        r &= calcXUVariableAux(&(ct), mp, k, &(C).o);                                \
+        if(!(COST_ONLY)) r &= ddpf(xnext, &(ct), k, (C).o.p, N);                     \
+        r &= ddpL(&(ct), k, &(C).o);                                                 \
+        return r;                                                                    \
+    }
 
 // Layout of the derivative-record fields (DER, FIN) of width W (doubles per step and trajectory):
 //   lane mapping: [step][tile of 64 trajectories][component][trajectory in tile] — k_derivs, lane = (trajectory,
@@ -917,124 +937,6 @@ __device__ __forceinline__ void store_mul_fin(const DevPtrs &P, int b, const mul
     }
 }
 
-// Per-lane snapshot of the problem parameters.  The generated callbacks read parameters as
-// p[i][j] through a `double **`; read from global memory, every such value would have to be
-// re-loaded after each store of the kernel (the compiler cannot prove that the parameter
-// arrays do not alias the output arrays), which costs two dependent memory round trips per
-// use.  Fixed-size parameters are therefore passed BY VALUE as a kernel argument (ParamValues)
-// and copied into a private array: after SROA every p[i][j] is a wave-uniform value that was
-// loaded once from the kernel-argument segment by a scalar load, i.e. it lives in an SGPR and
-// costs no vector register.  Per-time-step parameters (size -1) stay in global memory.
-struct ParamValues {
-    double v[ILQG_PTOTAL];
-};
-struct ParamTable {
-    double *ptr[ILQG_NP + ILQG_HOOK_SLOTS];  // the problem's parameters, then the hooks (see ilqg_hooks)
-};
-//
-// VECTOR = true: the copies are made lane values (an empty asm statement the optimiser cannot look through), i.e. they
-// live in vector registers as the rows of a per-trajectory table do (trajectory_params).  The shared lane-mapped sweep and
-// searches hold more wave-uniform values than there are scalar registers; what does not fit travels through
-// v_writelane / v_readlane — vector instructions with wait states, inside the step loops — while vector registers are
-// to spare there.  Per kernel, where that kernel's launch time gained by it (profiles/r14_vector_params.txt), and only for
-// a problem with few parameter doubles: each costs two vector registers.  -DILQG_VECTOR_PARAMS=0: scalar everywhere, as before.
-#ifndef ILQG_VECTOR_PARAMS
-#define ILQG_VECTOR_PARAMS 1
-#endif
-#ifndef ILQG_VECTOR_PARAMS_MAX  // parameter doubles up to which a kernel may hold them per lane (CarParking: 20)
-#define ILQG_VECTOR_PARAMS_MAX 24
-#endif
-#ifndef ILQG_VECTOR_PARAMS_BACKWARD  // k_backward<2>
-#define ILQG_VECTOR_PARAMS_BACKWARD 1
-#endif
-#ifndef ILQG_VECTOR_PARAMS_SEARCH0  // k_search<0, true>
-#define ILQG_VECTOR_PARAMS_SEARCH0 1
-#endif
-#ifndef ILQG_VECTOR_PARAMS_SEARCH1  // k_search<1, true>
-#define ILQG_VECTOR_PARAMS_SEARCH1 1
-#endif
-constexpr bool VECTOR_PARAMS = ILQG_VECTOR_PARAMS && !ILQG_WAVE_MAP && ILQG_PTOTAL <= ILQG_VECTOR_PARAMS_MAX;
-template <bool VECTOR = false>
-__device__ __forceinline__ void load_params(ParamValues &V, ParamTable &T, ilqg_hooks &H, const ParamValues &A,
-                                            double **p) {
-    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
-    constexpr int offs[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_POFFSETS;
-#pragma unroll
-    for(int i = 0; i < ILQG_NP; i++) {
-        if(sizes[i] > 0) {
-#pragma unroll
-            for(int j = 0; j < sizes[i]; j++) {
-                double v = A.v[offs[i] + j];
-                if(VECTOR) asm volatile("" : "+v"(v));
-                V.v[offs[i] + j] = v;
-            }
-            T.ptr[i] = &V.v[offs[i]];
-        } else {
-            T.ptr[i] = p[i];
-        }
-    }
-    H.nonfinite = 0.0;
-    H.huge = 0.0;
-    H.slow = 0.0;
-    H.limgrad = 1.0;
-    T.ptr[ILQG_HOOK_NONFINITE] = &H.nonfinite;
-    T.ptr[ILQG_HOOK_HUGE] = &H.huge;
-    T.ptr[ILQG_HOOK_SLOW] = &H.slow;
-    T.ptr[ILQG_HOOK_LIMGRAD] = &H.limgrad;
-    H.alone = 0.0;
-    T.ptr[ILQG_HOOK_ALONE] = &H.alone;
-    H.record = nullptr;
-    T.ptr[ILQG_HOOK_RECORD] = reinterpret_cast<double *>(&H.record);
-}
-
-// What a kernel needs to call the generated callbacks.  Four separate private objects, each pointing
-// only at the next (o -> table -> values, hooks): the optimiser dissolves them one level at a time into
-// registers; a single struct holding pointers into itself would stay in scratch memory.
-struct Callbacks {
-    tOptSet o;   // what the callbacks see as `o` (p, n_hor, penalty weights)
-    tOptSet o1;  // the same with n_hor = 1: init_running loops over n_hor elements
-};
-template <bool VECTOR = false>
-__device__ __forceinline__ void make_callbacks(Callbacks &C, ParamTable &T, ParamValues &V, ilqg_hooks &H,
-                                               const DevPtrs &P, const ilqg_dev_opts_t &O, const ParamValues &A) {
-    load_params<VECTOR>(V, T, H, A, P.p);
-    tOptSet &o = C.o;
-    o.p = T.ptr;
-    o.n_hor = P.N;
-    o.w_pen_l = O.w_pen_init_l;
-    o.w_pen_f = O.w_pen_init_f;
-    o.tolConstraint = O.tolConstraint;
-    o.w_pen_fact1 = O.w_pen_fact1;
-    o.w_pen_fact2 = O.w_pen_fact2;
-    o.w_pen_max_l = O.w_pen_max_l;
-    o.w_pen_max_f = O.w_pen_max_f;
-    C.o1 = o;
-    C.o1.n_hor = 1;
-}
-// problems with multipliers: the penalty weights are per trajectory (they grow with the constraint violation)
-__device__ __forceinline__ void set_penalty_weights(Callbacks &C, double w_l, double w_f) {
-    C.o.w_pen_l = C.o1.w_pen_l = w_l;
-    C.o.w_pen_f = C.o1.w_pen_f = w_f;
-}
-__device__ __forceinline__ void load_penalty_weights(Callbacks &C, const DevPtrs &P, int b) {
-    if(HAS_MUL) set_penalty_weights(C, P.f[ILQG_F_WPEN_L][b], P.f[ILQG_F_WPEN_F][b]);
-}
-// for the derivatives: the weights of the last accepted step.  A rejected step may raise the current ones
-// (iLQG.c:345-349) while the reference sweeps again over the derivatives it has; kernels that re-evaluate
-// derivatives instead of keeping them (fused backward pass, wave mapping) reproduce those with these weights.
-__device__ __forceinline__ void load_penalty_weights_der(Callbacks &C, const DevPtrs &P, int b) {
-    if(HAS_MUL) set_penalty_weights(C, P.f[ILQG_F_WPEN_L_DER][b], P.f[ILQG_F_WPEN_F_DER][b]);
-}
-// declares the callback context C and the lane's hooks H of a kernel with arguments (P, O, A)
-#define ILQG_CALLBACKS(C, H) ILQG_CALLBACKS_IN(C, H, false)
-// the same with the fixed-size parameters in vector registers where VECTOR_ holds (see load_params)
-#define ILQG_CALLBACKS_IN(C, H, VECTOR_) \
-    ParamValues C##_values;              \
-    ParamTable C##_table;                \
-    ilqg_hooks H;                        \
-    Callbacks C;                         \
-    make_callbacks<(VECTOR_)>(C, C##_table, C##_values, H, P, O, A)
-
 // ---------------------------------------------------------------------------
 // host layout [b][k][f]  <->  device layout [k][b/64][f][b%64] of the lane mapping (the wave mapping's
 // trajectory-major fields are copied without a kernel)
@@ -1077,13 +979,6 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
     const int b = (int)(i / ((size_t)wh * steps));
     host[i] = (fcol < wd) ? dev[(size_t)k * wd * Bp + (size_t)(b >> 6) * (wd * WAVE) + (size_t)fcol * WAVE + (b & 63)] : 0.0;
 }
-
-// per-trajectory problem parameters: row b of the context's table over the lane's private parameters (k_policy.inc, where
-// the order rule is stated); the kernels below call it with their pack `rows`
-struct PolicyParamMap;
-template <class... Behind>
-__device__ __forceinline__ void trajectory_params(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *__restrict__ values,
-                                                  const PolicyParamMap &map, const Behind &...);
 
 #if !ILQG_WAVE_MAP
 #include "k_lane_backward.inc"  // k_derivs, k_backward, k_backward_split, k_pack_records

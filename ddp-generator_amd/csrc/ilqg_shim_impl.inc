@@ -189,13 +189,13 @@ struct ilqg_dev : DevBuffers {
     bool plant_named;           // the plants run under plant_values and this map
     PolicyParamMap plant_map;
     // pb_on: the lane-mapped kernels that take ParamValues run as the instantiation whose pack is the table pb_values and its map
-    // (LAUNCH_PV)
+    // (with_rows)
     bool pb_on;
     PolicyParamMap pb_map;
     bool sr_on[SR];             // sr_rows[s] is in use
     bool win_given[SR];         // the slot has a future in win_future[s] (else its window holds)
     int win_rounds, win_steps;  // 0: no loop open
-    // what LAUNCH_PV hands the rows twins: rows_on = pb_on or some sr_on; rows_map = pb_map (empty without a table) with the
+    // what with_rows hands the rows twins: rows_on = pb_on or some sr_on; rows_map = pb_map (empty without a table) with the
     // step rows in use (rows_refresh, after every change of either set)
     bool rows_on;
     PolicyParamMap rows_map;
@@ -437,6 +437,38 @@ static bool step_rows_into(Map &m, const ilqg_dev_t *d) {  // (a template: the m
     }
     return any;
 }
+
+// The ONE place that picks the instantiation of a lane-mapped kernel that takes ParamValues: the kernel as it was before
+// there were per-trajectory parameters — its old name, an empty pack, not one argument more — unless the context holds a
+// table (ilqg_dev_set_params_batch) or rows of a per-time-step parameter (ilqg_dev_set_param_steps_batch); then the
+// instantiation whose pack is the table and its map, behind the kernel's own arguments — with step rows only, a table that
+// is not read under an empty map (rows_refresh).  with_rows hands the launch, a generic callable, nothing or that pair:
+//     with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_rollout<RK_INIT, decltype(tr)...>), ..., tr...); });
+// Both forms share the kernel's timing slot.  The wave mapping has no second form (ilqg_dev_set_params_batch refuses), and
+// its libraries do not instantiate one.
+template <class Launch>
+static void with_rows(ilqg_dev_t *d, Launch &&launch) {
+    if constexpr(!WAVE_MAP) {
+        if(d->rows_on) return launch((const double *)d->pb_values.get(), d->rows_map);
+    }
+    launch();
+}
+// the same shape for a kernel's OWN rows behind them (k_policy<true>: values, shared, map; k_plant<true>: values, map)
+template <class Launch, class... Own>
+static void with_own_rows(bool on, Launch &&launch, Own... own) {
+    if(!on) return launch();
+    launch(own...);
+}
+// The two kernels that are no templates, k_derivs and k_multipliers, have a rows twin of another name, K_rows<table, map>
+#if !ILQG_WAVE_MAP
+#define LAUNCH_TWIN(d, K, grid, block, lds, stream, ...)                                                               \
+    with_rows(d, [&](auto... tr) {                                                                                     \
+        if constexpr(sizeof...(tr) == 0) hipLaunchKernelGGL(K, grid, block, lds, stream, __VA_ARGS__);                 \
+        else hipLaunchKernelGGL((K##_rows<decltype(tr)...>), grid, block, lds, stream, __VA_ARGS__, tr...);            \
+    })
+#else
+#define LAUNCH_TWIN(d, K, grid, block, lds, stream, ...) hipLaunchKernelGGL(K, grid, block, lds, stream, __VA_ARGS__)
+#endif
 
 extern "C" {
 
@@ -740,7 +772,7 @@ int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const dou
 // Per-trajectory problem parameters.  Nothing here touches a trajectory: like ilqg_dev_set_params it only changes what the
 // NEXT launch reads.  The copy is enqueued on the context's stream, behind every launch that still reads the old rows.
 static const PolicyParamMap *policy_param_map(int n_named, const int *named, const double *values, PolicyParamMap &map);
-// the map the rows twins get (LAUNCH_PV): the table's, or an empty one, with the step rows in use
+// the map the rows twins get (with_rows): the table's, or an empty one, with the step rows in use
 static void rows_refresh(ilqg_dev_t *d) {
     PolicyParamMap m;
     if(d->pb_on) {
@@ -1105,28 +1137,6 @@ int ilqg_dev_io_end(ilqg_dev_t *d) {
         return 1;                                                        \
     }
 
-// The ONE place that picks the instantiation of a lane-mapped kernel that takes ParamValues: the kernel as it was before
-// there were per-trajectory parameters — its old name, an empty pack, not one argument more — unless the context holds a
-// table (ilqg_dev_set_params_batch) or rows of a per-time-step parameter (ilqg_dev_set_param_steps_batch); then the
-// instantiation whose pack is the table and its map, behind the kernel's own arguments — with step rows only, a table that
-// is not read under an empty map (rows_refresh).  K: the kernel's name with its own template arguments, left open, in parentheses: (k_rollout<RK_INIT).  The two
-// kernels that are no templates have a twin of another name: LAUNCH_PV_AS(d, (k_derivs), (k_derivs_rows<ILQG_PV_ROWS>), ...).
-// Both forms share the kernel's timing slot.  The wave mapping has no second form (ilqg_dev_set_params_batch refuses).
-#define ILQG_OPEN_NAME(...) __VA_ARGS__
-#define ILQG_PV_ROWS const double *, PolicyParamMap
-#if !ILQG_WAVE_MAP
-#define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...)                                                                    \
-    do {                                                                                                                                \
-        if((d)->rows_on)                                                                                                                \
-            hipLaunchKernelGGL((ILQG_OPEN_NAME ROWS), grid, block, lds, stream, __VA_ARGS__, (const double *)(d)->pb_values.get(), (d)->rows_map); \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__);                                         \
-    } while(0)
-#else
-#define LAUNCH_PV_AS(d, SHARED, ROWS, grid, block, lds, stream, ...) hipLaunchKernelGGL((ILQG_OPEN_NAME SHARED), grid, block, lds, stream, __VA_ARGS__)
-#endif
-#define LAUNCH_PV(d, K, ...) LAUNCH_PV_AS(d, (ILQG_OPEN_NAME K>), (ILQG_OPEN_NAME K, ILQG_PV_ROWS>), __VA_ARGS__)
-
 // ls_keep = 2: every current trajectory back into the arrays X / U (the host is about to read or write them, an
 // initial roll-out is about to store there, or a search that does not keep its roll-outs follows)
 static int all_home(ilqg_dev_t *d) {
@@ -1146,7 +1156,7 @@ int ilqg_dev_reset(ilqg_dev_t *d) {
     if(HAS_MUL) {  // update_multipliers(o, 1) of the solver entry (iLQG.c:236)
         NEED_PARAMS(d);
         Timed t(d, ILQG_K_MULTIPLIERS);
-        LAUNCH_PV_AS(d, (k_multipliers), (k_multipliers_rows<ILQG_PV_ROWS>), dim3(d->Bp / WAVE), dim3(WAVE), 0, d->stream, d->P, d->O, d->pv, 1);
+        LAUNCH_TWIN(d, k_multipliers, dim3(d->Bp / WAVE), dim3(WAVE), 0, d->stream, d->P, d->O, d->pv, 1);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1173,9 +1183,9 @@ static void launch_rollout(ilqg_dev_t *d, int mode, int kernel_id, int a0, int n
     Timed t(d, kernel_id, stream);
     const dim3 grid((d->Bp + ROLL_BLOCK - 1) / ROLL_BLOCK, n_alpha), block(ROLL_BLOCK);
     if(mode == ROLL_INIT)
-        LAUNCH_PV(d, (k_rollout<RK_INIT), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
+        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_rollout<RK_INIT, decltype(tr)...>), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0, tr...); });
     else if(mode == ROLL_COST)
-        LAUNCH_PV(d, (k_rollout<RK_COST), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
+        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_rollout<RK_COST, decltype(tr)...>), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0, tr...); });
 #if ILQG_WAVE_MAP && defined(ILQG_ROLLOUT_PARTS)
     else if(!HAS_MUL && !d->env.no_rollout_parts) {  // the generated file offers the step in parts: several wavefronts per 64 trajectories
         DevPtrs Q = d->P;
@@ -1193,7 +1203,7 @@ static void launch_rollout(ilqg_dev_t *d, int mode, int kernel_id, int a0, int n
     }
 #endif
     else
-        LAUNCH_PV(d, (k_rollout<RK_GENERAL), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0);
+        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_rollout<RK_GENERAL, decltype(tr)...>), grid, block, 0, stream, d->P, d->O, d->pv, mode, a0, tr...); });
 }
 
 int ilqg_dev_rollout_init(ilqg_dev_t *d) {
@@ -1405,27 +1415,14 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
                          int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     if(roll_enter(d)) return 1;
     const dim3 grid = grid1((size_t)d->B * (size_t)R, ROLL_BLOCK);
-    // (with a per-trajectory table — lane mapping only — the trajectory's row goes first, the roll-out's behind it)
-#if !ILQG_WAVE_MAP
-    if(d->rows_on && !map) {
-        Timed t(d, ILQG_K_POLICY, roll_stream(d));
-        hipLaunchKernelGGL((k_policy<false, const double *, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0,
-                           alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values.get(), d->rows_map);
-    } else if(d->rows_on) {
-        Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
-        hipLaunchKernelGGL((k_policy<true, const double *, PolicyParamMap, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0,
-                           roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, (const double *)d->pb_values.get(),
-                           d->rows_map, values, shared ? 1 : 0, *map);
-    } else
-#endif
-    if(!map) {
-        Timed t(d, ILQG_K_POLICY, roll_stream(d));
-        hipLaunchKernelGGL(k_policy<false>, grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost,
-                           ok, x_end, x, u);
-    } else {
-        Timed t(d, ILQG_K_POLICY_PARAMS, roll_stream(d));
-        hipLaunchKernelGGL((k_policy<true, const double *, int, PolicyParamMap>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, R,
-                           x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, values, shared ? 1 : 0, *map);
+    {   // (with a per-trajectory table — lane mapping only — the trajectory's row goes first, the roll-out's behind it)
+        Timed t(d, map ? ILQG_K_POLICY_PARAMS : ILQG_K_POLICY, roll_stream(d));
+        with_rows(d, [&](auto... tr) {
+            with_own_rows(map != nullptr, [&](auto... own) {
+                hipLaunchKernelGGL((k_policy<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
+                                   d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, tr..., own...);
+            }, values, shared ? 1 : 0, map ? *map : PolicyParamMap{});
+        });
     }
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
@@ -1556,26 +1553,15 @@ int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
     if(roll_enter(d)) return 1;
     {
         Timed t(d, ILQG_K_PLANT, roll_stream(d));
-#if !ILQG_WAVE_MAP  // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
-        if(d->rows_on && d->plant_named)
-            hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK),
-                               dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(),
-                               (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get(),
-                               (const double *)d->pb_values.get(), d->rows_map, (const double *)d->plant_values.get(), d->plant_map);
-        else if(d->rows_on)
-            hipLaunchKernelGGL((k_plant<false, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d),
-                               d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(), (const double *)d->plant_dist.get(), round * steps,
-                               rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get(), (const double *)d->pb_values.get(), d->rows_map);
-        else
-#endif
-        if(d->plant_named)
-            hipLaunchKernelGGL((k_plant<true, const double *, PolicyParamMap>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
-                               d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(), (const double *)d->plant_dist.get(), round * steps, rounds * steps,
-                               round, rounds, d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get(), (const double *)d->plant_values.get(), d->plant_map);
-        else
-            hipLaunchKernelGGL(k_plant<false>, grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O, d->pv, steps,
-                               feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(), (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds,
-                               d->log_x.get(), d->log_u.get(), d->plant_cost.get(), d->log_c.get());
+        // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
+        with_rows(d, [&](auto... tr) {
+            with_own_rows(d->plant_named, [&](auto... own) {
+                hipLaunchKernelGGL((k_plant<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0,
+                                   roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(),
+                                   (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(),
+                                   d->plant_cost.get(), d->log_c.get(), tr..., own...);
+            }, (const double *)d->plant_values.get(), d->plant_map);
+        });
     }
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
@@ -2003,7 +1989,7 @@ int ilqg_dev_derivs(ilqg_dev_t *d) {
     {
         Timed t(d, ILQG_K_DERIVS);
         const size_t total = (size_t)d->Bp * (d->N + 1);
-        LAUNCH_PV_AS(d, (k_derivs), (k_derivs_rows<ILQG_PV_ROWS>), grid1(total, 256), dim3(256), 0, d->stream, d->P, d->O, d->pv);
+        LAUNCH_TWIN(d, k_derivs, grid1(total, 256), dim3(256), 0, d->stream, d->P, d->O, d->pv);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2025,15 +2011,15 @@ int ilqg_dev_backward(ilqg_dev_t *d, int mode) {
         Timed t(d, mode == 2 ? ILQG_K_BACKWARD_FUSED : ILQG_K_BACKWARD);
         const dim3 grid(d->Bp / WAVE), block(WAVE);
         if(mode == 0)
-            LAUNCH_PV(d, (k_backward<0), grid, block, 0, d->stream, d->P, d->O, d->pv);
+            with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_backward<0, decltype(tr)...>), grid, block, 0, d->stream, d->P, d->O, d->pv, tr...); });
         else if(mode == 1)
-            LAUNCH_PV(d, (k_backward<1), grid, block, 0, d->stream, d->P, d->O, d->pv);
+            with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_backward<1, decltype(tr)...>), grid, block, 0, d->stream, d->P, d->O, d->pv, tr...); });
 #if ILQG_HAVE_SPLIT
         else if(d->O.bw_split && !HAS_MUL && !d->rows_on)  // (k_backward_split knows the shared parameters only)
             hipLaunchKernelGGL(k_backward_split, grid, dim3(2 * WAVE), 0, d->stream, d->P, d->O, d->pv);
 #endif
         else
-            LAUNCH_PV(d, (k_backward<2), grid, block, 0, d->stream, d->P, d->O, d->pv);
+            with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_backward<2, decltype(tr)...>), grid, block, 0, d->stream, d->P, d->O, d->pv, tr...); });
     }
     if(mode != 2) {
         Timed t(d, ILQG_K_TRANSPOSE);
@@ -2090,9 +2076,9 @@ int ilqg_dev_search(ilqg_dev_t *d) {
             const int T = WAVE / s1;
             const bool dma = T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma;
             if(dma)
-                LAUNCH_PV(d, (k_search<0, true), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, 0, s1, set);
+                with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<0, true, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, 0, s1, set, tr...); });
             else
-                LAUNCH_PV(d, (k_search<0, false), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0, s1, set);
+                with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<0, false, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0, s1, set, tr...); });
         }
         if(n2 > 0) {  // the grid covers the worst case; wavefronts beyond the pending count return at once
             {
@@ -2100,9 +2086,9 @@ int ilqg_dev_search(ilqg_dev_t *d) {
                 const int T = WAVE / n2;
                 const bool dma = T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma;
                 if(dma)
-                    LAUNCH_PV(d, (k_search<1, true), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, s1, n2, set);
+                    with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<1, true, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, s1, n2, set, tr...); });
                 else
-                    LAUNCH_PV(d, (k_search<1, false), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, s1, n2, set);
+                    with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<1, false, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, s1, n2, set, tr...); });
             }
             Timed t(d, ILQG_K_ADOPT, rs);
             hipLaunchKernelGGL(k_adopt_home, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1);
@@ -2220,7 +2206,7 @@ int ilqg_dev_update(ilqg_dev_t *d) {
     }
     if(HAS_MUL) {
         Timed t(d, ILQG_K_MULTIPLIERS, rs);
-        LAUNCH_PV_AS(d, (k_multipliers), (k_multipliers_rows<ILQG_PV_ROWS>), dim3(d->Bp / WAVE), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0);
+        LAUNCH_TWIN(d, k_multipliers, dim3(d->Bp / WAVE), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0);
     }
     if(d->O.resweep || HAS_MUL) launch_rollout(d, ROLL_COST, ILQG_K_ROLLOUT_COST, 0, 1, rs);
     HIP_TRY(hipGetLastError());

@@ -172,8 +172,6 @@ __global__ __launch_bounds__(WAVE) void k_multipliers(DevPtrs P, ilqg_dev_opts_t
 // per-trajectory table and its map)
 template <class... Rows>
 __device__ __forceinline__ void multipliers_lane(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int init, Rows... rows) {
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
-    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "multipliers_lane(P, O, A, init) or multipliers_lane(P, O, A, init, table, map)");
 #endif
     const int b = blockIdx.x * WAVE + threadIdx.x;
     if(b >= P.B) return;
@@ -185,7 +183,7 @@ __device__ __forceinline__ void multipliers_lane(DevPtrs P, ilqg_dev_opts_t O, P
     const int N = P.N;
     ILQG_CALLBACKS(C, H);
 #if !ILQG_WAVE_MAP
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
 #endif
     load_penalty_weights(C, P, b);
     const double wl = C.o.w_pen_l;

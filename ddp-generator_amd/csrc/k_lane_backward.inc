@@ -106,8 +106,6 @@ using RecZeros = NoZeros;
 // (the lane's work, for k_derivs and for k_derivs_rows below: Rows is empty or the context's per-trajectory table and its map)
 template <class... Rows>
 __device__ __forceinline__ void derivs_lane(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
-    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "derivs_lane(P, O, A) or derivs_lane(P, O, A, table, map)");
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int b = (int)(tid % P.Bp);
     const int k = (int)(tid / P.Bp);
@@ -115,7 +113,7 @@ __device__ __forceinline__ void derivs_lane(DevPtrs P, ilqg_dev_opts_t O, ParamV
     if(P.i[ILQG_I_STATUS][b] != ILQG_ST_ACTIVE || !P.i[ILQG_I_NEED_DERIVS][b]) return;
 
     ILQG_CALLBACKS(C, H);
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
     load_penalty_weights_der(C, P, b);
     int ok = 1;
     if(k < P.N) {
@@ -392,8 +390,7 @@ __device__ __forceinline__ int backward_sweep_fused(const DevPtrs &P, Callbacks 
 template <int mode, class... Rows>
 __global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
     // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
-    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "k_backward<...>(...) or k_backward<..., const double *, PolicyParamMap>(..., table, map)");
+    constexpr bool PER_TRAJECTORY = RowPack<OWN_NONE, Rows...>::has_trajectory_rows;
     const Place place(1);
 #ifdef ILQG_BACKWARD_PRIO  // measurement builds: issue priority of the sweep's wavefront over search wavefronts on its SIMD
     __builtin_amdgcn_s_setprio(ILQG_BACKWARD_PRIO);
@@ -409,7 +406,7 @@ __global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P,
     }
     // (the shared fused sweep: parameters per lane, where measured faster — load_params)
     ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && mode == 2 && ILQG_VECTOR_PARAMS_BACKWARD);
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
     load_penalty_weights_der(C, P, b);
     double lambda = P.f[ILQG_F_LAMBDA][b], dlambda = P.f[ILQG_F_DLAMBDA][b];
     double dV0 = 0.0, dV1 = 0.0, g_norm = P.f[ILQG_F_GNORM][b];

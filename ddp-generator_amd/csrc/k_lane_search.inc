@@ -37,8 +37,7 @@ template <int stage, bool DMA, class... Rows>
 __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int a0, int n, int set,
                                                                   Rows... rows) {
     // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
-    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "k_search<...>(...) or k_search<..., const double *, PolicyParamMap>(..., table, map)");
+    constexpr bool PER_TRAJECTORY = RowPack<OWN_NONE, Rows...>::has_trajectory_rows;
     extern __shared__ __attribute__((aligned(16))) double s_rec[];  // DMA: [2][T * RN] doubles
     const Place place(2 + stage);
     const int lane = threadIdx.x;
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
     // (the shared kernels with the records through LDS: parameters per lane, where measured faster — load_params)
     ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && DMA && (stage ? ILQG_VECTOR_PARAMS_SEARCH1 : ILQG_VECTOR_PARAMS_SEARCH0));
     // (b = pending[ee] or ee: lanes beyond the end repeat the last entry, and read its row)
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
     load_penalty_weights(C, P, b);
     trajEl_t ct;
     multipliersEl_t mk;
@@ -170,18 +169,7 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
         if(!DMA) load_nominal<true, 1>(cur, qn);  // the next step's record is in flight while this one computes
         if(HAS_MUL) load_mul(P, k, b, mk);
         double xnext[NX];
-        auto step = [&]() {
-#pragma unroll
-            for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
-#pragma unroll
-            for(int j = 0; j < NU; j++) ct.u[j] = uin[j];
-            int r = calcXVariableAux(&ct, mp, k, &C.o);
-            clampU(ct.u, &ct, k, C.o.p, N);
-            r &= calcXUVariableAux(&ct, mp, k, &C.o);
-            r &= ddpf(xnext, &ct, k, C.o.p, N);
-            r &= ddpL(&ct, k, &C.o);
-            return r;
-        };
+        auto step = ILQG_FORWARD_STEP(false, ct, mp, k, N, C, xin, uin, xnext);
         const int r = run_step(H, okc, step);
         okc &= r;
         csum += ct.c;

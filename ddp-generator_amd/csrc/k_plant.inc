@@ -1,5 +1,5 @@
 // The plant of a closed loop on the device (ilqg_dev_plant_*, ilqg_batch_receding_plant).  Included by ilqg_kernels.hip
-// inside its anonymous namespace, behind k_policy.inc (load_policy_step, policy_control, override_params, PolicyParamMap).
+// inside its anonymous namespace, behind k_policy.inc (load_policy_step, policy_control); its parameter rows: ilqg_params.inc.
 //
 // k_plant: the plant of trajectory b advances `steps` steps from ITS OWN state xp[b] under the policy of slot b — what
 // k_policy rolls out with alpha = 0: the current (x, u) where it lives (cur_x / cur_u) and the gains L of the packed
@@ -26,26 +26,13 @@
 // value NaN or Inf) or where the state behind the disturbance is not finite; a start that is not finite fails at once.
 // NOTHING of the batch is written.
 
-// row b of the plant's table over the lane's parameters: k_policy's override with one row per trajectory (g = b, r = 0)
-__device__ __forceinline__ void plant_params(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *__restrict__ values,
-                                             const PolicyParamMap &map) {
-    override_params(V, T, P, (size_t)b, 0, values, 0, map);
-}
-// the plant's row behind the trajectory's (the model's): trajectory_params' order
-__device__ __forceinline__ void plant_params_behind(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *, const PolicyParamMap &,
-                                                    const double *__restrict__ values, const PolicyParamMap &map) {
-    override_params(V, T, P, (size_t)b, 0, values, 0, map, true);
-}
-
 template <bool PLANT_PARAMS, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int steps, int feedback,
                                                                         double *__restrict__ xp, int *__restrict__ failed,
                                                                         const double *__restrict__ dist, int at0, int total, int round, int rounds,
                                                                         double *__restrict__ lx, double *__restrict__ lu, double *__restrict__ lc,
                                                                         double *__restrict__ lp, Rows... rows) {
-    // the pack: [the context's per-trajectory table, its map,] [the plants' table, its map]
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) == (PLANT_PARAMS ? 4 : 2);
-    static_assert(sizeof...(Rows) == (PER_TRAJECTORY ? 2 : 0) + (PLANT_PARAMS ? 2 : 0), "k_plant<true>(..., [table, map,] values, map); k_plant<false>(..., [table, map])");
+    // the pack: [the context's per-trajectory table, its map,] [the plants' table, its map] (RowPack)
     const int b = (int)(blockIdx.x * ROLL_BLOCK + threadIdx.x);
     if(b >= P.B) return;
     const int N = P.N;
@@ -66,9 +53,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
     }
 
     ILQG_CALLBACKS(C, H);
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
-    if constexpr(PLANT_PARAMS && PER_TRAJECTORY) plant_params_behind(C_values, C_table, P, b, rows...);
-    if constexpr(PLANT_PARAMS && !PER_TRAJECTORY) plant_params(C_values, C_table, P, b, rows...);
+    apply_rows<PLANT_PARAMS ? OWN_PLANT : OWN_NONE>(C_values, C_table, P, b, (size_t)b, 0, rows...);  // (the plant's row: one per trajectory)
     load_penalty_weights(C, P, b);
     el_t ct;
     multipliersEl_t mk;
@@ -114,18 +99,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs 
 
         if(HAS_MUL) load_mul(P, k, b, mk);
         double xnext[NX];
-        auto step = [&]() {
-#pragma unroll
-            for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
-#pragma unroll
-            for(int j = 0; j < NU; j++) ct.u[j] = uin[j];
-            int r = calcXVariableAux(&ct, mp, k, &C.o);
-            clampU(ct.u, &ct, k, C.o.p, N);
-            r &= calcXUVariableAux(&ct, mp, k, &C.o);
-            r &= ddpf(xnext, &ct, k, C.o.p, N);
-            r &= ddpL(&ct, k, &C.o);
-            return r;
-        };
+        auto step = ILQG_FORWARD_STEP(false, ct, mp, k, N, C, xin, uin, xnext);
         const int r = run_step(H, okc, step);
         csum += ct.c;
 #pragma unroll

@@ -70,110 +70,12 @@ __device__ __forceinline__ void policy_control(double (&uin)[NU], const NomStep 
     }
 }
 
-// Per-roll-out problem parameters (ilqg_batch_policy_rollout_params).  k_policy<true> is the same roll-out with three more
-// arguments — the caller's table `values`, [B][R][W] or with `shared` [R][W], and a by-value map of the ParamValues slots:
-// src[j] = the column of a row that replaces slot j, or -1 for a slot that keeps the batch's value.  Behind ILQG_CALLBACKS
-// every lane overrides the mapped slots of its PRIVATE ParamValues with row (shared ? r : g) of the table; the callbacks
-// then read them through the same ParamTable as ever.  The map is a kernel argument, so the test of a slot is a scalar
-// branch; an overridden slot lives in two vector registers instead of two scalar ones.  The policy (x, u, l, L of slot b),
-// the multipliers, the penalty weights and the per-time-step parameters are the batch's.  k_policy<false> has no further
-// argument (the pack is empty) and not one statement more than before.
-// Per-time-step parameters per trajectory (ilqg_batch_set_param_steps_batch) ride in the same map: for the s-th parameter of
-// size -1 in paramdesc[] order, rows[s] = its table [B][n_hor + 1], trajectory-major, or null while that parameter is the
-// shared window.  The member exists only in libraries whose problem has such a parameter (N_STEP_PARAMS, from ILQG_PSIZES):
-// everywhere else the map, and with it every kernel that takes one, is what it was.
-constexpr int n_step_params() {
-    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
-    int n = 0;
-    for(int i = 0; i < ILQG_NP; i++) n += sizes[i] == -1 ? 1 : 0;
-    return n;
-}
-constexpr int N_STEP_PARAMS = n_step_params();
-template <int n>
-struct StepRows {
-    const double *rows[n] = {};
-};
-template <>
-struct StepRows<0> {};
-struct PolicyParamMap : StepRows<N_STEP_PARAMS> {
-    short src[ILQG_PTOTAL];
-    int W;
-};
-// Register-resident overrides cost two vector registers per parameter double, 90 for the n = 16 problem.  Its FMA-free
-// builds (tests only) have none to give — their k_policy<false> already takes 448 of 512 — and would pay in scratch memory;
-// there the callbacks read EVERY fixed-size parameter from global memory instead: a named one in the lane's row of the
-// caller's table, the others in the context's own parameter buffers (P.p, which hold the fixed-size parameters too).  No
-// private copy, no register, and a reload behind every store the compiler cannot tell apart.
-#ifndef ILQG_POLICY_PARAMS_IN_MEMORY
-#if defined(ILQG_STRICT_FP)
-#define ILQG_POLICY_PARAMS_IN_MEMORY (2 * ILQG_PTOTAL > 64)
-#else
-#define ILQG_POLICY_PARAMS_IN_MEMORY 0
-#endif
-#endif
-// behind: a second override of the same lane (below); in the pointer form a slot it does not name keeps what the first one left
-__device__ __forceinline__ void override_params(ParamValues &V, ParamTable &T, const DevPtrs &P, size_t g, int r, const double *__restrict__ values,
-                                                int shared, const PolicyParamMap &map, bool behind = false) {
-    const double *row = values + (shared ? (size_t)r : g) * (size_t)map.W;
-    if(ILQG_POLICY_PARAMS_IN_MEMORY) {
-        constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
-        constexpr int offs[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_POFFSETS;
-#pragma unroll
-        for(int i = 0; i < ILQG_NP; i++)
-            if(sizes[i] > 0) T.ptr[i] = map.src[offs[i]] >= 0 ? const_cast<double *>(row + map.src[offs[i]]) : (behind ? T.ptr[i] : P.p[i]);
-    } else {
-#pragma unroll
-        for(int j = 0; j < ILQG_PTOTAL; j++)
-            if(map.src[j] >= 0) V.v[j] = row[map.src[j]];
-    }
-}
-
-// Per-trajectory problem parameters (ilqg_batch_set_params_batch): the context's table [B][W] with its map, the first two of
-// a kernel's pack `rows` (a kernel with an EMPTY pack is the kernel of before, under its old name; the two kernels that were no
-// templates, k_derivs and k_multipliers, stay so and have the twins k_derivs_rows / k_multipliers_rows).  Right behind ILQG_CALLBACKS a lane overrides the mapped slots of its private ParamValues with row b
-// of the table — b = the trajectory the lane works for, whatever its lane index means — ONCE per launch, never inside a step
-// loop: from there on the values are the lane's registers, where the shared ones are the wavefront's.  This is the one place
-// that states it, for k_rollout, k_derivs, k_backward, k_search, k_multipliers, k_policy and k_plant (and, with the plant's
-// table, for plant_params).  The same statement points the lane at its rows of the per-time-step parameters
-// (trajectory_step_params); with step rows only, the table's map is empty (every src -1, W = 0) and `values` is not read.  ORDER: the trajectory's row first, then the roll-out's or the plant's row — whatever the pack
-// holds behind the first two: a slot named in both gets the latter.
-// The trajectory's windows of the per-time-step parameters.  load_params left T.ptr[i] = the shared array, which the
-// generated callbacks index as p[i][k], k = 0 .. n_hor: that indexing is fixed, so a window per trajectory is a POINTER PER
-// LANE, row b of the table (two vector registers per such parameter, and a vector load per use where the shared window takes
-// a scalar one; eight consecutive steps of a lane share a 64-byte line).  A null table (a scalar test: the map is a kernel
-// argument) leaves the shared window.  Index arithmetic over B (n_hor + 1) in size_t.
-template <class Map>
-__device__ __forceinline__ void trajectory_step_params(ParamTable &T, const DevPtrs &P, int b, const Map &map) {
-    constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
-    int s = 0;
-#pragma unroll
-    for(int i = 0; i < ILQG_NP; i++)
-        if(sizes[i] == -1) {
-            if(map.rows[s]) T.ptr[i] = const_cast<double *>(map.rows[s]) + (size_t)b * (size_t)(P.N + 1);
-            s++;
-        }
-}
-template <class... Behind>
-__device__ __forceinline__ void trajectory_params(ParamValues &V, ParamTable &T, const DevPtrs &P, int b, const double *__restrict__ values,
-                                                  const PolicyParamMap &map, const Behind &...) {
-    override_params(V, T, P, (size_t)b, 0, values, 0, map);
-    if constexpr(N_STEP_PARAMS > 0) trajectory_step_params(T, P, b, map);
-}
-// the roll-out's own row (k_policy: values, shared, map) behind the trajectory's
-__device__ __forceinline__ void rollout_params_behind(ParamValues &V, ParamTable &T, const DevPtrs &P, size_t g, int r, const double *, const PolicyParamMap &,
-                                                      const double *__restrict__ values, int shared, const PolicyParamMap &map) {
-    override_params(V, T, P, g, r, values, shared, map, true);
-}
-
 template <bool PER_ROLLOUT_PARAMS, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
                                                                          double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
                                                                          double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
                                                                          Rows... rows) {
-    // the pack: [the context's per-trajectory table, its map,] [values, shared, map of the roll-outs' own rows]
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) == (PER_ROLLOUT_PARAMS ? 5 : 2);
-    static_assert(sizeof...(Rows) == (PER_TRAJECTORY ? 2 : 0) + (PER_ROLLOUT_PARAMS ? 3 : 0),
-                  "k_policy<true>(..., [table, map,] values, shared, map); k_policy<false>(..., [table, map])");
+    // the pack: [the context's per-trajectory table, its map,] [values, shared, map of the roll-outs' own rows] (RowPack)
     const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
     if(g >= (size_t)P.B * (size_t)R) return;
     const int b = (int)(g / (size_t)R);
@@ -194,9 +96,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
     }
 
     ILQG_CALLBACKS(C, H);
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
-    if constexpr(PER_ROLLOUT_PARAMS && PER_TRAJECTORY) rollout_params_behind(C_values, C_table, P, g, (int)(g - (size_t)b * (size_t)R), rows...);
-    if constexpr(PER_ROLLOUT_PARAMS && !PER_TRAJECTORY) override_params(C_values, C_table, P, g, (int)(g - (size_t)b * (size_t)R), rows...);
+    apply_rows<PER_ROLLOUT_PARAMS ? OWN_ROLLOUT : OWN_NONE>(C_values, C_table, P, b, g, (int)(g - (size_t)b * (size_t)R), rows...);
     load_penalty_weights(C, P, b);
     el_t ct;
     multipliersEl_t mk;
@@ -238,18 +138,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
 
         if(HAS_MUL) load_mul(P, k, b, mk);
         double xnext[NX];
-        auto step = [&]() {
-#pragma unroll
-            for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
-#pragma unroll
-            for(int j = 0; j < NU; j++) ct.u[j] = uin[j];
-            int r = calcXVariableAux(&ct, mp, k, &C.o);
-            clampU(ct.u, &ct, k, C.o.p, N);
-            r &= calcXUVariableAux(&ct, mp, k, &C.o);
-            r &= ddpf(xnext, &ct, k, C.o.p, N);
-            r &= ddpL(&ct, k, &C.o);
-            return r;
-        };
+        auto step = ILQG_FORWARD_STEP(false, ct, mp, k, N, C, xin, uin, xnext);
         const int r = run_step(H, okc, step);
         okc &= r;
         csum += ct.c;

@@ -81,9 +81,7 @@ static_assert(ILQG_ROLL_WAVES == ilqgdev::WAVES, "ilqgdev's ring is that of ONE 
 
 template <int KIND, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int mode, int a0, Rows... rows) {
-    // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
-    constexpr bool PER_TRAJECTORY = sizeof...(Rows) != 0;
-    static_assert(sizeof...(Rows) == 0 || sizeof...(Rows) == 2, "k_rollout<...>(...) or k_rollout<..., const double *, PolicyParamMap>(..., table, map)");
+    // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map (RowPack)
     int b = blockIdx.x * ROLL_BLOCK + threadIdx.x;
     int ai = a0 + blockIdx.y;
     double *keep = nullptr;  // second stage: where this lane's trajectory is kept
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
     const bool feedback = (alpha != 0.0);  // alpha == 0.0: u = u_nom without feedback (iLQG_func.tem:156-158)
 
     ILQG_CALLBACKS(C, H);
-    if constexpr(PER_TRAJECTORY) trajectory_params(C_values, C_table, P, b, rows...);
+    apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
     // penalty weights of this trajectory; the initial roll-out runs before the solver entry sets them, with the
     // zero-initialised option set of the MEX entry (iLQG_mex.c:23,116; iLQG.c:233-234)
     if(HAS_MUL && KIND == RK_INIT) set_penalty_weights(C, 0.0, 0.0);
@@ -227,18 +225,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtr
         }
         // the step (iLQG_func.tem:160-176)
         double xnext[NX];
-        auto step = [&]() {
-#pragma unroll
-            for(int i = 0; i < NX; i++) ct.x[i] = xin[i];
-#pragma unroll
-            for(int j = 0; j < NU; j++) ct.u[j] = uin[j];
-            int r = calcXVariableAux(&ct, mp, k, &C.o);
-            if(!cost_only) clampU(ct.u, &ct, k, C.o.p, N);
-            r &= calcXUVariableAux(&ct, mp, k, &C.o);
-            if(!cost_only) r &= ddpf(xnext, &ct, k, C.o.p, N);
-            r &= ddpL(&ct, k, &C.o);
-            return r;
-        };
+        auto step = ILQG_FORWARD_STEP(cost_only, ct, mp, k, N, C, xin, uin, xnext);
         const int r = run_step(H, okc, step);
         okc &= r;
         csum += ct.c;

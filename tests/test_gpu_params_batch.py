@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.harness import HX_N, HX_PARAMS, hx_inputs, lib_path
-from params_batch_cases import BUILDS, SLOTS, B, FdCase, dict_of, oracle_stages, rows
+from params_batch_cases import BUILDS, SLOTS, B, FdCase, dict_of, oracle_stages, rows, setup
 from plant_cases import BOTH, noise, plant_over_rows, plant_starts
 from policy_cases import perturbed_starts, reference_rollout
 from policy_param_cases import NAMED, PER_STEP, draws, params_of
@@ -120,6 +120,32 @@ def test_a_batch_is_its_trajectories(ilqg):
         states_equal(full_state(one), whole, "slot %d against a batch of one under set_param" % b, slice(0, 1), slice(b, b + 1))
         one.close()
     c.close()
+
+
+def test_a_batch_is_its_trajectories_with_per_lane_loads_in_the_searches(ilqg, monkeypatch):
+    """The same identity under ILQG_NO_DMA=1, short horizon: the searches then load the nominal records per lane
+    (k_search<0 | 1, false>), a form the record size of no shipped lane-mapped problem selects, so its instantiations with the
+    table are reached by nothing else.  FMA-free CarParking, B = 70, n_hor = 8, iterate(5), bit for bit."""
+    N = 8
+    monkeypatch.setenv("ILQG_NO_DMA", "1")  # (read when a context is created)
+    problem, _, params, opts, x0, u0 = setup("carparking", 0)
+    u0 = np.ascontiguousarray(u0[:, :N])
+    kw = dict(n_hor=N, params=params, opts=dict(opts, max_iter=40), strict=True)
+    s = ilqg.BatchSolver(problem, 0, batch=B, **kw)
+    table, mine = rows("carparking", params)
+    s.set_params_batch(mine)
+    s.init(x0, u0)
+    s.iterate(5)
+    whole = full_state(s)
+    for b in SLOTS:
+        one = ilqg.BatchSolver(problem, 0, batch=1, **kw)
+        for n in NAMED["carparking"]:
+            one.set_param(n, mine[n][b])
+        one.init(x0[b:b + 1], u0[b:b + 1])
+        one.iterate(5)
+        states_equal(full_state(one), whole, "slot %d against a batch of one under set_param, per-lane loads" % b, slice(0, 1), slice(b, b + 1))
+        one.close()
+    s.close()
 
 
 # ---------------------------------------------------------------------------
