@@ -79,6 +79,7 @@ struct ilqg_batch {
     /* per-time-step parameters per trajectory (ilqg_batch_set_param_steps_batch): ps_on[i] != 0 while parameter i (size -1)
      * has a row per trajectory on the groups' devices; c->p[i] keeps the shared window set_param last gave it */
     char ps_on[64];
+    int hist_cap;                    /* the iteration history's capacity on every group (ilqg_batch_set_history), 0: none */
     /* full solves: finished trajectories are retired (ilqg_batch_solve) */
     int compact;                     /* 0: never; else the smallest number of live trajectories still worth a smaller context */
     int trace_n;                     /* the last solve, poll by poll: iterations done, trajectories active, slots iterated */
@@ -533,7 +534,14 @@ static int restart(ilqg_batch_t *c) {
     return 0;
 }
 
-int ilqg_batch_init(ilqg_batch_t *c) { return push_config(c) || restart(c); }
+/* counts and entries of the iteration history, on every group, in the order of its stream */
+static int clear_history(ilqg_batch_t *c, const char *who) {
+    int g;
+    if(c->hist_cap > 0) EACH_GROUP(g) if(ilqg_dev_set_history(c->dev[g], c->hist_cap)) return fail(c, who);
+    return 0;
+}
+
+int ilqg_batch_init(ilqg_batch_t *c) { return push_config(c) || clear_history(c, "ilqg_batch_init") || restart(c); }
 
 /* The _device forms take and fill device memory of the caller in the order of ITS stream, by events, and never wait on the
  * host.  Their bracket opens in two parts, because entries refuse between them: device_ptrs refuses what is not device memory
@@ -1394,6 +1402,10 @@ int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const 
                                    "through them: rows per start are not supported.  Make the names shared again first: "
                                    "ilqg_batch_set_param_steps_batch(c, name, values = NULL)");
     }
+    if(c->hist_cap > 0)
+        return fail_msg(c, "ilqg_batch_solve_stream: the batch records an iteration history (ilqg_batch_set_history), which belongs to its "
+                           "slots, while the starts of a stream pass through them: a history per start is not supported.  Switch it off "
+                           "first: ilqg_batch_set_history(c, 0)");
     if(push_config(c)) return 1;
     ilqg_dev_dims(dims);
     NXd = dims[0];
@@ -1592,6 +1604,81 @@ static int find_int(const char *name) {
     for(i = 0; i < sizeof(int_names) / sizeof(int_names[0]); i++)
         if(strcmp(int_names[i].name, name) == 0) return int_names[i].field;
     return -1;
+}
+
+/* ---- the iteration history ------------------------------------------------------------------------------------------
+ * The one table of its names: the entry's fields as the shim numbers them (ILQG_H_* doubles, ILQG_HI_* ints). */
+static const struct { const char *name; int is_int; int field; } history_names[] = {
+    {"cost", 0, ILQG_H_COST},     {"new_cost", 0, ILQG_H_NEW_COST}, {"z", 0, ILQG_H_Z},           {"lambda", 0, ILQG_H_LAMBDA},
+    {"g_norm", 0, ILQG_H_GNORM},  {"dV0", 0, ILQG_H_DV0},           {"dV1", 0, ILQG_H_DV1},       {"w_pen_l", 0, ILQG_H_WPEN_L},
+    {"w_pen_f", 0, ILQG_H_WPEN_F}, {"alpha_idx", 1, ILQG_HI_ALPHA_IDX}, {"bp_calls", 1, ILQG_HI_BP_CALLS},
+    {"iterations", 1, ILQG_HI_ITER}, {"n", 1, ILQG_HI_N},
+};
+/* the field of `name` for the getter `who` of doubles / ints, or refused (-2) with c->err set */
+static int history_field(ilqg_batch_t *c, const char *who, const char *name, int want_int, const void *out) {
+    size_t i;
+    int dims[2];
+    if(!out) {
+        snprintf(c->err, sizeof(c->err), "%s: out is NULL", who);
+        return -2;
+    }
+    if(c->hist_cap == 0) {
+        snprintf(c->err, sizeof(c->err), "%s: the batch has no iteration history: ilqg_batch_set_history(c, cap > 0) switches one on", who);
+        return -2;
+    }
+    for(i = 0; name && i < sizeof(history_names) / sizeof(history_names[0]); i++) {
+        if(strcmp(history_names[i].name, name) != 0) continue;
+        if(history_names[i].is_int != want_int) {
+            snprintf(c->err, sizeof(c->err), "%s: '%s' is %s: read it with %s", who, name, want_int ? "a double field" : "an int field",
+                     want_int ? "ilqg_batch_get_history" : "ilqg_batch_get_history_int");
+            return -2;
+        }
+        ilqg_dev_multiplier_dims(dims);
+        if(!want_int && history_names[i].field >= ILQG_H_WPEN_L && dims[0] + dims[1] == 0) {
+            snprintf(c->err, sizeof(c->err), "%s: '%s' is recorded in libraries of problems with multipliers only; this problem has none", who, name);
+            return -2;
+        }
+        return history_names[i].field;
+    }
+    snprintf(c->err, sizeof(c->err), "%s: no such history field '%s' (cost new_cost z lambda g_norm dV0 dV1 w_pen_l w_pen_f; ints: alpha_idx "
+                                     "bp_calls iterations n)", who, name ? name : "(NULL)");
+    return -2;
+}
+
+int ilqg_batch_history_cap(const ilqg_batch_t *c) { return c->hist_cap; }
+
+/* every group's buffers are made before any group changes: a capacity that does not fit leaves the history as it was */
+int ilqg_batch_set_history(ilqg_batch_t *c, int cap) {
+    int g, h;
+    if(cap < 0) {
+        snprintf(c->err, sizeof(c->err), "ilqg_batch_set_history: cap = %d, must not be negative (cap > 0: that many entries per trajectory, 0: no history)", cap);
+        return 1;
+    }
+    EACH_GROUP(g) if(ilqg_dev_reserve_history(c->dev[g], cap)) {
+        fail(c, "ilqg_batch_set_history");
+        for(h = 0; h <= g; h++) (void)ilqg_dev_reserve_history(c->dev[h], 0);
+        return 1;
+    }
+    EACH_GROUP(g) if(ilqg_dev_set_history(c->dev[g], cap)) return fail(c, "ilqg_batch_set_history");
+    c->hist_cap = cap;
+    return 0;
+}
+
+int ilqg_batch_get_history(ilqg_batch_t *c, const char *name, double *out) {
+    const int f = history_field(c, "ilqg_batch_get_history", name, 0, out);
+    int g;
+    if(f == -2) return 1;
+    EACH_GROUP(g) if(ilqg_dev_get_history(c->dev[g], f, out + (size_t)c->first[g] * c->hist_cap)) return fail(c, "ilqg_batch_get_history");
+    return 0;
+}
+
+int ilqg_batch_get_history_int(ilqg_batch_t *c, const char *name, int *out) {
+    const int f = history_field(c, "ilqg_batch_get_history_int", name, 1, out);
+    int g;
+    if(f == -2) return 1;
+    EACH_GROUP(g)
+        if(ilqg_dev_get_history_int(c->dev[g], f, out + (size_t)c->first[g] * (f == ILQG_HI_N ? 1 : c->hist_cap))) return fail(c, "ilqg_batch_get_history_int");
+    return 0;
 }
 
 int ilqg_batch_get_scalar(ilqg_batch_t *c, const char *name, double *out) {
@@ -2312,6 +2399,38 @@ int ilqg_multi_get_x(ilqg_multi_t *m, double *x) {
 int ilqg_multi_get_u(ilqg_multi_t *m, double *u) {
     int g;
     EACH_SHARD(g) if(ilqg_batch_get_u(m->shard[g], u + (size_t)m->first[g] * m->N * N_U)) return multi_fail(m, g);
+    return 0;
+}
+/* the iteration history per shard: every shard records its own trajectories; the getters place them by rows */
+int ilqg_multi_set_history(ilqg_multi_t *m, int cap) {
+    int g, h;
+    if(!m) return 1;
+    EACH_SHARD(g) {
+        const int was = ilqg_batch_history_cap(m->shard[g]);
+        if(ilqg_batch_set_history(m->shard[g], cap)) {
+            multi_fail(m, g);
+            /* (the shards before it go back to the capacity they had, cleared: a shard's own history stays as it was) */
+            for(h = 0; h < g; h++) (void)ilqg_batch_set_history(m->shard[h], was);
+            return 1;
+        }
+    }
+    return 0;
+}
+int ilqg_multi_history_cap(const ilqg_multi_t *m) { return m ? ilqg_batch_history_cap(m->shard[0]) : 0; }
+int ilqg_multi_get_history(ilqg_multi_t *m, const char *name, double *out) {
+    int g;
+    if(!m) return 1;
+    EACH_SHARD(g)
+        if(ilqg_batch_get_history(m->shard[g], name, out ? out + (size_t)m->first[g] * ilqg_batch_history_cap(m->shard[g]) : NULL)) return multi_fail(m, g);
+    return 0;
+}
+int ilqg_multi_get_history_int(ilqg_multi_t *m, const char *name, int *out) {
+    int g;
+    if(!m) return 1;
+    EACH_SHARD(g) {
+        const size_t w = (name && strcmp(name, "n") == 0) ? 1 : (size_t)ilqg_batch_history_cap(m->shard[g]);
+        if(ilqg_batch_get_history_int(m->shard[g], name, out ? out + (size_t)m->first[g] * w : NULL)) return multi_fail(m, g);
+    }
     return 0;
 }
 int ilqg_multi_get_int(ilqg_multi_t *m, const char *name, int *out) {

@@ -124,7 +124,30 @@ enum {
     ILQG_K_PLANT,    /* k_plant (ilqg_dev_plant_advance) */
     ILQG_K_SHIFT_PARAM_ROWS, /* k_shift_param_rows (ilqg_dev_shift_param_batch) */
     ILQG_K_SHIFT_WINDOWS, /* k_shift_windows (ilqg_dev_windows_move) */
+    ILQG_K_HISTORY,  /* k_history (ilqg_dev_update of a context with a history) */
     ILQG_K_COUNT
+};
+
+/* fields of an entry of the iteration history (ilqg_dev_set_history): doubles ... */
+enum {
+    ILQG_H_COST = 0, /* ILQG_F_COST: the nominal cost the search started from */
+    ILQG_H_NEW_COST, /* ILQG_F_NEW_COST: the reference's log_cost             */
+    ILQG_H_Z,        /* reduction_ratio(dcost, expected): its log_z           */
+    ILQG_H_LAMBDA,   /* behind the backward pass's retries, before the update */
+    ILQG_H_GNORM,
+    ILQG_H_DV0,
+    ILQG_H_DV1,
+    ILQG_H_WPEN_L,   /* these two in libraries of problems with multipliers only */
+    ILQG_H_WPEN_F,
+    ILQG_H_COUNT
+};
+/* ... and ints; ILQG_HI_N is no field of an entry but the per-trajectory count of entries */
+enum {
+    ILQG_HI_N = -1,
+    ILQG_HI_ALPHA_IDX = 0, /* 1-based, n_alpha + 1 = none: the reference's log_linesearch */
+    ILQG_HI_BP_CALLS,
+    ILQG_HI_ITER,          /* ILQG_I_ITER then: the index the reference logs under */
+    ILQG_HI_COUNT
 };
 
 /* all functions return 0 on success, non-zero on error (message via ilqg_dev_error) */
@@ -286,6 +309,24 @@ int ilqg_dev_search(ilqg_dev_t *d);           /* all step sizes in parallel + fi
 int ilqg_dev_winner(ilqg_dev_t *d);           /* re-roll the accepted step size, storing the trajectory */
 int ilqg_dev_update(ilqg_dev_t *d);           /* accept/reject bookkeeping (iLQG.c:311-361) */
 int ilqg_dev_iterate(ilqg_dev_t *d, int n);   /* n lock-step iterations */
+/* The iteration history: with capacity cap > 0 every ilqg_dev_update first appends, for every trajectory that is
+ * ILQG_ST_ACTIVE then (its line search has just run), one entry of the ILQG_H_* / ILQG_HI_* fields at position n[b] of the
+ * trajectory's own count, which goes up by one; entries at positions >= cap are dropped while n counts on (k_history, one
+ * launch in front of k_update on its stream).  set: cap > 0 allocates (two buffers of the context) and clears counts and
+ * entries — at an unchanged cap it clears in the order of the context's stream, without a wait or an allocation —, cap = 0
+ * frees; a context without a history launches and allocates nothing.  Where the new buffers do not fit, the history stays as
+ * it was.  ilqg_dev_shift and ilqg_dev_reset do not clear.  ilqg_dev_move carries the count and the min(n, cap) entries of
+ * every trajectory it moves; a destination without a history gets one of the source's capacity.
+ * get (waits): field ILQG_H_* into out [batch][cap]; get_int: ILQG_HI_N into out [batch], ILQG_HI_* into out [batch][cap];
+ * unwritten entries are zero.  cap: the capacity, 0 = none.
+ * reserve: makes the buffers of capacity cap aside and changes nothing else; the set of that cap that follows takes them and
+ * cannot fail for memory (a caller with several contexts reserves on all before it sets on any).  cap <= 0 or the capacity
+ * the context has: releases what was aside. */
+int ilqg_dev_reserve_history(ilqg_dev_t *d, int cap);
+int ilqg_dev_set_history(ilqg_dev_t *d, int cap);
+int ilqg_dev_get_history(ilqg_dev_t *d, int field, double *out);
+int ilqg_dev_get_history_int(ilqg_dev_t *d, int field, int *out);
+int ilqg_dev_history_cap(const ilqg_dev_t *d);
 int ilqg_dev_sync(ilqg_dev_t *d);
 int ilqg_dev_count_active(ilqg_dev_t *d, int *n_active); /* synchronises */
 /* solver state of trajectories from[0..count) of src -> trajectories to[0..count) of dst (same device and horizon): current

@@ -140,6 +140,10 @@ struct DevBuffers {
     // the futures of a resident loop's windows (ilqg_dev_windows_begin): per slot the values beyond the window, [B][win_per] for
     // a parameter with rows, [win_per] for the shared window; grow-only
     Buffer<double> win_future[SR];
+    Buffer<double> hist_d;                 // the iteration history (ilqg_dev_set_history): History::d, History::i
+    Buffer<int> hist_i;
+    Buffer<double> hist_next_d;            //   ... and those of the capacity it is about to take (ilqg_dev_reserve_history)
+    Buffer<int> hist_next_i;
     Buffer<double> staging;                // see io_deferred
     Buffer<char, PinnedMem> pinned;
 };
@@ -199,6 +203,8 @@ struct ilqg_dev : DevBuffers {
     // step rows in use (rows_refresh, after every change of either set)
     bool rows_on;
     PolicyParamMap rows_map;
+    int hist_next_cap;          // the capacity hist_next_d / hist_next_i were made for (0: none aside)
+    History hist;               // views of hist_d / hist_i; cap = 0: no history, ilqg_dev_update launches nothing for it
     hipEvent_t ext_in, ext_out;  // ordering with a stream of the caller (ilqg_dev_stream_in / _out), made with the context
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
@@ -502,7 +508,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "layout kernels", "k_backward[fused derivs]", "k_rollout[stage 2 | winner]",
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
                                               "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant", "k_shift_param_rows",
-                                              "k_shift_windows"};
+                                              "k_shift_windows", "k_history"};
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -2179,6 +2185,10 @@ int ilqg_dev_search(ilqg_dev_t *d) {
     return roll_leave(d);
 }
 
+// the two launches of the iteration history, defined at the end of this file (see k_history in k_common.inc for why there)
+static void launch_history(ilqg_dev_t *d, hipStream_t stream);
+static void launch_move_history(ilqg_dev_t *dst, ilqg_dev_t *src, const int *to, const int *from, int count);
+
 int ilqg_dev_winner(ilqg_dev_t *d) {
     NEED_PARAMS(d);
     HIP_TRY(hipSetDevice(d->device));
@@ -2197,6 +2207,10 @@ int ilqg_dev_update(ilqg_dev_t *d) {
     HIP_TRY(hipSetDevice(d->device));
     hipStream_t rs = roll_stream(d);
     if(roll_enter(d)) return 1;
+    if(d->hist.cap > 0) {  // the record of the search that has just run, before the update moves what it holds
+        Timed t(d, ILQG_K_HISTORY, rs);
+        launch_history(d, rs);
+    }
     {
         Timed t(d, ILQG_K_UPDATE, rs);
         const int reset = (!WAVE_MAP && d->defer_commit) ? 1 : 0;
@@ -2285,8 +2299,109 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
                            idx + count, count, (int)W);
         HIP_TRY(hipGetLastError());
     }
+    if(src->hist.cap > 0) {  // ... and their histories; a destination without one gets one of the source's capacity
+        if(dst->hist.cap == 0 && ilqg_dev_set_history(dst, src->hist.cap)) return 1;
+        launch_move_history(dst, src, idx, idx + count, count);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(dst->stream));
     return 0;
+}
+
+// The iteration history.  Both buffers are made before the old ones go, so a capacity that does not fit leaves the history
+// as it was; the context's stream is drained in front of the exchange (k_history runs on the roll-outs' stream, which
+// hands back to the context's stream in ilqg_dev_update).
+static size_t history_doubles(const ilqg_dev_t *d, int cap) { return (size_t)HIST_DOUBLES * cap * d->Bp; }
+static size_t history_ints(const ilqg_dev_t *d, int cap) { return ((size_t)ILQG_HI_COUNT * cap + 1) * d->Bp; }
+int ilqg_dev_history_cap(const ilqg_dev_t *d) { return d->hist.cap; }
+// the buffers of a history of capacity cap, made aside (hist_next_*): ilqg_dev_set_history(d, cap) takes them.  cap <= 0 or
+// the capacity the context has: whatever was aside is released, nothing is made.
+int ilqg_dev_reserve_history(ilqg_dev_t *d, int cap) {
+    HIP_TRY(hipSetDevice(d->device));
+    d->hist_next_cap = 0;
+    if(d->hist_next_d.release() | d->hist_next_i.release()) return 1;
+    if(cap <= 0 || cap == d->hist.cap) return 0;
+    if(d->hist_next_d.renew(history_doubles(d, cap) * sizeof(double)) || d->hist_next_i.renew(history_ints(d, cap) * sizeof(int))) {
+        const std::string why = g_err;
+        (void)hipGetLastError();
+        (void)d->hist_next_d.release();
+        g_err = "set_history: no device memory for a history of cap = " + std::to_string(cap) + " entries per trajectory (" +
+                std::to_string(history_doubles(d, cap) * sizeof(double) + history_ints(d, cap) * sizeof(int)) + " bytes); the history stays as it was: " + why;
+        return 1;
+    }
+    d->hist_next_cap = cap;
+    return 0;
+}
+int ilqg_dev_set_history(ilqg_dev_t *d, int cap) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(cap < 0) {
+        g_err = "set_history: cap must not be negative (cap > 0: a history of that many entries per trajectory, 0: none)";
+        return 1;
+    }
+    if(cap != d->hist.cap) {
+        if(cap > 0 && d->hist_next_cap != cap && ilqg_dev_reserve_history(d, cap)) return 1;
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        d->hist_d = std::move(d->hist_next_d);  // (cap = 0: nothing is aside, the old buffers go)
+        d->hist_i = std::move(d->hist_next_i);
+        d->hist_next_cap = 0;
+        d->hist = History{d->hist_d.get(), d->hist_i.get(), cap, d->Bp};
+    }
+    if(cap > 0) {
+        HIP_TRY(hipMemsetAsync(d->hist.d, 0, d->hist_d.bytes(), d->stream));
+        HIP_TRY(hipMemsetAsync(d->hist.i, 0, d->hist_i.bytes(), d->stream));
+    }
+    return 0;
+}
+}  // extern "C"
+// one field's slab [cap][Bp] to the host, turned into [B][cap]
+template <class T>
+static int history_field(ilqg_dev_t *d, const T *slab, T *out) {
+    const int cap = d->hist.cap;
+    std::vector<T> host((size_t)cap * d->Bp);
+    HIP_TRY(hipMemcpyAsync(host.data(), slab, host.size() * sizeof(T), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    for(int b = 0; b < d->B; b++)
+        for(int e = 0; e < cap; e++) out[(size_t)b * cap + e] = host[(size_t)e * d->Bp + b];
+    return 0;
+}
+extern "C" {
+static int history_readable(ilqg_dev_t *d, const char *who, const void *out) {
+    if(d->hist.cap == 0) {
+        g_err = std::string(who) + ": the context has no history (ilqg_dev_set_history with cap > 0 switches one on)";
+        return 1;
+    }
+    if(!out) {
+        g_err = std::string(who) + ": out is NULL";
+        return 1;
+    }
+    return 0;
+}
+int ilqg_dev_get_history(ilqg_dev_t *d, int field, double *out) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(history_readable(d, "get_history", out)) return 1;
+    if(field < 0 || field >= ILQG_H_COUNT) {
+        g_err = "get_history: no such field";
+        return 1;
+    }
+    if(field >= HIST_DOUBLES) {
+        g_err = "get_history: w_pen_l / w_pen_f are recorded in libraries of problems with multipliers only; this problem has none";
+        return 1;
+    }
+    return history_field(d, d->hist.d + d->hist.at(field, 0, 0), out);
+}
+int ilqg_dev_get_history_int(ilqg_dev_t *d, int field, int *out) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(history_readable(d, "get_history_int", out)) return 1;
+    if(field == ILQG_HI_N) {
+        HIP_TRY(hipMemcpyAsync(out, d->hist.i, (size_t)d->B * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        return 0;
+    }
+    if(field < 0 || field >= ILQG_HI_COUNT) {
+        g_err = "get_history_int: no such field";
+        return 1;
+    }
+    return history_field(d, d->hist.ints() + d->hist.at(field, 0, 0), out);
 }
 
 int ilqg_dev_sync(ilqg_dev_t *d) {
@@ -2444,6 +2559,16 @@ int ilqg_dev_sincos_batch(int device, int n, const double *x, double *s, double 
     HIP_TRY(hipMemcpy(s, ds.get(), n * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(c, dc.get(), n * 8, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// The first uses of k_history and k_move_history in this translation unit: where a template is first used is where its code
+// lands in the code object (see k_history in k_common.inc) — here, behind every kernel of the solver and in front of the
+// box QP's unit-test kernels, which call nothing out of line.
+static void launch_history(ilqg_dev_t *d, hipStream_t stream) {
+    hipLaunchKernelGGL(k_history<>, grid1(d->Bp, 256), dim3(256), 0, stream, d->P, d->hist);
+}
+static void launch_move_history(ilqg_dev_t *dst, ilqg_dev_t *src, const int *to, const int *from, int count) {
+    hipLaunchKernelGGL(k_move_history<>, grid1((size_t)count * dst->hist.cap, 256), dim3(256), 0, dst->stream, dst->hist, src->hist, to, from, count);
 }
 
 // rows: 0 box_qp (one problem per lane), 1 the cooperative form of the wave mapping (one per wavefront), 2 box_qp with the

@@ -158,6 +158,52 @@ __global__ void k_update(DevPtrs P, ilqg_dev_opts_t O, int commit_s1, int commit
     P.i[ILQG_I_RESWEEP][b] = resweep;
 }
 
+// The iteration history of a context (ilqg_dev_set_history): per trajectory the count n of line searches recorded so far and
+// the first `cap` entries, laid out [field][cap][Bp] behind each other — the doubles of ILQG_H_* in d, in i the counts [Bp]
+// and behind them the ints of ILQG_HI_*: lane = trajectory, so every store of a wavefront is one contiguous run.
+struct History {
+    double *d;
+    int *i;
+    int cap, Bp;
+    __host__ __device__ size_t at(int field, int entry, int b) const { return ((size_t)field * cap + entry) * Bp + b; }
+    __host__ __device__ int *ints() const { return i + Bp; }  // (behind the counts)
+};
+constexpr int HIST_DOUBLES = HAS_MUL ? ILQG_H_COUNT : ILQG_H_WPEN_L;  // the penalty weights only where the problem has multipliers
+
+// (Both history kernels are templates for one reason: a template is instantiated, and so emitted into the code object, where
+// it is first USED, and the shim first uses these two (launch_history, launch_move_history) behind every kernel of the solver,
+// in front of the box QP's unit-test kernels only.  A kernel emitted in the middle moves everything behind it, and with it
+// the pc-relative offsets in every kernel that calls an out-of-line function such as ilqg_sincos_slow: each of those would
+// read as changed in tools/kernel_resources.py --digest.)
+
+// In front of k_update, on its stream: one entry for every trajectory whose line search has just run (ILQG_ST_ACTIVE here:
+// what left in this iteration's backward pass logs nothing, as in the reference) — what the per-trajectory fields hold at the
+// return of line_search(), i.e. line_search.c:70-72's log_linesearch / log_z / log_cost and the values iLQG.c:314,353 print,
+// before k_update moves lambda, the cost and the iteration count.  Position n[b]; beyond cap dropped while n counts on.
+template <class Hist = History>
+__global__ void k_history(DevPtrs P, Hist H) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if(b >= P.B || P.i[ILQG_I_STATUS][b] != ILQG_ST_ACTIVE) return;
+    const int n = H.i[b];
+    H.i[b] = n + 1;
+    if(n >= H.cap) return;
+    H.d[H.at(ILQG_H_COST, n, b)] = P.f[ILQG_F_COST][b];
+    H.d[H.at(ILQG_H_NEW_COST, n, b)] = P.f[ILQG_F_NEW_COST][b];
+    H.d[H.at(ILQG_H_Z, n, b)] = reduction_ratio(P.f[ILQG_F_DCOST][b], P.f[ILQG_F_EXPECTED][b]);
+    H.d[H.at(ILQG_H_LAMBDA, n, b)] = P.f[ILQG_F_LAMBDA][b];
+    H.d[H.at(ILQG_H_GNORM, n, b)] = P.f[ILQG_F_GNORM][b];
+    H.d[H.at(ILQG_H_DV0, n, b)] = P.f[ILQG_F_DV0][b];
+    H.d[H.at(ILQG_H_DV1, n, b)] = P.f[ILQG_F_DV1][b];
+    if(HAS_MUL) {
+        H.d[H.at(ILQG_H_WPEN_L, n, b)] = P.f[ILQG_F_WPEN_L][b];
+        H.d[H.at(ILQG_H_WPEN_F, n, b)] = P.f[ILQG_F_WPEN_F][b];
+    }
+    int *const hi = H.ints();
+    hi[H.at(ILQG_HI_ALPHA_IDX, n, b)] = P.i[ILQG_I_ALPHA_IDX][b];
+    hi[H.at(ILQG_HI_BP_CALLS, n, b)] = P.i[ILQG_I_BP_CALLS][b];
+    hi[H.at(ILQG_HI_ITER, n, b)] = P.i[ILQG_I_ITER][b];
+}
+
 // update_multipliers (iLQG_func.tem:419-521) for the trajectories k_update flagged, or with init != 0 at the solver
 // entry (iLQG.c:236) for all live ones.  The generated functions walk o->nominal->t and o->multipliers.t over
 // o->n_hor elements; here they see a one-element view per time step (the constraint values they read are the
@@ -351,6 +397,21 @@ __global__ void k_move_rows(double *__restrict__ dst, const double *__restrict__
     if(w >= (size_t)count * W) return;
     const int j = (int)(w / W), i = (int)(w % W);
     dst[(size_t)to[j] * W + i] = src[(size_t)from[j] * W + i];
+}
+
+// ... and their histories: slot to[j] of D becomes a copy of slot from[j] of S — the count as it is, the entries S holds of
+// it (min(n, S.cap)) as far as D has room, zero behind them.  One thread per (entry of D, j), j fastest.
+template <class Hist = History>
+__global__ void k_move_history(Hist D, Hist S, const int *to, const int *from, int count) {
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(w >= (size_t)count * D.cap) return;
+    const int j = (int)(w % count), e = (int)(w / count);
+    const int bs = from[j], bd = to[j];
+    const int n = S.i[bs];
+    const bool held = e < n && e < S.cap;
+    if(e == 0) D.i[bd] = n;
+    for(int f = 0; f < HIST_DOUBLES; f++) D.d[D.at(f, e, bd)] = held ? S.d[S.at(f, e, bs)] : 0.0;
+    for(int f = 0; f < ILQG_HI_COUNT; f++) D.ints()[D.at(f, e, bd)] = held ? S.ints()[S.at(f, e, bs)] : 0;
 }
 
 __global__ void k_count_active(const int *status, int B, int *out) {

@@ -350,6 +350,47 @@ def _policy_rollout(solver, entry, x0, alpha, feedback, trajectories, params):
     return out
 
 
+HISTORY_DOUBLES = ("cost", "new_cost", "z", "lambda", "g_norm", "dV0", "dV1")
+HISTORY_PENALTIES = ("w_pen_l", "w_pen_f")  # in libraries of problems with multipliers only
+HISTORY_INTS = ("alpha_idx", "bp_calls", "iterations")
+
+
+def _set_history(solver, prefix, cap):
+    """BatchSolver.set_history / MultiSolver.set_history: the checks and the one library call"""
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)):
+        raise IlqgError("set_history: cap must be an integer, not %r" % (cap,))
+    if cap < 0:
+        raise IlqgError("set_history: cap = %d, must not be negative (cap > 0: that many entries per trajectory, 0: no history)" % cap)
+    solver._ck(_receding_entry(solver.lib, prefix + "set_history")(solver.h, int(cap)))
+
+
+def _history(solver, prefix, names):
+    """BatchSolver.history / MultiSolver.history: one library call per name"""
+    get, get_int = _receding_entry(solver.lib, prefix + "get_history"), _receding_entry(solver.lib, prefix + "get_history_int")
+    cap = int(_receding_entry(solver.lib, prefix + "history_cap")(solver.h))
+    if cap < 1:
+        raise IlqgError("history: the solver has no iteration history: set_history(cap > 0) switches one on")
+    me, mf = solver.multiplier_dims()
+    known = HISTORY_DOUBLES + (HISTORY_PENALTIES if me + mf else ()) + HISTORY_INTS + ("n",)
+    if names is None:
+        names = known
+    if isinstance(names, str):
+        names = (names,)
+    for name in names:
+        if name in HISTORY_PENALTIES and name not in known:
+            raise IlqgError("history: '%s' is recorded in libraries of problems with multipliers only; this problem has none" % name)
+        if name not in known:
+            raise IlqgError("history: no such history field %r (%s)" % (name, " ".join(known)))
+    out = {}
+    for name in names:
+        if name == "n":
+            out[name] = np.zeros(solver.B, dtype=np.int32)
+        else:
+            out[name] = np.zeros((solver.B, cap), dtype=np.int32 if name in HISTORY_INTS else np.float64)
+        solver._ck((get_int if out[name].dtype == np.int32 else get)(solver.h, name.encode(), _address(out[name])))
+    return out
+
+
 def _receding_entry(lib, name):
     """ilqg_batch_shift / ilqg_batch_receding / ilqg_multi_shift, ilqg_batch_head / _head_device / _shift_device /
     _shift_param / ilqg_multi_head, ilqg_batch_policy_rollout / _policy_rollout_device / ilqg_multi_policy_rollout and their
@@ -467,6 +508,15 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_receding_plant_windows.argtypes = [v, C.c_int, C.c_int, C.c_int, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, v,
                                                           C.c_int, C.POINTER(C.c_char_p), C.POINTER(v), v, v, v, v, v]
         lib.ilqg_multi_receding_plant_windows.argtypes = lib.ilqg_batch_receding_plant_windows.argtypes
+    if hasattr(lib, "ilqg_batch_set_history"):  # (and for the iteration history)
+        lib.ilqg_batch_set_history.argtypes = [v, C.c_int]
+        lib.ilqg_batch_get_history.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_batch_get_history_int.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_batch_history_cap.argtypes = [v]
+        lib.ilqg_multi_set_history.argtypes = [v, C.c_int]
+        lib.ilqg_multi_get_history.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_multi_get_history_int.argtypes = [v, C.c_char_p, v]
+        lib.ilqg_multi_history_cap.argtypes = [v]
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -930,6 +980,21 @@ class BatchSolver:
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=np.int32), (self.B,)))
         self._ck(self.lib.ilqg_batch_set_int(self.h, name.encode(), v))
 
+    def set_history(self, cap):
+        """the iteration history on the device (ilqg_batch_set_history): with cap > 0 every update of an iteration — in
+        iterate, solve (compacted too), every receding* loop, or the stage update() — first appends one entry for every
+        trajectory that is active then, i.e. whose line search has just run, at position n[b] of the trajectory's own count;
+        entries at positions >= cap are dropped while n counts on.  set_history and init() clear counts and entries, shift()
+        and the resident loops do not.  0 switches off and frees.  solve_stream refuses a solver with a history."""
+        _set_history(self, "ilqg_batch_", cap)
+
+    def history(self, names=None):
+        """the recorded entries (ilqg_batch_get_history / _get_history_int): dict of arrays [B, cap] — float64 cost, new_cost,
+        z, lambda, g_norm, dV0, dV1 (and w_pen_l, w_pen_f where the problem has multipliers), int32 alpha_idx, bp_calls,
+        iterations — plus n [B] int32, the entries recorded per trajectory (it may exceed cap).  Entry e of trajectory b is
+        valid for e < min(n[b], cap); unwritten entries are zero.  names: a name or a sequence of them (default: all)."""
+        return _history(self, "ilqg_batch_", names)
+
     def success(self):
         """the reference's iLQG() return value per trajectory (what the drop-in iLQG() of this library returns too)"""
         status, iters = self.ints("status"), self.ints("iterations")
@@ -1097,6 +1162,19 @@ class MultiSolver:
         out = np.zeros((self.B, self.N, self.problem.nu))
         self._ck(self.lib.ilqg_multi_get_u(self.h, out))
         return out
+
+    def multiplier_dims(self):
+        d = np.zeros(2, dtype=np.int32)
+        self.lib.ilqg_problem_multiplier_dims(d)
+        return int(d[0]), int(d[1])
+
+    def set_history(self, cap):
+        """BatchSolver.set_history on every shard (ilqg_multi_set_history)"""
+        _set_history(self, "ilqg_multi_", cap)
+
+    def history(self, names=None):
+        """BatchSolver.history of every shard, placed by rows (ilqg_multi_get_history / _get_history_int)"""
+        return _history(self, "ilqg_multi_", names)
 
     def ints(self, name):
         out = np.zeros((self.B, MAX_ALPHA if name == "alpha_ok" else 1), dtype=np.int32)

@@ -438,6 +438,39 @@ int ilqg_batch_set_scalar(ilqg_batch_t *c, const char *name, const double *in);
 int ilqg_batch_get_int(ilqg_batch_t *c, const char *name, int *out);
 int ilqg_batch_set_int(ilqg_batch_t *c, const char *name, const int *in);
 
+/* The ITERATION HISTORY: every trajectory's line searches, recorded on the device without a host round trip — what the
+ * reference keeps in log_linesearch / log_z / log_cost (line_search.c:70-72) and prints per iteration (iLQG.c:314, 353).
+ * ONE RULE.  With a history of capacity cap switched on, every time the batch runs the update of an iteration — inside
+ * ilqg_batch_iterate, ilqg_batch_solve (compacted too: a trajectory's history moves with it and is home at the end), every
+ * ilqg_batch_receding* loop, or as the stage ilqg_batch_update — it first APPENDS one entry for every trajectory that is
+ * active (status 0) at that point: exactly those whose line search has just run.  A trajectory that left in this
+ * iteration's backward pass (status 4, 1, 6) appends nothing, as the reference writes no log for it.  The entry holds what
+ * the per-trajectory fields hold then, i.e. at the return of line_search():
+ *   doubles  cost      the nominal cost the search started from
+ *            new_cost  the reference's log_cost
+ *            z         dcost / expected where expected > 0, else 0 (line_search.c:44-48): the reference's log_z
+ *            lambda    behind the backward pass's retries, BEFORE the update moves it
+ *            g_norm dV0 dV1
+ *            w_pen_l w_pen_f   only in libraries of problems with multipliers; elsewhere the names are refused
+ *   ints     alpha_idx   1-based, n_alpha + 1 = none accepted: the reference's log_linesearch
+ *            bp_calls    backward sweeps of this iteration
+ *            iterations  the reference's `iter` at that moment, the index it logs under
+ * For a rejected search new_cost and z are whatever the fields hold (the reference's carried-over values).
+ * The entry goes to position n[b], a count per trajectory, which then goes up by one; entries at positions >= cap are
+ * DROPPED while n counts on.  ilqg_batch_set_history and ilqg_batch_init CLEAR counts and entries; ilqg_batch_shift and
+ * the resident loops do NOT: receding(rounds, steps, iterations) leaves rounds * iterations entries whose `iterations`
+ * field restarts at 0 every round, and from an init on position and `iterations` coincide.  Unwritten entries read as zero.
+ * Recording changes no solver output; without a history nothing is launched and nothing allocated.
+ * set: cap > 0 switches on (or resizes) and clears, 0 switches off and frees.  get: out [B][cap], trajectory-major.
+ * get_int: name "n" gives [B] (it may exceed cap), the others [B][cap].  Refused, with the batch and its history left as
+ * they were and nothing launched: cap < 0; a capacity the device has no memory for; a getter without a history; an unknown
+ * name; w_pen_* without multipliers; out = NULL.  ilqg_batch_solve_stream refuses a batch with a history: it belongs to
+ * slots, starts pass through them — switch it off first, ilqg_batch_set_history(c, 0). */
+int ilqg_batch_set_history(ilqg_batch_t *c, int cap);
+int ilqg_batch_get_history(ilqg_batch_t *c, const char *name, double *out /* [B][cap] */);
+int ilqg_batch_get_history_int(ilqg_batch_t *c, const char *name, int *out /* "n": [B]; else [B][cap] */);
+int ilqg_batch_history_cap(const ilqg_batch_t *c);
+
 /* Per-trajectory exit reasons ("status" of ilqg_batch_get_int): 0 active; 1 gradient test passed (iLQG.c:297-303);
  * 2 accepted step with dcost < tolFun (iLQG.c:330-335); 3 max_iter iterations done (iLQG.c:372-376); 4 backward pass:
  * lambda > lambdaMax (iLQG.c:273-274); 5 rejected step: lambda > lambdaMax (iLQG.c:356-360); 6 NaN/Inf in calc_derivs
@@ -499,6 +532,11 @@ int ilqg_multi_active(ilqg_multi_t *m, int *n_active);
 int ilqg_multi_get_x(ilqg_multi_t *m, double *x);
 int ilqg_multi_get_u(ilqg_multi_t *m, double *u);
 int ilqg_multi_get_int(ilqg_multi_t *m, const char *name, int *out);
+/* ilqg_batch_set_history / _get_history / _get_history_int per shard; out [batch][cap] resp. [batch], placed by rows */
+int ilqg_multi_set_history(ilqg_multi_t *m, int cap);
+int ilqg_multi_get_history(ilqg_multi_t *m, const char *name, double *out);
+int ilqg_multi_get_history_int(ilqg_multi_t *m, const char *name, int *out);
+int ilqg_multi_history_cap(const ilqg_multi_t *m);
 int ilqg_multi_gather_costs(ilqg_multi_t *m, double *cost /* [batch] */);
 
 /* The reference's MEX entry for a C caller (iLQG_mex.c:19-144):
