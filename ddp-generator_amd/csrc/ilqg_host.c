@@ -838,25 +838,28 @@ static int policy_names(ilqg_batch_t *c, const char *who, int n_names, const cha
 }
 #define POLICY_VALUES_AT(w) (shared ? values : values + (size_t)c->first[g] * (size_t)n_starts * (size_t)(w))
 
-/* The four entries below.  params: the _params forms (names resolved, at least one; else n_names is 0 here and names, values
- * and shared are not read); on_device: the _device forms (device memory of the caller, in the order of its stream, no wait). */
+/* The six entries below.  params: the _params forms and the _noise forms with n_names != 0 (names resolved, at least one;
+ * else n_names is 0 here and names, values and shared are not read); on_device: the _device forms (device memory of the
+ * caller, in the order of its stream, no wait); dist: the disturbance table of the _noise forms, [B][n_starts][n_hor][N_X] or
+ * with dist_shared [n_starts][n_hor][N_X], NULL in the others. */
 static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_device, int n_starts, const double *x0, int n_names,
-                          const char *const *names, const double *values, int shared, double alpha, int feedback, double *cost, int *ok,
-                          double *x_end, double *x, double *u, void *stream) {
+                          const char *const *names, const double *values, int shared, const double *dist, int dist_shared, double alpha,
+                          int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream) {
     const char *const what = params ? "policy_rollout_params" : "policy_rollout";
     const char *const what_stream = params ? "policy_rollout_params: stream" : "policy_rollout: stream";
-    const named_ptr_t ptrs[] = {{x0, "x0"}, {params ? values : NULL, "values"}, {cost, "cost"}, {ok, "ok"}, {x_end, "x_end"}, {x, "x"}, {u, "u"}};
+    const named_ptr_t ptrs[] = {{x0, "x0"}, {params ? values : NULL, "values"}, {dist, "disturbance"}, {cost, "cost"}, {ok, "ok"},
+                                {x_end, "x_end"}, {x, "x"}, {u, "u"}};
     int g, named[POLICY_MAX_NAMES], W = 0;
     if(policy_args(c, who, n_starts, x0)) return 1;
     if(params && policy_names(c, who, n_names, names, values, named, &W)) return 1;
-    if(on_device && device_ptrs(c, who, ptrs, 7)) return 1;
+    if(on_device && device_ptrs(c, who, ptrs, 8)) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
     if(push_config(c)) return 1;
     if(on_device && stream_in(c, stream, what_stream)) return 1;
     EACH_GROUP(g) {
         if((on_device ? ilqg_dev_policy_rollout : ilqg_dev_policy_rollout_host)(
-               c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared, alpha, feedback,
-               POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
+               c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared,
+               dist_shared ? dist : POLICY_AT(dist, (size_t)c->N * N_X), dist_shared, alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
             return fail(c, what);
         if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, what_stream);
     }
@@ -865,25 +868,44 @@ static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_d
 
 int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                               double *x_end, double *x, double *u) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout", 0, 0, n_starts, x0, 0, NULL, NULL, 0, alpha, feedback, cost, ok, x_end, x, u, NULL);
+    return policy_rollout(c, "ilqg_batch_policy_rollout", 0, 0, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, alpha, feedback, cost, ok, x_end, x, u, NULL);
 }
 
 int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                                      double *x_end, double *x, double *u, void *stream) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout_device", 0, 1, n_starts, x0, 0, NULL, NULL, 0, alpha, feedback, cost, ok, x_end, x, u, stream);
+    return policy_rollout(c, "ilqg_batch_policy_rollout_device", 0, 1, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, alpha, feedback, cost, ok, x_end, x, u,
+                          stream);
 }
 
 int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                      int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout_params", 1, 0, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok, x_end,
-                          x, u, NULL);
+    return policy_rollout(c, "ilqg_batch_policy_rollout_params", 1, 0, n_starts, x0, n_names, names, values, shared, NULL, 0, alpha, feedback, cost, ok,
+                          x_end, x, u, NULL);
 }
 
 int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
                                             const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
                                             double *x, double *u, void *stream) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout_params_device", 1, 1, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok,
-                          x_end, x, u, stream);
+    return policy_rollout(c, "ilqg_batch_policy_rollout_params_device", 1, 1, n_starts, x0, n_names, names, values, shared, NULL, 0, alpha, feedback,
+                          cost, ok, x_end, x, u, stream);
+}
+
+/* The same roll-outs under a disturbance table (see include/ilqg_batch.h): the superset entries.  n_names = 0: no parameter
+ * table, names, values and shared are not read (as in ilqg_batch_receding_plant); else the rules of the _params forms. */
+int ilqg_batch_policy_rollout_noise(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, const double *disturbance, int disturbance_shared, double alpha, int feedback, double *cost,
+                                    int *ok, double *x_end, double *x, double *u) {
+    const int params = n_names != 0;
+    return policy_rollout(c, "ilqg_batch_policy_rollout_noise", params, 0, n_starts, x0, params ? n_names : 0, names, values, params ? shared : 0,
+                          disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u, NULL);
+}
+
+int ilqg_batch_policy_rollout_noise_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
+                                           const double *values, int shared, const double *disturbance, int disturbance_shared, double alpha,
+                                           int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream) {
+    const int params = n_names != 0;
+    return policy_rollout(c, "ilqg_batch_policy_rollout_noise_device", params, 1, n_starts, x0, params ? n_names : 0, names, values,
+                          params ? shared : 0, disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u, stream);
 }
 
 /* the wave mapping carries no parameters per trajectory: refused by every entry that would set or read them */
@@ -2290,17 +2312,18 @@ int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l,
             return multi_fail(m, g);
     return 0;
 }
-/* both entries below: every shard's part through the worker of ilqg_batch_policy_rollout / ilqg_batch_policy_rollout_params */
+/* the three entries below: every shard's part through the worker of ilqg_batch_policy_rollout / _params / _noise (a full
+ * disturbance table sharded by rows, a shared one given to every shard) */
 static int multi_policy_rollout(ilqg_multi_t *m, const char *who, int params, int n_starts, const double *x0, int n_names, const char *const *names,
-                                const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
-                                double *u) {
+                                const double *values, int shared, const double *dist, int dist_shared, double alpha, int feedback, double *cost,
+                                int *ok, double *x_end, double *x, double *u) {
     const size_t W = (params && values && !shared) ? rows_width(n_names, names) : 0;
     const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
     int g;
     EACH_SHARD(g) {
         const size_t at = (size_t)m->first[g] * r;
         if(policy_rollout(m->shard[g], who, params, 0, n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
-                          alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
+                          (dist && !dist_shared) ? dist + at * (size_t)m->N * N_X : dist, dist_shared, alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
                           x ? x + at * (size_t)(m->N + 1) * N_X : NULL, u ? u + at * (size_t)m->N * N_U : NULL, NULL))
             return multi_fail(m, g);
     }
@@ -2308,12 +2331,19 @@ static int multi_policy_rollout(ilqg_multi_t *m, const char *who, int params, in
 }
 int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                               double *x_end, double *x, double *u) {
-    return multi_policy_rollout(m, "ilqg_batch_policy_rollout", 0, n_starts, x0, 0, NULL, NULL, 0, alpha, feedback, cost, ok, x_end, x, u);
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout", 0, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, alpha, feedback, cost, ok, x_end, x, u);
 }
 int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                      int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_params", 1, n_starts, x0, n_names, names, values, shared, alpha, feedback, cost, ok,
-                                x_end, x, u);
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_params", 1, n_starts, x0, n_names, names, values, shared, NULL, 0, alpha, feedback, cost,
+                                ok, x_end, x, u);
+}
+int ilqg_multi_policy_rollout_noise(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, const double *disturbance, int disturbance_shared, double alpha, int feedback, double *cost,
+                                    int *ok, double *x_end, double *x, double *u) {
+    const int params = n_names != 0;
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_noise", params, n_starts, x0, params ? n_names : 0, names, params ? values : NULL,
+                                params ? shared : 0, disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,

@@ -246,11 +246,17 @@ int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double 
  * behind the other in the order of named[].  The policy, multipliers, penalty weights and per-time-step parameters are the
  * context's.  ilqg_dev_policy_rollout takes DEVICE memory (values lives where x0 lives), is asynchronous on the context's
  * stream and waits for nothing; ilqg_dev_policy_rollout_host takes host memory, stages through the context's staging buffer
- * (which only grows) and waits once.  R >= 1; needs ilqg_dev_set_params before it. */
-int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
-                            int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
-                                 int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+ * (which only grows) and waits once.  R >= 1; needs ilqg_dev_set_params before it.
+ * dist = NULL: no process noise — the same kernels, launches and bits as before the argument existed.  Else behind every step
+ * k = 0 .. n_hor-1 the roll-out's state is pushed, x_{k+1} <- x_next + w[b][r][k] (the rule of ilqg_dev_plant_advance):
+ * dist [batch][R][n_hor][N_X], or with dist_shared != 0 [R][n_hor][N_X] for every trajectory; it lives where x0 lives (the
+ * host form stages it behind the values).  ok = 0 also where a disturbed state is not finite, the one behind row n_hor-1 —
+ * which moves x_end, x[n_hor] and the final cost — included.  No new kernel and no new timing slot. */
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                            const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                 const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
+                                 double *u);
 /* The plant of a closed loop that stays on the device (k_plant.inc): `rounds` times { ilqg_dev_iterate; ilqg_dev_plant_advance;
  * ilqg_dev_shift(d, steps, 0); ilqg_dev_plant_put_x0; ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_plant_begin
  * and one ilqg_dev_plant_read — the caller's loop; nothing in it waits or copies.

@@ -1417,8 +1417,8 @@ static const PolicyParamMap *policy_param_map(int n_named, const int *named, con
 }
 // map == nullptr: k_policy<false>; else the same under the rows of `values` (device memory), k_policy<true>.  Each has its
 // own timing slot.
-static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, double alpha,
-                         int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, const double *dist,
+                         int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     if(roll_enter(d)) return 1;
     const dim3 grid = grid1((size_t)d->B * (size_t)R, ROLL_BLOCK);
     {   // (with a per-trajectory table — lane mapping only — the trajectory's row goes first, the roll-out's behind it)
@@ -1426,7 +1426,7 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
         with_rows(d, [&](auto... tr) {
             with_own_rows(map != nullptr, [&](auto... own) {
                 hipLaunchKernelGGL((k_policy<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
-                                   d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, tr..., own...);
+                                   d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, dist, dist_shared ? 1 : 0, tr..., own...);
             }, values, shared ? 1 : 0, map ? *map : PolicyParamMap{});
         });
     }
@@ -1434,9 +1434,11 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
     return roll_leave(d);
 }
 
-// the host form: the starts, then with a map the table of values, then the outputs, in one piece of the staging buffer
-static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, double alpha,
-                                 int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+// the host form: the starts, then with a map the table of values, then the disturbance table if there is one, then the
+// outputs, in one piece of the staging buffer
+static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared,
+                                 const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
+                                 double *u) {
     const size_t n = (size_t)d->B * (size_t)R;
     void *const host[5] = {cost, ok, x_end, x, u};
     const size_t bytes[5] = {n * sizeof(double), n * sizeof(int), n * NX * sizeof(double), n * (size_t)(d->N + 1) * NX * sizeof(double),
@@ -1444,7 +1446,9 @@ static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const P
     const size_t in_bytes = n * NX * sizeof(double);
     const size_t val_bytes = map ? (shared ? (size_t)R : n) * (size_t)map->W * sizeof(double) : 0;
     const size_t val_off = (in_bytes + 255) & ~(size_t)255;  // slices 256 bytes apart, the starts first
-    size_t off[5], total = val_off + ((val_bytes + 255) & ~(size_t)255);
+    const size_t dist_bytes = dist ? (dist_shared ? (size_t)R : n) * (size_t)d->N * NX * sizeof(double) : 0;
+    const size_t dist_off = val_off + ((val_bytes + 255) & ~(size_t)255);
+    size_t off[5], total = dist_off + ((dist_bytes + 255) & ~(size_t)255);
     for(int i = 0; i < 5; i++) {
         off[i] = total;
         if(host[i]) total += (bytes[i] + 255) & ~(size_t)255;
@@ -1453,9 +1457,11 @@ static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const P
     if(stage(d, total, &dev, &pin)) return 1;
     if(stage_in(d, dev, pin, x0, in_bytes)) return 1;
     if(map && stage_in(d, (char *)dev + val_off, pin ? (char *)pin + val_off : nullptr, values, val_bytes)) return 1;
+    if(dist && stage_in(d, (char *)dev + dist_off, pin ? (char *)pin + dist_off : nullptr, dist, dist_bytes)) return 1;
     void *dv[5];
     for(int i = 0; i < 5; i++) dv[i] = host[i] ? (void *)((char *)dev + off[i]) : nullptr;
-    if(launch_policy(d, R, (const double *)dev, map, (const double *)((char *)dev + val_off), shared, alpha, feedback, (double *)dv[0], (int *)dv[1],
+    if(launch_policy(d, R, (const double *)dev, map, (const double *)((char *)dev + val_off), shared,
+                     dist ? (const double *)((char *)dev + dist_off) : nullptr, dist_shared, alpha, feedback, (double *)dv[0], (int *)dv[1],
                      (double *)dv[2], (double *)dv[3], (double *)dv[4]))
         return 1;
     for(int i = 0; i < 5; i++) {
@@ -1468,27 +1474,30 @@ static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const P
     return 0;
 }
 
-// both entries: n_named == 0 = no table (k_policy<false>), else roll-out (b, r) under its row of `values`
+// both entries: n_named == 0 = no table (k_policy<false>), else roll-out (b, r) under its row of `values`; dist == nullptr =
+// no disturbance, else roll-out (b, r) under its rows of `dist` (dist_shared: row r for every trajectory)
 static int policy_rollout(ilqg_dev_t *d, bool on_host, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                          double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+                          const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
+                          double *u) {
     HIP_TRY(hipSetDevice(d->device));
     NEED_PARAMS(d);
     PolicyParamMap table;
     const PolicyParamMap *map = nullptr;
     if(!policy_args_ok(d, R, x0) || (n_named != 0 && !(map = policy_param_map(n_named, named, values, table)))) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
-    return on_host ? policy_rollout_staged(d, R, x0, map, values, shared, alpha, feedback, cost, ok, x_end, x, u)
-                   : launch_policy(d, R, x0, map, values, shared, alpha, feedback, cost, ok, x_end, x, u);
+    return on_host ? policy_rollout_staged(d, R, x0, map, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u)
+                   : launch_policy(d, R, x0, map, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 
-int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
-                            int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return policy_rollout(d, false, R, x0, n_named, named, values, shared, alpha, feedback, cost, ok, x_end, x, u);
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                            const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    return policy_rollout(d, false, R, x0, n_named, named, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared, double alpha,
-                                 int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return policy_rollout(d, true, R, x0, n_named, named, values, shared, alpha, feedback, cost, ok, x_end, x, u);
+int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                 const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
+                                 double *u) {
+    return policy_rollout(d, true, R, x0, n_named, named, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u);
 }
 
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {

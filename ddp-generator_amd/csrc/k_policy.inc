@@ -25,6 +25,15 @@
 // roll-out, so a lane's stores of a step are scattered 8-byte pieces, 64 cache lines per store instruction: accepted,
 // because they are optional — the costs-only call does not pay for them (one wave-uniform branch per step, no store).
 // A roll-out whose start is not finite ends at once with ok = 0.  All indices over B * R are size_t.
+//
+// Process noise (dist != null, a run-time argument as in k_plant: a null pointer is a wave-uniform branch and the call is
+// the call without a table).  Behind every step k = 0 .. N-1 the roll-out's state is pushed,
+//     x_{k+1} <- x_next + w[g][k]      (dist [B][R][N][NX]; with dist_shared != 0: w[r][k], dist [R][N][NX])
+// the rule of k_plant: the control of step k + 1 is computed at the disturbed state, row N - 1 moves the state the final
+// cost is evaluated at (x_end, x[N]).  ok = 0 as soon as a disturbed state is not finite, the one behind row N - 1
+// included; such a lane stays out of the later guarded steps as one whose guard failed does.  A lane's row is NX doubles
+// from its own 8-byte-aligned place, read right before the add: requested ahead of the step, as k_plant does with its
+// one lane per trajectory, the row lives across the step and costs its registers (profiles/r17_policy_noise.txt).
 __device__ __forceinline__ void load_policy_step(NomStep &s, const NomPtrs &q, bool use_l, bool use_K) {
 #pragma unroll
     for(int i = 0; i < NU; i++) s.u[i] = q.u[i * XSI];
@@ -74,7 +83,7 @@ template <bool PER_ROLLOUT_PARAMS, class... Rows>
 __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
                                                                          double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
                                                                          double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
-                                                                         Rows... rows) {
+                                                                         const double *__restrict__ dist, int dist_shared, Rows... rows) {
     // the pack: [the context's per-trajectory table, its map,] [values, shared, map of the roll-outs' own rows] (RowPack)
     const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
     if(g >= (size_t)P.B * (size_t)R) return;
@@ -94,6 +103,12 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
         if(ocost) ocost[g] = __builtin_nan("");
         return;
     }
+
+    // this roll-out's row of the disturbance table at step k: ((dist_shared ? r : g) * N + k) * NX, moved on step by step.
+    // Computed HERE, in front of the parameters: behind them the scalar registers are the parameters' (k_policy<true> of
+    // synth16p, the n = 16 pair with stored tensors, has none left for dist_shared: its library then does not compile).
+    size_t wat = (dist_shared ? g - (size_t)b * (size_t)R : g) * (size_t)N * NX;
+    asm volatile("" : "+v"(wat));
 
     ILQG_CALLBACKS(C, H);
     apply_rows<PER_ROLLOUT_PARAMS ? OWN_ROLLOUT : OWN_NONE>(C_values, C_table, P, b, g, (int)(g - (size_t)b * (size_t)R), rows...);
@@ -151,6 +166,16 @@ __global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs
 #pragma unroll
             for(int i = 0; i < NU; i++) ou[uat + i] = ct.u[i];
             uat += NU;
+        }
+        if(dist) {  // x_{k+1} <- x_next + w_k: the row is read HERE, behind the step (held across it, it costs the step's registers)
+            bool good = true;
+#pragma unroll
+            for(int i = 0; i < NX; i++) {
+                xnext[i] = xnext[i] + dist[wat + i];
+                good &= (__builtin_fabs(xnext[i]) < __builtin_inf());
+            }
+            wat += NX;
+            okc &= good ? 1 : 0;
         }
 #pragma unroll
         for(int i = 0; i < NX; i++) xc[i] = xnext[i];

@@ -338,14 +338,46 @@ def _receding_plant(solver, entry, rounds, steps, iterations, feedback, x_plant,
     return out
 
 
-def _policy_rollout(solver, entry, x0, alpha, feedback, trajectories, params):
-    """BatchSolver.policy_rollout / MultiSolver.policy_rollout in host memory: the checks, the arrays and the one library call"""
+def _rollout_disturbance(solver, disturbance, R, device=None):
+    """(address, disturbance_shared, what must outlive the call) of policy_rollout(disturbance=...): [B, R, N, nx], or
+    [R, N, nx] for every trajectory; a host array of real numbers, or with `device` a contiguous float64 torch tensor on that
+    GPU, read where it is.  Checked here, before any library call."""
+    who, what = "policy_rollout", "disturbance"
+    full, short = (solver.B, R, solver.N, solver.problem.nx), (R, solver.N, solver.problem.nx)
+    if device is None:
+        a = _host_numbers(who, what, disturbance) if _is_cuda(disturbance) else _plant_numbers(who, what, disturbance)  # (the first refuses)
+    else:
+        if not _is_cuda(disturbance):
+            raise IlqgError("%s: %s is in host memory and device=True: pass a float64 torch tensor on the solver's GPU" % (who, what))
+        a = disturbance
+    shape = tuple(int(n) for n in a.shape)
+    if shape not in (full, short):
+        raise IlqgError("%s: %s has shape %s, expected %s = (B, R, n_hor, nx) or %s for every trajectory, with R = %d as in x0" % (
+            who, what, shape, full, short, R))
+    shared = 1 if shape == short and shape != full else 0
+    if device is None:
+        a = np.ascontiguousarray(a)
+        return _address(a), shared, a
+    return _cuda_address(a, shape, device, "%s: %s" % (who, what)), shared, a
+
+
+def _policy_rollout(solver, entry, x0, alpha, feedback, trajectories, params, disturbance=None):
+    """BatchSolver.policy_rollout / MultiSolver.policy_rollout in host memory: the checks, the arrays and the one library call.
+    Without a disturbance the entries that have always been there are called with the arguments they have always had; with
+    one, the superset entry `entry`_noise (n_names = 0: no parameter table)."""
     x0 = _policy_starts(x0, solver.B, solver.problem.nx)
     R, named = x0.shape[1], ()
     out, ptr = _rollout_outputs(solver, R, trajectories)
+    if disturbance is not None:
+        dist, dist_shared, keep = _rollout_disturbance(solver, disturbance, R)
+        named = (0, None, None, 0)
     if params is not None:
         names, values, shared = _rollout_params(solver, params, R)
-        entry, named = entry + "_params", (len(names), names, _address(values), shared)
+        named = (len(names), names, _address(values), shared)
+    if disturbance is not None:
+        entry, named = entry + "_noise", named + (dist, dist_shared)
+    elif params is not None:
+        entry += "_params"
     solver._ck(_receding_entry(solver.lib, entry)(solver.h, R, _address(x0), *named, float(alpha), 1 if feedback else 0, *ptr))
     return out
 
@@ -487,6 +519,11 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_policy_rollout_params.argtypes = named
         lib.ilqg_batch_policy_rollout_params_device.argtypes = named + [v]
         lib.ilqg_multi_policy_rollout_params.argtypes = named
+    if hasattr(lib, "ilqg_batch_policy_rollout_noise"):  # (and under a disturbance table per roll-out)
+        noise = [v, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, C.c_int, v, C.c_int, C.c_double, C.c_int, v, v, v, v, v]
+        lib.ilqg_batch_policy_rollout_noise.argtypes = noise
+        lib.ilqg_batch_policy_rollout_noise_device.argtypes = noise + [v]
+        lib.ilqg_multi_policy_rollout_noise.argtypes = noise
     if hasattr(lib, "ilqg_batch_set_params_batch"):  # (and for problem parameters per trajectory)
         lib.ilqg_batch_set_params_batch.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v]
         lib.ilqg_batch_set_params_batch_device.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v, v]
@@ -763,7 +800,7 @@ class BatchSolver:
         self._ck(entry(self.h, int(steps), *ptr, stream))
         return out
 
-    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False, params=None):
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False, params=None, disturbance=None):
         """every plan's feedback policy rolled out from R starts per trajectory on the GPU (ilqg_batch_policy_rollout):
         x0 [B,R,nx], or [R,nx] for every trajectory; u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if
         feedback], clamped, through the problem's dynamics and cost.  The policy is what head(N, gains=True) returns — behind
@@ -777,12 +814,17 @@ class BatchSolver:
         [R,size] for all trajectories (the last axis may be left out for size 1), R as in x0.  The policy stays the plan's:
         its gains were computed under the batch's parameters.  Per-time-step parameters stay shared and cannot be named;
         the batch's parameters do not change.  With device=True contiguous float64 torch tensors on the solver's GPU,
-        packed with torch.cat on torch's current stream (a single tensor is read where it is)."""
+        packed with torch.cat on torch's current stream (a single tensor is read where it is).
+        disturbance: process noise, a push on the state behind every step (ilqg_batch_policy_rollout_noise): roll-out (b, r)
+        goes on from x_next + disturbance[b, r, k] behind step k = 0 .. N-1 — [B,R,N,nx], or [R,N,nx] for every trajectory
+        (common random numbers).  The control of step k+1 is computed at the disturbed state; row N-1 moves x_end, x[N] and the
+        state the final cost is evaluated at; ok is 0 too where a disturbed state is not finite.  A numpy array, or with
+        device=True a contiguous float64 torch tensor on the solver's GPU.  None: the call without a table, unchanged."""
         nx, B, named = self.problem.nx, self.B, ()
         if not device:
             if _is_cuda(x0):
                 raise IlqgError("policy_rollout: x0 is a tensor on the device: pass device=True")
-            return _policy_rollout(self, "ilqg_batch_policy_rollout", x0, alpha, feedback, trajectories, params)
+            return _policy_rollout(self, "ilqg_batch_policy_rollout", x0, alpha, feedback, trajectories, params, disturbance)
         if not _is_cuda(x0):
             raise IlqgError("policy_rollout: device=True and x0 is in host memory: pass a float64 torch tensor on the solver's GPU")
         if len(x0.shape) != 3 or int(x0.shape[1]) < 1:
@@ -791,12 +833,18 @@ class BatchSolver:
         px = _cuda_address(x0, (B, R, nx), self.device, "x0")
         if params is not None:
             names, cols, shared = _rollout_params(self, params, R, self.device)
-        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_device" if params is None else "ilqg_batch_policy_rollout_params_device")
+        if disturbance is not None:
+            dist, dist_shared, keep_dist = _rollout_disturbance(self, disturbance, R, self.device)
+            named = (0, None, None, 0)
+        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_noise_device" if disturbance is not None else
+                                "ilqg_batch_policy_rollout_device" if params is None else "ilqg_batch_policy_rollout_params_device")
         torch, dev, stream = _torch_stream(self.device)
         out, ptr = _rollout_outputs(self, R, trajectories, torch, dev)
         if params is not None:
             values, keep = _tensor_table(torch, dev, cols)
             named = (len(names), names, values, shared)
+        if disturbance is not None:
+            named = named + (dist, dist_shared)
         self._ck(entry(self.h, R, px, *named, float(alpha), 1 if feedback else 0, *ptr, stream))
         return out
 
@@ -1126,10 +1174,11 @@ class MultiSolver:
         self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *ptr))
         return out
 
-    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, params=None):
-        """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout, with params ilqg_multi_policy_rollout_params),
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, params=None, disturbance=None):
+        """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout, with params ilqg_multi_policy_rollout_params,
+        with a disturbance ilqg_multi_policy_rollout_noise: a [B,R,N,nx] table sharded by rows, a [R,N,nx] one given to every shard),
         numpy arrays"""
-        return _policy_rollout(self, "ilqg_multi_policy_rollout", x0, alpha, feedback, trajectories, params)
+        return _policy_rollout(self, "ilqg_multi_policy_rollout", x0, alpha, feedback, trajectories, params, disturbance)
 
     def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None, windows=None):
         """BatchSolver.receding_plant of every shard, one shard after the other (ilqg_multi_receding_plant, with windows

@@ -251,6 +251,30 @@ int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double
 int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
                                             const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
                                             double *x, double *u, void *stream);
+/* The same roll-outs UNDER PROCESS NOISE, each under a disturbance table of its own: the closed-loop cost of a plan over its
+ * whole horizon when the state is pushed behind every step — what the feedback gains L exist for.  The superset entry: with
+ * disturbance = NULL and n_names = 0 it is ilqg_batch_policy_rollout, with disturbance = NULL and n_names > 0
+ * ilqg_batch_policy_rollout_params, the same kernels, launches and bits.
+ *
+ * For roll-out (b, r) and step k = 0 .. n_hor-1, behind the step of forward_pass (the rule of ilqg_batch_receding_plant,
+ * step (2)):      x_{k+1} <- x_next + w[b][r][k]
+ * disturbance: [B][n_starts][n_hor][N_X], or with disturbance_shared != 0 [n_starts][n_hor][N_X], used for every trajectory
+ * (common random numbers across trajectories).  The control of step k+1 is computed at the disturbed state; row n_hor-1 moves
+ * the end state, so x_end, x[n_hor] and the final cost, which is evaluated at the disturbed state.  x holds the states the
+ * controls were applied at, x[0] = the start; u the clamped controls.  ok = 0 as soon as a guard fails or a disturbed state is
+ * not finite, the one behind row n_hor-1 included; no other roll-out changes by a bit.
+ * n_names = 0: no parameter table — names, values and shared are not read.  n_names > 0: the rules and refusals of
+ * ilqg_batch_policy_rollout_params; the order stays "trajectory's row, then roll-out's row".  Refused before anything is
+ * launched or changed, the argument named: what those entries refuse and, in the device form, a disturbance that is not device
+ * memory of the context's device.  All outputs NULL is a no-op after the checks.  The host form stages the table behind the
+ * values through the context's buffers, which only grow; the device form reads it where it lies, under the stream contract of
+ * ilqg_batch_head_device. */
+int ilqg_batch_policy_rollout_noise(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, const double *disturbance, int disturbance_shared, double alpha, int feedback, double *cost,
+                                    int *ok, double *x_end, double *x, double *u);
+int ilqg_batch_policy_rollout_noise_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
+                                           const double *values, int shared, const double *disturbance, int disturbance_shared, double alpha,
+                                           int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream);
 /* THE CLOSED LOOP OF PLANNER AND PLANT, resident on the device for `rounds` control intervals — ilqg_batch_receding with a
  * plant that has a state of its own, may differ from the model and may be disturbed: what closed-loop cost the controllers
  * reach when the wheelbase is 5 % off and the state is pushed at every step.  Each of the `rounds` rounds is
@@ -515,6 +539,11 @@ int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, d
 /* ilqg_batch_policy_rollout_params per shard (host memory): values is offset by the shard's first trajectory unless shared */
 int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                      int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+/* ilqg_batch_policy_rollout_noise per shard (host memory): a full disturbance table is offset by the shard's first trajectory
+ * like values, a shared one is given to every shard */
+int ilqg_multi_policy_rollout_noise(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, const double *disturbance, int disturbance_shared, double alpha, int feedback, double *cost,
+                                    int *ok, double *x_end, double *x, double *u);
 /* ilqg_batch_receding_plant per shard, one shard after the other (host memory): every [B]... array is offset by the shard's first trajectory */
 int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,

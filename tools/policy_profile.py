@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Roll-outs of the policy from perturbed starts (BatchSolver.policy_rollout, k_policy) against the line search's roll-outs.
 
-    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search] [--params]
+    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search] [--params] [--noise]
 
 One process per invocation, one stream group (a launch's HIP-event time is then that launch alone).  The yardstick is the
 line search of the SAME run with ls_keep = 0, ls_split = 0: k_rollout[search] rolls out (active trajectories) x n_alpha
@@ -16,6 +16,12 @@ events (ilqg_batch_get_timing), read before and after every leg.  Not part of be
 SINGLE parameter named, each roll-out with a row of its own ([B, R, W], nominal * (1 + 0.05 N(0, 1))), and at R = 8 one
 [R, W] table shared by every trajectory against the per-trajectory table.  Each is reported as a ratio to the plain k_policy
 launch of the same R in the same run.
+
+--noise adds the roll-outs under a disturbance table (policy_rollout(disturbance=...), the same k_policy with a table argument)
+to the same alternation: R = 8, costs only, device form, with a table per roll-out ([B, R, N, nx], 0.01 N(0, 1) drawn on the
+GPU) and with one [R, N, nx] table shared by every trajectory, each as a ratio to the plain k_policy launch at R = 8 of the
+same run (the leg "device R=8").  That plain launch is also what a build of the parent commit is compared with — the same
+tool run there, alternating with this one: a null table is meant to cost nothing measurable.
 """
 import argparse
 import os
@@ -33,7 +39,7 @@ def spread(v, unit="ms"):
     return "median %10.4f %s  min %10.4f  max %10.4f  (n = %d)" % (np.median(v), unit, v.min(), v.max(), len(v))
 
 
-def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=False):
+def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=False, with_noise=False):
     import torch
     if scalar_search:  # (read once, when the context is made)
         os.environ["ILQG_NO_ROLLOUT_PARTS"] = "1"
@@ -90,8 +96,19 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
         print("   --params: %d fixed-size parameters, %d doubles per row when all are named (%s); the single one is %s" % (
             len(fixed), sum(size for _, size in fixed), ", ".join(n for n, _ in fixed), single), flush=True)
 
+    noise = {}
+    if with_noise:
+        gen_w = torch.Generator(device="cuda").manual_seed(7)
+        # (scaled in place: a second copy of the table per roll-out is 8 or 17 GB more of the device's memory)
+        noise["noise full R=8"] = torch.randn((B, 8, N, nx), dtype=torch.float64, device="cuda", generator=gen_w).mul_(0.01)
+        noise["noise shared R=8"] = torch.randn((8, N, nx), dtype=torch.float64, device="cuda", generator=gen_w).mul_(0.01)
+        legs += [(name, 8) for name in noise]
+        print("   --noise: a table per roll-out of %.2f GB, a shared one of %.1f KB" % (B * 8 * N * nx * 8 / 1e9, 8 * N * nx * 8 / 1e3), flush=True)
+
     def leg(name, R):
-        if name in tables:
+        if name in noise:
+            s.policy_rollout(dev_starts[R], device=True, disturbance=noise[name])
+        elif name in tables:
             s.policy_rollout(dev_starts[R], device=True, params=tables[name])
         elif name == "search":
             s.iterate(1)
@@ -150,6 +167,10 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
         m, p0 = np.median(kern[name]), np.median(kern[plain])
         print("ratio per launch, k_policy_params %-11s / k_policy %-11s: %.3f  (medians; its repeats span %.3f .. %.3f of its median, the plain launch's %.3f .. %.3f of its)" % (
             name, plain, m / p0, np.min(kern[name]) / m, np.max(kern[name]) / m, np.min(kern[plain]) / p0, np.max(kern[plain]) / p0))
+    for name in noise:
+        m, p0 = np.median(kern[name]), np.median(kern["device R=8"])
+        print("ratio per launch, k_policy %-16s / k_policy device R=8 (no table): %.3f  (medians; its repeats span %.3f .. %.3f of its median, the plain launch's %.3f .. %.3f of its)" % (
+            name, m / p0, np.min(kern[name]) / m, np.max(kern[name]) / m, np.min(kern["device R=8"]) / p0, np.max(kern["device R=8"]) / p0))
     if with_params:
         print("ratio per launch, shared [R, W] table / per-trajectory [B, R, W] table at R = 8, all parameters named: %.3f" % (
             np.median(kern["shared R=8"]) / np.median(kern["all R=8"])))
@@ -171,12 +192,14 @@ def main():
                     "several wavefronts per 64 trajectories): the search on k_rollout instead, one lane per roll-out like k_policy")
     ap.add_argument("--params", action="store_true", help="also the roll-outs under parameters per roll-out (k_policy_params): all fixed-size "
                     "parameters named, a single one named, and a shared against a per-trajectory table at R = 8")
+    ap.add_argument("--noise", action="store_true", help="also the roll-outs under a disturbance table at R = 8, costs only: a table per roll-out "
+                    "and one shared by every trajectory, as ratios to the plain launch of the same run")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.load_package()
     from ddp_generator_amd import ilqg, synth
     for config in (("headline", "config5") if a.config == "both" else (a.config,)):
-        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search, a.params)
+        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search, a.params, a.noise)
 
 
 if __name__ == "__main__":
