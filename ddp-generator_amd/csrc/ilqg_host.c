@@ -563,19 +563,14 @@ static int stream_in(ilqg_batch_t *c, void *stream, const char *what) {
 /* Receding horizon (no reference counterpart as a call; it is what the MEX entry's caller does between two calls:
  * u_nom = [u(:, s+1:end), tail] and a new x0, iLQG_mex.c:113-120).  The plan moves on the device (ilqg_dev_shift); only
  * x0_new and u_tail go up, or are read where they lie (on_device: ilqg_batch_shift_device).  Then exactly ilqg_batch_init:
- * initial roll-out, solver entry state. */
-static int shift(ilqg_batch_t *c, const char *who, int on_device, int steps, const double *x0_new, const double *u_tail, void *stream) {
-    const named_ptr_t ptrs[] = {{x0_new, "x0_new"}, {u_tail, "u_tail"}};
+ * initial roll-out, solver entry state.
+ * shift_groups is that for every group, behind the checks.  round < 0: the caller's shift by `steps` with its x0_new / u_tail;
+ * round >= 0: the shift step of that round of the open resident loop, which has the steps, the windows and the new x_0 on
+ * the device. */
+static int shift_groups(ilqg_batch_t *c, int round, int on_device, int steps, const double *x0_new, const double *u_tail, void *stream) {
     int g;
-    if(steps < 0 || steps >= c->N) {
-        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 0 .. n_hor - 1 = %d", who, steps, c->N - 1);
-        return 1;
-    }
-    if(on_device && device_ptrs(c, who, ptrs, 2)) return 1;
-    if(push_config(c)) return 1;
-    if(on_device && stream_in(c, stream, "shift: stream")) return 1;
     /* the shift kernel brings U home and clears the location indices, then the caller's values */
-    EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, x0_new == NULL)) return fail(c, "shift");
+    EACH_GROUP(g) if(round >= 0 ? ilqg_dev_loop_shift(c->dev[g], round) : ilqg_dev_shift(c->dev[g], steps, x0_new == NULL)) return fail(c, "shift");
     EACH_GROUP(g) {
         const double *const x0_g = x0_new ? x0_new + (size_t)c->first[g] * N_X : NULL;
         const double *const tail_g = (u_tail && steps > 0) ? u_tail + (size_t)c->first[g] * steps * N_U : NULL;
@@ -586,6 +581,17 @@ static int shift(ilqg_batch_t *c, const char *who, int on_device, int steps, con
         if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift: stream");
     }
     return restart(c);
+}
+static int shift(ilqg_batch_t *c, const char *who, int on_device, int steps, const double *x0_new, const double *u_tail, void *stream) {
+    const named_ptr_t ptrs[] = {{x0_new, "x0_new"}, {u_tail, "u_tail"}};
+    if(steps < 0 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 0 .. n_hor - 1 = %d", who, steps, c->N - 1);
+        return 1;
+    }
+    if(on_device && device_ptrs(c, who, ptrs, 2)) return 1;
+    if(push_config(c)) return 1;
+    if(on_device && stream_in(c, stream, "shift: stream")) return 1;
+    return shift_groups(c, -1, on_device, steps, x0_new, u_tail, stream);
 }
 
 int ilqg_batch_shift(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail) {
@@ -668,75 +674,6 @@ static int window_names(ilqg_batch_t *c, const char *who, int n_windows, const c
         by_param[k] = future[i];
     }
     return 0;
-}
-/* the futures go up once, every group its rows of a parameter that has rows (ilqg_dev_windows_begin) */
-static int windows_begin(ilqg_batch_t *c, const char *who, int rounds, int steps, const double *const *by_param) {
-    const size_t per = (size_t)rounds * (size_t)steps;
-    const double *of_group[WINDOW_MAX_PARAMS];
-    int g, i;
-    EACH_GROUP(g) {
-        for(i = 0; i < WINDOW_MAX_PARAMS; i++) of_group[i] = (by_param[i] && c->ps_on[i]) ? by_param[i] + (size_t)c->first[g] * per : by_param[i];
-        if(ilqg_dev_windows_begin(c->dev[g], rounds, steps, of_group)) return fail(c, who);
-    }
-    return 0;
-}
-/* round r: every window moves `steps` on, on the device in one launch per group, and the host mirror of a shared window with
- * it (a later ilqg_batch_set_param of another parameter re-pushes from that mirror) */
-static int windows_move(ilqg_batch_t *c, const char *who, int r, int steps, const double *const *by_param) {
-    int g, i, k;
-    const int n = c->N + 1;
-    EACH_GROUP(g) if(ilqg_dev_windows_move(c->dev[g], r)) return fail(c, who);
-    for(i = 0; i < n_params && i < WINDOW_MAX_PARAMS; i++)
-        if(paramdesc[i]->size == -1 && !c->ps_on[i]) {
-            const double *tail = by_param[i] ? by_param[i] + (size_t)r * (size_t)steps : NULL;
-            for(k = 0; k < n; k++) c->p[i][k] = k + steps < n ? c->p[i][k + steps] : (tail ? tail[k + steps - n] : c->p[i][n - 1]);
-        }
-    return 0;
-}
-
-static int iterate_groups(ilqg_batch_t *c, int n);
-/* ilqg_batch_receding (windowed = 0: a per-time-step problem is refused) and ilqg_batch_receding_windows */
-static int receding(ilqg_batch_t *c, const char *who, int windowed, int rounds, int steps, int iterations, int n_windows,
-                    const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied, double *cost) {
-    const double *by_param[WINDOW_MAX_PARAMS];
-    int g, r;
-    if(rounds < 1 || iterations < 0) {
-        snprintf(c->err, sizeof(c->err), "%s: need rounds >= 1 and iterations >= 0", who);
-        return 1;
-    }
-    if(steps < 1 || steps >= c->N) {
-        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", who, steps, c->N - 1);
-        return 1;
-    }
-    if(!windowed && no_step_params(c, who)) return 1;
-    if(windowed && window_names(c, who, n_windows, window_names_, future, by_param)) return 1;
-    if(push_config(c)) return 1;
-    EACH_GROUP(g) if(ilqg_dev_log_begin(c->dev[g], rounds, steps)) return fail(c, "receding: log");
-    if(windowed && windows_begin(c, "receding: windows", rounds, steps, by_param)) return 1;
-    for(r = 0; r < rounds; r++) {
-        if(iterate_groups(c, iterations)) return 1;
-        EACH_GROUP(g) if(ilqg_dev_log_append(c->dev[g], r)) return fail(c, "receding: log");
-        /* the windows move before the shift: its initial roll-out reads them */
-        if(windowed && windows_move(c, "receding: windows", r, steps, by_param)) return 1;
-        if(ilqg_batch_shift(c, steps, NULL, NULL)) return 1;
-    }
-    EACH_GROUP(g) {
-        const size_t at = (size_t)c->first[g] * rounds * steps;
-        if(ilqg_dev_log_read(c->dev[g], x_applied ? x_applied + at * N_X : NULL, u_applied ? u_applied + at * N_U : NULL,
-                             cost ? cost + (size_t)c->first[g] * rounds : NULL))
-            return fail(c, "receding: log");
-    }
-    return 0;
-}
-
-int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, double *x_applied, double *u_applied, double *cost) {
-    return receding(c, "ilqg_batch_receding", 0, rounds, steps, iterations, 0, NULL, NULL, x_applied, u_applied, cost);
-}
-
-int ilqg_batch_receding_windows(ilqg_batch_t *c, int rounds, int steps, int iterations, int n_windows, const char *const *window_names_,
-                                const double *const *future, double *x_applied, double *u_applied, double *cost) {
-    if(!c) return 1;
-    return receding(c, "ilqg_batch_receding_windows", 1, rounds, steps, iterations, n_windows, window_names_, future, x_applied, u_applied, cost);
 }
 
 /* The control interval of a caller with its own plant: {iterate; head; the caller's plant step; shift}.  The heads are read
@@ -1113,81 +1050,129 @@ int ilqg_batch_shift_param_batch_device(ilqg_batch_t *c, const char *name, int s
     return shift_param_batch(c, "ilqg_batch_shift_param_batch_device", 1, name, steps, tail, stream);
 }
 
-/* The closed loop of planner and plant, resident on the device (k_plant.inc): per round { iterate; the plants advance
- * `steps` steps from their own states under the plans' policies and the plants' parameters; the plans shift and start again
- * from the plants' states }.  Everything is refused before anything is launched or allocated; values, disturbance and
- * x_plant go up once (ilqg_dev_plant_begin), the logs come down once (ilqg_dev_plant_read), and nothing waits in between. */
-static int receding_plant(ilqg_batch_t *c, const char *who, int windowed, int rounds, int steps, int iterations, int feedback, double *x_plant,
-                          int n_names, const char *const *names, const double *values, const double *disturbance, int n_windows,
-                          const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
-                          double *cost_applied, double *plan_cost, int *ok) {
-    const double *by_param[WINDOW_MAX_PARAMS];
-    int g, r, named[POLICY_MAX_NAMES], W = 0;
+/* The receding-horizon loop, resident on the device: per round { iterate; apply — the plans' heads are recorded, or with a
+ * plant (k_plant.inc) the plants advance `steps` steps from their own states under the plans' policies and the plants'
+ * parameters —; the windows move; the plans shift and start again, from the state they reach or from the plants' }.  Everything
+ * is refused before anything is launched or allocated; what the caller gives goes up once (ilqg_dev_loop_begin), the logs
+ * come down once (ilqg_dev_loop_read), and nothing waits in between.  The four public entries fill this: */
+typedef struct {
+    const char *who;
+    int plant;    /* 0: ilqg_batch_receding[_windows]; the fields down to `disturbance` are not read and the logs are x_applied,
+                   * u_applied and plan_cost */
+    int windowed; /* 0: a per-time-step problem is refused, the three fields below are not read */
+    int rounds, steps, iterations, feedback;
+    double *x_plant;
+    int n_names;
+    const char *const *names;
+    const double *values, *disturbance;
+    int n_windows;
+    const char *const *window_names;
+    const double *const *future;
+    double *x_applied, *u_applied, *cost_applied, *plan_cost;
+    int *ok;
+} receding_t;
+static int iterate_groups(ilqg_batch_t *c, int n);
+static int receding(ilqg_batch_t *c, const receding_t *a) {
+    const double *by_param[WINDOW_MAX_PARAMS], *of_group[WINDOW_MAX_PARAMS];
+    const int rounds = a->rounds, steps = a->steps, n = c->N + 1;
+    const size_t per = (size_t)(rounds > 0 ? rounds : 0) * (size_t)(steps > 0 ? steps : 0);
+    int g, r, i, k, named[POLICY_MAX_NAMES], W = 0;
     if(rounds < 1) {
-        snprintf(c->err, sizeof(c->err), "%s: rounds = %d, must be at least 1", who, rounds);
+        snprintf(c->err, sizeof(c->err), "%s: rounds = %d, must be at least 1", a->who, rounds);
         return 1;
     }
-    if(iterations < 0) {
-        snprintf(c->err, sizeof(c->err), "%s: iterations = %d, must not be negative", who, iterations);
+    if(a->iterations < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: iterations = %d, must not be negative", a->who, a->iterations);
         return 1;
     }
     if(steps < 1 || steps >= c->N) {
-        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", who, steps, c->N - 1);
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 1 .. n_hor - 1 = %d", a->who, steps, c->N - 1);
         return 1;
     }
-    if(!windowed && no_step_params(c, who)) return 1;
-    if(n_names < 0) {
-        snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0: the plant is the model)", who, n_names);
+    if(!a->windowed && no_step_params(c, a->who)) return 1;
+    if(a->plant && a->n_names < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0: the plant is the model)", a->who, a->n_names);
         return 1;
     }
-    if(n_names > 0 && policy_names(c, who, n_names, names, values, named, &W)) return 1;
-    if(windowed && window_names(c, who, n_windows, window_names_, future, by_param)) return 1;
+    if(a->plant && a->n_names > 0 && policy_names(c, a->who, a->n_names, a->names, a->values, named, &W)) return 1;
+    if(a->windowed && window_names(c, a->who, a->n_windows, a->window_names, a->future, by_param)) return 1;
     if(push_config(c)) return 1;
-    {
-        const size_t per = (size_t)rounds * (size_t)steps;
-        EACH_GROUP(g) {
-            const size_t first = (size_t)c->first[g];
-            if(ilqg_dev_plant_begin(c->dev[g], rounds, steps, x_plant ? x_plant + first * N_X : NULL, n_names, named,
-                                    n_names > 0 ? values + first * (size_t)W : NULL, disturbance ? disturbance + first * per * N_X : NULL))
-                return fail(c, "receding_plant");
+    EACH_GROUP(g) {
+        const size_t first = (size_t)c->first[g];
+        ilqg_dev_loop_t loop;
+        memset(&loop, 0, sizeof(loop));
+        loop.rounds = rounds;
+        loop.steps = steps;
+        if(a->plant) {
+            loop.plant = 1;
+            loop.x_plant = a->x_plant ? a->x_plant + first * N_X : NULL;
+            loop.n_named = a->n_names;
+            loop.named = named;
+            loop.values = a->n_names > 0 ? a->values + first * (size_t)W : NULL;
+            loop.disturbance = a->disturbance ? a->disturbance + first * per * N_X : NULL;
         }
-        if(windowed && windows_begin(c, "receding_plant: windows", rounds, steps, by_param)) return 1;
-        for(r = 0; r < rounds; r++) {
-            if(iterate_groups(c, iterations)) return 1;
-            /* the plants read the plans the shift moves: k_plant is enqueued in front of k_shift_* on every group's stream */
-            EACH_GROUP(g) if(ilqg_dev_plant_advance(c->dev[g], r, feedback)) return fail(c, "receding_plant: plant");
-            /* the plants have read the round's windows where they stood; they move before the shift, whose initial roll-out reads them */
-            if(windowed && windows_move(c, "receding_plant: windows", r, steps, by_param)) return 1;
-            /* ilqg_batch_shift(c, steps, x0_new = the plants' states, NULL), the states being on the device already */
-            EACH_GROUP(g) if(ilqg_dev_shift(c->dev[g], steps, 0)) return fail(c, "shift");
-            EACH_GROUP(g) if(ilqg_dev_plant_put_x0(c->dev[g])) return fail(c, "shift: x0_new");
-            if(restart(c)) return 1;
+        if(a->windowed) { /* every group its rows of a future whose parameter has rows */
+            for(i = 0; i < WINDOW_MAX_PARAMS; i++) of_group[i] = (by_param[i] && c->ps_on[i]) ? by_param[i] + first * per : by_param[i];
+            loop.windows = 1;
+            loop.future = of_group;
         }
-        EACH_GROUP(g) {
-            const size_t first = (size_t)c->first[g];
-            if(ilqg_dev_plant_read(c->dev[g], x_plant ? x_plant + first * N_X : NULL, x_applied ? x_applied + first * per * N_X : NULL,
-                                   u_applied ? u_applied + first * per * N_U : NULL, cost_applied ? cost_applied + first * rounds : NULL,
-                                   plan_cost ? plan_cost + first * rounds : NULL, ok ? ok + first : NULL))
-                return fail(c, "receding_plant: log");
-        }
+        if(ilqg_dev_loop_begin(c->dev[g], &loop)) return fail(c, a->plant ? "receding_plant" : "receding");
+    }
+    for(r = 0; r < rounds; r++) {
+        if(iterate_groups(c, a->iterations)) return 1;
+        /* the plants read the plans the shift moves: k_plant is enqueued in front of k_shift_* on every group's stream */
+        EACH_GROUP(g) if(ilqg_dev_loop_apply(c->dev[g], r, a->feedback)) return fail(c, a->plant ? "receding_plant: plant" : "receding: log");
+        /* the plants have read the round's windows where they stood; they move — in the shift step, on the device, and here the
+         * host mirror of a shared window with them (a later ilqg_batch_set_param of another parameter re-pushes from that
+         * mirror) — before the shift, whose initial roll-out reads them */
+        for(i = 0; a->windowed && i < n_params && i < WINDOW_MAX_PARAMS; i++)
+            if(paramdesc[i]->size == -1 && !c->ps_on[i]) {
+                const double *tail = by_param[i] ? by_param[i] + (size_t)r * (size_t)steps : NULL;
+                for(k = 0; k < n; k++) c->p[i][k] = k + steps < n ? c->p[i][k + steps] : (tail ? tail[k + steps - n] : c->p[i][n - 1]);
+            }
+        /* ilqg_batch_shift(c, steps, NULL, NULL), or with x0_new = the plants' states, which are on the device already */
+        if(shift_groups(c, r, 0, steps, NULL, NULL, NULL)) return 1;
+    }
+    EACH_GROUP(g) {
+        const size_t first = (size_t)c->first[g];
+        if(ilqg_dev_loop_read(c->dev[g], a->x_plant ? a->x_plant + first * N_X : NULL, a->x_applied ? a->x_applied + first * per * N_X : NULL,
+                              a->u_applied ? a->u_applied + first * per * N_U : NULL, a->cost_applied ? a->cost_applied + first * rounds : NULL,
+                              a->plan_cost ? a->plan_cost + first * rounds : NULL, a->ok ? a->ok + first : NULL))
+            return fail(c, a->plant ? "receding_plant: log" : "receding: log");
     }
     return 0;
+}
+
+int ilqg_batch_receding(ilqg_batch_t *c, int rounds, int steps, int iterations, double *x_applied, double *u_applied, double *cost) {
+    const receding_t a = {"ilqg_batch_receding", 0, 0, rounds, steps, iterations, 0, NULL, 0, NULL, NULL, NULL, 0, NULL, NULL, x_applied, u_applied, NULL,
+                          cost, NULL};
+    return receding(c, &a);
+}
+
+int ilqg_batch_receding_windows(ilqg_batch_t *c, int rounds, int steps, int iterations, int n_windows, const char *const *window_names_,
+                                const double *const *future, double *x_applied, double *u_applied, double *cost) {
+    const receding_t a = {"ilqg_batch_receding_windows", 0, 1, rounds, steps, iterations, 0, NULL, 0, NULL, NULL, NULL, n_windows, window_names_, future,
+                          x_applied, u_applied, NULL, cost, NULL};
+    if(!c) return 1;
+    return receding(c, &a);
 }
 
 int ilqg_batch_receding_plant(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
                               double *cost_applied, double *plan_cost, int *ok) {
-    return receding_plant(c, "ilqg_batch_receding_plant", 0, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, 0,
-                          NULL, NULL, x_applied, u_applied, cost_applied, plan_cost, ok);
+    const receding_t a = {"ilqg_batch_receding_plant", 1, 0, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, 0, NULL,
+                          NULL, x_applied, u_applied, cost_applied, plan_cost, ok};
+    return receding(c, &a);
 }
 
 int ilqg_batch_receding_plant_windows(ilqg_batch_t *c, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                                       const char *const *names, const double *values, const double *disturbance, int n_windows,
                                       const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
                                       double *cost_applied, double *plan_cost, int *ok) {
+    const receding_t a = {"ilqg_batch_receding_plant_windows", 1, 1, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance,
+                          n_windows, window_names_, future, x_applied, u_applied, cost_applied, plan_cost, ok};
     if(!c) return 1;
-    return receding_plant(c, "ilqg_batch_receding_plant_windows", 1, rounds, steps, iterations, feedback, x_plant, n_names, names, values,
-                          disturbance, n_windows, window_names_, future, x_applied, u_applied, cost_applied, plan_cost, ok);
+    return receding(c, &a);
 }
 
 /* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param), and in the host
@@ -2345,49 +2330,49 @@ int ilqg_multi_policy_rollout_noise(ilqg_multi_t *m, int n_starts, const double 
     return multi_policy_rollout(m, "ilqg_batch_policy_rollout_noise", params, n_starts, x0, params ? n_names : 0, names, params ? values : NULL,
                                 params ? shared : 0, disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u);
 }
-int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
-                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
-                              double *cost_applied, double *plan_cost, int *ok) {
-    const size_t W = values ? rows_width(n_names, names) : 0;
-    const size_t rn = rounds > 0 ? (size_t)rounds : 0, per = rn * (steps > 0 ? (size_t)steps : 0);
-    int g;
-    EACH_SHARD(g) {
-        const size_t at = (size_t)m->first[g];
-        if(ilqg_batch_receding_plant(m->shard[g], rounds, steps, iterations, feedback, x_plant ? x_plant + at * N_X : NULL, n_names, names,
-                                     values ? values + at * W : NULL, disturbance ? disturbance + at * per * N_X : NULL,
-                                     x_applied ? x_applied + at * per * N_X : NULL, u_applied ? u_applied + at * per * N_U : NULL,
-                                     cost_applied ? cost_applied + at * rn : NULL, plan_cost ? plan_cost + at * rn : NULL, ok ? ok + at : NULL))
-            return multi_fail(m, g);
-    }
-    return 0;
-}
-/* ilqg_batch_receding_plant_windows per shard.  A future is offset by the shard's first trajectory where its name has rows in the
- * shard; what the shard would refuse (a name that is no per-time-step parameter, too many names) passes as it is, and the
- * shard refuses */
-int ilqg_multi_receding_plant_windows(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
-                                      const char *const *names, const double *values, const double *disturbance, int n_windows,
-                                      const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
-                                      double *cost_applied, double *plan_cost, int *ok) {
+/* the two entries below: every shard's part through its own entry, ilqg_batch_receding_plant or (windowed) _plant_windows.  A
+ * future is offset by the shard's first trajectory where its name has rows in the shard; what the shard would refuse (a name
+ * that is no per-time-step parameter, too many names) passes as it is, and the shard refuses */
+static int multi_receding_plant(ilqg_multi_t *m, int windowed, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                                const char *const *names, const double *values, const double *disturbance, int n_windows,
+                                const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
+                                double *cost_applied, double *plan_cost, int *ok) {
     const size_t W = values ? rows_width(n_names, names) : 0;
     const size_t rn = rounds > 0 ? (size_t)rounds : 0, per = rn * (steps > 0 ? (size_t)steps : 0);
     const double *of_shard[WINDOW_MAX_PARAMS];
-    const int offset = window_names_ && future && n_windows > 0 && n_windows <= WINDOW_MAX_PARAMS;
+    const int offset = windowed && window_names_ && future && n_windows > 0 && n_windows <= WINDOW_MAX_PARAMS;
     int g, i, k;
-    if(!m) return 1;
     EACH_SHARD(g) {
         const size_t at = (size_t)m->first[g];
+        double *const xp = x_plant ? x_plant + at * N_X : NULL, *const xa = x_applied ? x_applied + at * per * N_X : NULL;
+        double *const ua = u_applied ? u_applied + at * per * N_U : NULL, *const ca = cost_applied ? cost_applied + at * rn : NULL;
+        double *const pc = plan_cost ? plan_cost + at * rn : NULL;
+        const double *const v = values ? values + at * W : NULL, *const w = disturbance ? disturbance + at * per * N_X : NULL;
+        int *const okg = ok ? ok + at : NULL;
         for(i = 0; offset && i < n_windows; i++) {
             k = window_names_[i] ? find_param(window_names_[i]) : -1;
             of_shard[i] = (future[i] && k >= 0 && k < WINDOW_MAX_PARAMS && m->shard[g]->ps_on[k]) ? future[i] + at * per : future[i];
         }
-        if(ilqg_batch_receding_plant_windows(m->shard[g], rounds, steps, iterations, feedback, x_plant ? x_plant + at * N_X : NULL, n_names, names,
-                                             values ? values + at * W : NULL, disturbance ? disturbance + at * per * N_X : NULL, n_windows,
-                                             window_names_, offset ? of_shard : future, x_applied ? x_applied + at * per * N_X : NULL,
-                                             u_applied ? u_applied + at * per * N_U : NULL, cost_applied ? cost_applied + at * rn : NULL,
-                                             plan_cost ? plan_cost + at * rn : NULL, ok ? ok + at : NULL))
+        if(windowed ? ilqg_batch_receding_plant_windows(m->shard[g], rounds, steps, iterations, feedback, xp, n_names, names, v, w, n_windows, window_names_,
+                                                        offset ? of_shard : future, xa, ua, ca, pc, okg)
+                    : ilqg_batch_receding_plant(m->shard[g], rounds, steps, iterations, feedback, xp, n_names, names, v, w, xa, ua, ca, pc, okg))
             return multi_fail(m, g);
     }
     return 0;
+}
+int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                              const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,
+                              double *cost_applied, double *plan_cost, int *ok) {
+    return multi_receding_plant(m, 0, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, 0, NULL, NULL, x_applied,
+                                u_applied, cost_applied, plan_cost, ok);
+}
+int ilqg_multi_receding_plant_windows(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
+                                      const char *const *names, const double *values, const double *disturbance, int n_windows,
+                                      const char *const *window_names_, const double *const *future, double *x_applied, double *u_applied,
+                                      double *cost_applied, double *plan_cost, int *ok) {
+    if(!m) return 1;
+    return multi_receding_plant(m, 1, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, n_windows, window_names_, future,
+                                x_applied, u_applied, cost_applied, plan_cost, ok);
 }
 int ilqg_multi_init(ilqg_multi_t *m) {
     int g;

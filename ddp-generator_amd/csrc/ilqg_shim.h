@@ -116,14 +116,14 @@ enum {
     ILQG_K_SEARCH2,  /*             k_search on the pending list (second stage) */
     ILQG_K_ADOPT,    /*             k_adopt_home / k_rejected_home, k_commit */
     ILQG_K_SHIFT,    /* receding horizon: k_shift_lane / k_shift_wave (ilqg_dev_shift) */
-    ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_log_append) */
+    ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_loop_apply) */
     ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head, ilqg_dev_head_device) */
     ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
     ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout with a table) */
-    ILQG_K_PLANT,    /* k_plant (ilqg_dev_plant_advance) */
+    ILQG_K_PLANT,    /* k_plant (ilqg_dev_loop_apply with plants) */
     ILQG_K_SHIFT_PARAM_ROWS, /* k_shift_param_rows (ilqg_dev_shift_param_batch) */
-    ILQG_K_SHIFT_WINDOWS, /* k_shift_windows (ilqg_dev_windows_move) */
+    ILQG_K_SHIFT_WINDOWS, /* k_shift_windows (ilqg_dev_loop_shift) */
     ILQG_K_HISTORY,  /* k_history (ilqg_dev_update of a context with a history) */
     ILQG_K_COUNT
 };
@@ -171,7 +171,7 @@ int ilqg_dev_set_params(ilqg_dev_t *d, int n_params, const int *sizes, const dou
  * on_device = 0: values is host memory, waits once; on_device != 0: device memory of the context's device, copied in the
  * order of the context's stream, no wait and (at an unchanged size) no allocation.  n_named = 0 clears the set: the kernels
  * are then those of a context that never had one; named and values are not read.  A call replaces the whole set.  Order with
- * the tables of ilqg_dev_policy_rollout and ilqg_dev_plant_begin: the trajectory's row first, then the roll-out's or plant's.
+ * the tables of ilqg_dev_policy_rollout and ilqg_dev_loop_begin: the trajectory's row first, then the roll-out's or plant's.
  * ilqg_dev_move carries the rows of the trajectories it moves; the destination takes the source's map.  Touches no
  * trajectory and launches no kernel.  get: the table as it is on the device, rows [batch][W] (host); waits. */
 int ilqg_dev_set_params_batch(ilqg_dev_t *d, int n_named, const int *named, const double *values, int on_device);
@@ -219,13 +219,6 @@ int ilqg_dev_rollout_init(ilqg_dev_t *d);     /* forward_pass(alpha = 0) + swap 
 int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0);
 /* the caller's tail behind a shift: host [batch][steps][N_U] into the last `steps` time steps of the controls */
 int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps);
-/* A log on the device of the steps a receding-horizon loop applies: begin sizes it for `rounds` rounds of `steps` steps,
- * append copies (x_k, u_k), k < steps, of every current plan and its cost into round `round`, read brings the whole log to
- * the host once: x [batch][rounds*steps][N_X], u [batch][rounds*steps][N_U], cost [batch][rounds] (any may be NULL);
- * synchronises. */
-int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps);
-int ilqg_dev_log_append(ilqg_dev_t *d, int round);
-int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost);
 /* The control interval of a caller with its own plant.  head: the first `steps` steps of every CURRENT plan, read where it
  * lives (nothing moves home), trajectory-major: x [batch][steps][N_X], u / l [batch][steps][N_U], L [batch][steps][N_U*N_X],
  * cost [batch]; any pointer may be NULL; 1 <= steps <= n_hor.  ilqg_dev_head fills host arrays (one wait at most),
@@ -248,7 +241,7 @@ int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double 
  * stream and waits for nothing; ilqg_dev_policy_rollout_host takes host memory, stages through the context's staging buffer
  * (which only grows) and waits once.  R >= 1; needs ilqg_dev_set_params before it.
  * dist = NULL: no process noise — the same kernels, launches and bits as before the argument existed.  Else behind every step
- * k = 0 .. n_hor-1 the roll-out's state is pushed, x_{k+1} <- x_next + w[b][r][k] (the rule of ilqg_dev_plant_advance):
+ * k = 0 .. n_hor-1 the roll-out's state is pushed, x_{k+1} <- x_next + w[b][r][k] (the rule of ilqg_dev_loop_apply):
  * dist [batch][R][n_hor][N_X], or with dist_shared != 0 [R][n_hor][N_X] for every trajectory; it lives where x0 lives (the
  * host form stages it behind the values).  ok = 0 also where a disturbed state is not finite, the one behind row n_hor-1 —
  * which moves x_end, x[n_hor] and the final cost — included.  No new kernel and no new timing slot. */
@@ -257,28 +250,51 @@ int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named,
 int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
                                  const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
                                  double *u);
-/* The plant of a closed loop that stays on the device (k_plant.inc): `rounds` times { ilqg_dev_iterate; ilqg_dev_plant_advance;
- * ilqg_dev_shift(d, steps, 0); ilqg_dev_plant_put_x0; ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_plant_begin
- * and one ilqg_dev_plant_read — the caller's loop; nothing in it waits or copies.
- * begin (HOST memory in, all of it sent once; waits once): the plants' states x_plant [batch][N_X], or NULL = every plan's
- * x_0; the plants' parameters — the context's fixed-size ones with the n_named parameters named[] replaced by row b of
- * values [batch][W], names and W as in ilqg_dev_policy_rollout with R = 1 and shared = 0; n_named = 0: the
- * context's own —; disturbance [batch][rounds*steps][N_X], added to the state behind each step, or NULL = none.  It also
- * sizes the logs (the rules of ilqg_dev_log_begin, whose log it takes) and clears the plants' failure flags.
- * rounds >= 1, 1 <= steps < n_hor.
- * advance: every plant that has not failed advances `steps` steps from its own state under the CURRENT plan's policy,
+/* The receding-horizon loop that stays on the device: `rounds` times { ilqg_dev_iterate; ilqg_dev_loop_apply; ilqg_dev_loop_shift;
+ * ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_loop_begin and one ilqg_dev_loop_read — the caller's loop;
+ * nothing in it waits or copies.  What the loop is, is stated once, here: */
+typedef struct {
+    int rounds, steps;          /* rounds >= 1, 1 <= steps < n_hor */
+    int plant;                  /* 0: the plans' own heads are recorded (k_log_steps); 1: plants advance (k_plant.inc) */
+    /* read only with `plant` (HOST memory): the plants' states [batch][N_X], or NULL = every plan's x_0; the plants' parameters —
+     * the context's fixed-size ones with the n_named parameters named[] replaced by row b of values [batch][W], names and W as
+     * in ilqg_dev_policy_rollout with R = 1 and shared = 0; n_named = 0: the context's own —; disturbance
+     * [batch][rounds*steps][N_X], added to the state behind each step, or NULL = none */
+    const double *x_plant;
+    int n_named;
+    const int *named;
+    const double *values, *disturbance;
+    int windows;                /* the windows of the per-time-step parameters move `steps` on each round (k_shift_windows) */
+    /* read only with `windows` (HOST memory): future[i], i an index into paramdesc[] (n_params entries; those of fixed-size
+     * parameters are not read), holds the values beyond parameter i's window for the whole loop: [batch][rounds * steps] where
+     * the parameter has rows in this context (ilqg_dev_set_param_steps_batch), [rounds * steps] where it is the shared window,
+     * NULL: the window holds its last value, per row.  future itself may be NULL (every window holds) */
+    const double *const *future;
+} ilqg_dev_loop_t;
+/* begin: the one place that checks the shape.  Sizes the logs — x [batch][rounds*steps][N_X], u [..][N_U], the plans' costs
+ * [batch][rounds] — and with `plant` the plants' buffers, anew for every loop, and the futures' buffers, which only grow; where
+ * one of them does not fit no loop is open and no log or plant is left.  With `plant` it clears the plants' failure flags and
+ * the logs (what a failed plant leaves unwritten reaches the host as zeros).  Everything the caller gave goes up once; waits
+ * for the stream first and once more behind what it sent.
+ * apply (round `round`): without plants (x_k, u_k), k < steps, of every current plan and its cost go to the logs.  With plants
+ * every plant that has not failed advances `steps` steps from its own state under the CURRENT plan's policy,
  * u = u_nom_k [+ L_k (xp - x_nom_k) if feedback], through the step of forward_pass under the plant's parameters and the
  * multipliers and penalty weights its slot has, then xp <- x_next + disturbance; the state each control was applied at, the
- * clamped control, the sum of the running costs and the plan's cost go to the logs of round `round`.  A plant fails — for
- * the rest of the loop, staying at its last finite state — when a step's guards fail or its state is not finite.  Writes
- * nothing of the solver's state.  put_x0: the plants' states become x_0 of the plans (ilqg_dev_put_x0_device).
+ * clamped control, the sum of the running costs and the plan's cost go to the logs.  A plant fails — for the rest of the loop,
+ * staying at its last finite state — when a step's guards fail or its state is not finite.  Writes nothing of the solver's
+ * state.  (k_plant runs on the stream of the roll-out family, between the two hand-overs with the context's stream.)
+ * shift (round `round`): with `windows` every size -1 parameter's window moves `steps` on, its tail columns
+ * [round * steps, (round + 1) * steps) of its future, in ONE launch on the context's stream (wave mapping: the constant record
+ * entries are marked stale as ilqg_dev_shift_param marks them; a library whose problem has no such parameter launches
+ * nothing); then ilqg_dev_shift(d, steps, use_plan_x0 = !plant); with plants their states then become x_0 of the plans
+ * (ilqg_dev_put_x0_device).  Apply and shift are two calls: the host moves its mirror of a shared window between them.
  * read (waits once): x_plant [batch][N_X] the plants' states now, x [batch][rounds*steps][N_X], u [..][N_U],
- * cost_applied / plan_cost [batch][rounds], ok [batch] (0 = failed); any may be NULL. */
-int ilqg_dev_plant_begin(ilqg_dev_t *d, int rounds, int steps, const double *x_plant, int n_named, const int *named, const double *values,
-                         const double *disturbance);
-int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback);
-int ilqg_dev_plant_put_x0(ilqg_dev_t *d);
-int ilqg_dev_plant_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok);
+ * cost_applied / plan_cost [batch][rounds], ok [batch] (0 = failed); any may be NULL; x_plant, cost_applied and ok need a
+ * loop with plants. */
+int ilqg_dev_loop_begin(ilqg_dev_t *d, const ilqg_dev_loop_t *loop);
+int ilqg_dev_loop_apply(ilqg_dev_t *d, int round, int feedback);
+int ilqg_dev_loop_shift(ilqg_dev_t *d, int round);
+int ilqg_dev_loop_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok);
 /* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) / ilqg_dev_write_u_tail with the source in DEVICE memory: no staging, no wait */
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0);
 int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps);
@@ -295,18 +311,6 @@ int ilqg_dev_check_device_ptr(ilqg_dev_t *d, const void *ptr, const char *what);
  * ilqg_dev_set_params marks them; no wave-mapped problem with such a parameter is built in this tree, so that path is
  * untested.) */
 int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail);
-/* The windows of a resident closed loop: `rounds` times { ...; ilqg_dev_windows_move(d, round); ilqg_dev_shift; ... } behind one
- * ilqg_dev_windows_begin.  begin: future[i], i an index into paramdesc[] (n_params entries; those of fixed-size parameters
- * are not read), is HOST memory holding the values beyond parameter i's window for the whole loop: [batch][rounds * steps]
- * where the parameter has rows in this context (ilqg_dev_set_param_steps_batch), [rounds * steps] where it is the shared
- * window, NULL: the window holds its last value, per row.  future itself may be NULL (every window holds).  The futures go up
- * once, into buffers of the context that only grow; waits once.  rounds >= 1, 1 <= steps < n_hor.
- * move: every size -1 parameter's window moves `steps` on, its tail columns [round * steps, (round + 1) * steps) of its
- * future, in ONE launch (k_shift_windows) on the context's stream; waits for nothing, copies nothing.  Wave mapping: the
- * constant record entries are marked stale as ilqg_dev_shift_param marks them.  A library whose problem has no per-time-step
- * parameter launches nothing in either. */
-int ilqg_dev_windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *const *future);
-int ilqg_dev_windows_move(ilqg_dev_t *d, int round);
 int ilqg_dev_derivs(ilqg_dev_t *d);           /* calc_derivs for trajectories that need it */
 /* back_pass.  mode 0: records from HBM + lambda retry loop + gradient test; 1: records from HBM, one
  * sweep (drop-in back_pass()); 2: as 0 with the derivatives evaluated on the fly (no k_derivs needed) */

@@ -125,8 +125,8 @@ struct DevBuffers {
     Buffer<double> xpl, upl;               // P.xpl, P.upl (ls_keep = 2)
     Buffer<unsigned> spec_ints;            // quad mapping with speculative retries: the protocol's words
     Buffer<double> spec_doubles;           //   ... the rows' results and gains
-    Buffer<double> log_x, log_u, log_c;    // receding horizon: the applied steps of every round (ilqg_dev_log_begin), host layout
-    // the plants of a closed loop (ilqg_dev_plant_begin): their states [B][NX], failure flags [B], the sums of the applied
+    Buffer<double> log_x, log_u, log_c;    // receding horizon: the applied steps of every round (ilqg_dev_loop_begin), host layout
+    // the plants of a closed loop (ilqg_dev_loop_begin): their states [B][NX], failure flags [B], the sums of the applied
     // running costs [B][rounds] (the applied steps and the plans' costs go to the log above), and what the caller sent:
     // the parameter rows [B][W] with their map, the disturbances [B][rounds * steps][NX]
     Buffer<double> plant_xp, plant_cost, plant_values, plant_dist;
@@ -137,8 +137,8 @@ struct DevBuffers {
     // [Bp][N + 1] (trajectory-major; rows B .. Bp - 1 are zero and belong to nobody); grow-only like pb_values
     static constexpr int SR = N_STEP_PARAMS > 0 ? N_STEP_PARAMS : 1;
     Buffer<double> sr_rows[SR];
-    // the futures of a resident loop's windows (ilqg_dev_windows_begin): per slot the values beyond the window, [B][win_per] for
-    // a parameter with rows, [win_per] for the shared window; grow-only
+    // the futures of a resident loop's windows (ilqg_dev_loop_begin): per slot the values beyond the window, [B][rounds * steps]
+    // for a parameter with rows, [rounds * steps] for the shared window; grow-only
     Buffer<double> win_future[SR];
     Buffer<double> hist_d;                 // the iteration history (ilqg_dev_set_history): History::d, History::i
     Buffer<int> hist_i;
@@ -189,16 +189,20 @@ struct ilqg_dev : DevBuffers {
     struct SharedWork *shared;  // wave mapping: the device's derivative work buffer (see SharedWork)
     int own_chunk;              // trajectories whose records fit the context's private buffer P.work (stage-by-stage calls)
     bool per_step_params;       // some problem parameter has one value per time step
-    int log_rounds, log_steps;  // the log's shape (log_x, log_u, log_c)
-    bool plant_named;           // the plants run under plant_values and this map
-    PolicyParamMap plant_map;
+    // The resident loop that is open (ilqg_dev_loop_begin; rounds = 0: none): the shape of its logs and futures, and what its
+    // per-round steps do
+    struct Loop {
+        int rounds, steps;
+        bool plant, windows;
+        bool named;             // the plants run under plant_values and this map
+        PolicyParamMap map;
+        bool given[SR];         // the slot has a future in win_future[s] (else its window holds)
+    } loop;
     // pb_on: the lane-mapped kernels that take ParamValues run as the instantiation whose pack is the table pb_values and its map
     // (with_rows)
     bool pb_on;
     PolicyParamMap pb_map;
     bool sr_on[SR];             // sr_rows[s] is in use
-    bool win_given[SR];         // the slot has a future in win_future[s] (else its window holds)
-    int win_rounds, win_steps;  // 0: no loop open
     // what with_rows hands the rows twins: rows_on = pb_on or some sr_on; rows_map = pb_map (empty without a table) with the
     // step rows in use (rows_refresh, after every change of either set)
     bool rows_on;
@@ -394,9 +398,9 @@ int drain_spans(ilqg_dev *d) {
 
 inline dim3 grid1(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 
-// the plants' buffers (ilqg_dev_plant_begin makes them anew for every loop; the caller has synchronised)
+// the plants' buffers (ilqg_dev_loop_begin makes them anew for every loop; the caller has synchronised)
 int plant_release(ilqg_dev *d) {
-    d->plant_named = false;
+    d->loop.named = false;
     return d->plant_xp.release() | d->plant_cost.release() | d->plant_values.release() | d->plant_dist.release() | d->plant_failed.release();
 }
 
@@ -1267,53 +1271,6 @@ int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps) {
     return io_done(d);
 }
 
-int ilqg_dev_log_begin(ilqg_dev_t *d, int rounds, int steps) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(rounds < 1 || steps < 1 || steps >= d->N) {
-        g_err = "ilqg_dev_log_begin: need rounds >= 1 and 1 <= steps < n_hor";
-        return 1;
-    }
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    d->log_rounds = d->log_steps = 0;
-    const size_t per = (size_t)d->B * rounds * steps;
-    if(d->log_x.renew(per * NX * sizeof(double)) || d->log_u.renew(per * NU * sizeof(double)) || d->log_c.renew((size_t)d->B * rounds * sizeof(double))) {
-        (void)(d->log_x.release() | d->log_u.release() | d->log_c.release());  // all or none: no log, as before the first begin
-        return 1;
-    }
-    d->log_rounds = rounds;
-    d->log_steps = steps;
-    return 0;
-}
-
-int ilqg_dev_log_append(ilqg_dev_t *d, int round) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(!d->log_x.get() || round < 0 || round >= d->log_rounds) {
-        g_err = "ilqg_dev_log_append: no such round in the log (ilqg_dev_log_begin)";
-        return 1;
-    }
-    {
-        Timed t(d, ILQG_K_LOG);
-        hipLaunchKernelGGL(k_log_steps, grid1((size_t)d->B * d->log_steps * (NX + NU), 256), dim3(256), 0, d->stream, d->P, d->log_x.get(),
-                           d->log_u.get(), d->log_c.get(), round, d->log_rounds, d->log_steps);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ilqg_dev_log_read(ilqg_dev_t *d, double *x, double *u, double *cost) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(!d->log_x.get()) {
-        g_err = "ilqg_dev_log_read: no log (ilqg_dev_log_begin)";
-        return 1;
-    }
-    const size_t per = (size_t)d->B * d->log_rounds * d->log_steps;
-    if(x) HIP_TRY(hipMemcpyAsync(x, d->log_x.get(), per * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(u) HIP_TRY(hipMemcpyAsync(u, d->log_u.get(), per * NU * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(cost) HIP_TRY(hipMemcpyAsync(cost, d->log_c.get(), (size_t)d->B * d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The control interval of a caller with its own plant (k_mpc_io.inc)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1513,99 +1470,6 @@ int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The plants of a closed loop (k_plant.inc).  k_plant runs where k_policy runs: on the stream of the roll-out family,
-// between the two hand-overs with the context's stream, so behind the iteration that made the plan and in front of the
-// k_shift_* that moves it.
-// ---------------------------------------------------------------------------------------------------------------------
-int ilqg_dev_plant_begin(ilqg_dev_t *d, int rounds, int steps, const double *x_plant, int n_named, const int *named, const double *values,
-                         const double *disturbance) {
-    HIP_TRY(hipSetDevice(d->device));
-    NEED_PARAMS(d);
-    if(rounds < 1 || steps < 1 || steps >= d->N) {
-        g_err = "ilqg_dev_plant_begin: need rounds >= 1 and 1 <= steps < n_hor";
-        return 1;
-    }
-    PolicyParamMap map;
-    if(n_named < 0 || (n_named > 0 && !policy_param_map(n_named, named, values, map))) {
-        if(n_named < 0) g_err = "ilqg_dev_plant_begin: n_names must not be negative";
-        return 1;
-    }
-    if(ilqg_dev_log_begin(d, rounds, steps)) return 1;  // (synchronises the context's stream)
-    if(d->roll) HIP_TRY(hipStreamSynchronize(d->roll));
-    if(plant_release(d)) return 1;
-    const size_t B = (size_t)d->B, per = B * (size_t)rounds * (size_t)steps;
-    if(d->plant_xp.renew(B * NX * sizeof(double)) || d->plant_failed.renew(B * sizeof(int)) || d->plant_cost.renew(B * (size_t)rounds * sizeof(double)) ||
-       (n_named > 0 && d->plant_values.renew(B * (size_t)map.W * sizeof(double))) || (disturbance && d->plant_dist.renew(per * NX * sizeof(double)))) {
-        (void)plant_release(d);  // all or none: no plants, as before the first begin
-        return 1;
-    }
-    HIP_TRY(hipMemsetAsync(d->plant_failed.get(), 0, B * sizeof(int), d->stream));
-    // (what a failed plant leaves unwritten reaches the host as zeros)
-    HIP_TRY(hipMemsetAsync(d->log_x.get(), 0, per * NX * sizeof(double), d->stream));
-    HIP_TRY(hipMemsetAsync(d->log_u.get(), 0, per * NU * sizeof(double), d->stream));
-    HIP_TRY(hipMemsetAsync(d->plant_cost.get(), 0, B * (size_t)rounds * sizeof(double), d->stream));
-    if(n_named > 0) {
-        d->plant_map = map;
-        d->plant_named = true;
-        HIP_TRY(hipMemcpyAsync(d->plant_values.get(), values, B * (size_t)map.W * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    }
-    if(disturbance) HIP_TRY(hipMemcpyAsync(d->plant_dist.get(), disturbance, per * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    if(x_plant) HIP_TRY(hipMemcpyAsync(d->plant_xp.get(), x_plant, B * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    else if(launch_head(d, 1, d->plant_xp.get(), nullptr, nullptr, nullptr, nullptr)) return 1;  // x_0 of every plan, where it lives
-    HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
-    return 0;
-}
-
-int ilqg_dev_plant_advance(ilqg_dev_t *d, int round, int feedback) {
-    HIP_TRY(hipSetDevice(d->device));
-    NEED_PARAMS(d);
-    if(!d->plant_xp.get() || !d->log_x.get() || round < 0 || round >= d->log_rounds) {
-        g_err = "ilqg_dev_plant_advance: no such round (ilqg_dev_plant_begin)";
-        return 1;
-    }
-    const int steps = d->log_steps, rounds = d->log_rounds;
-    if(roll_enter(d)) return 1;
-    {
-        Timed t(d, ILQG_K_PLANT, roll_stream(d));
-        // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
-        with_rows(d, [&](auto... tr) {
-            with_own_rows(d->plant_named, [&](auto... own) {
-                hipLaunchKernelGGL((k_plant<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0,
-                                   roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(),
-                                   (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(),
-                                   d->plant_cost.get(), d->log_c.get(), tr..., own...);
-            }, (const double *)d->plant_values.get(), d->plant_map);
-        });
-    }
-    HIP_TRY(hipGetLastError());
-    return roll_leave(d);
-}
-
-int ilqg_dev_plant_put_x0(ilqg_dev_t *d) {
-    if(!d->plant_xp.get()) {
-        g_err = "ilqg_dev_plant_put_x0: no plants (ilqg_dev_plant_begin)";
-        return 1;
-    }
-    return ilqg_dev_put_x0_device(d, d->plant_xp.get());
-}
-
-int ilqg_dev_plant_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(!d->plant_xp.get() || !d->log_x.get()) {
-        g_err = "ilqg_dev_plant_read: no plants (ilqg_dev_plant_begin)";
-        return 1;
-    }
-    const size_t B = (size_t)d->B;
-    if(x_plant) HIP_TRY(hipMemcpyAsync(x_plant, d->plant_xp.get(), B * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(cost_applied) HIP_TRY(hipMemcpyAsync(cost_applied, d->plant_cost.get(), B * (size_t)d->log_rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if(ok) HIP_TRY(hipMemcpyAsync(ok, d->plant_failed.get(), B * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    if(ilqg_dev_log_read(d, x, u, plan_cost)) return 1;  // (waits for the context's stream)
-    if(ok)
-        for(size_t b = 0; b < B; b++) ok[b] = ok[b] ? 0 : 1;  // the device keeps failure flags
-    return 0;
-}
-
 int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps) {
     HIP_TRY(hipSetDevice(d->device));
     if(steps < 1 || steps > d->N) {
@@ -1705,14 +1569,13 @@ int ilqg_dev_shift_param_batch(ilqg_dev_t *d, int index, int steps, const double
     return (tail && !on_device) ? io_done(d) : 0;
 }
 
-// The windows of a resident loop (ilqg_batch_receding_windows / _receding_plant_windows).  begin: the futures of the loop's
-// `rounds` rounds of `steps` steps go up ONCE, into buffers of the context that only grow; future[i], i an index into
-// paramdesc[], is host memory [B][rounds * steps] where parameter i has rows in this context, [rounds * steps] where it is the
-// shared window, or NULL: that window holds its last value, per row (entries of fixed-size parameters are not read).  Waits
-// once.  move: EVERY size -1 parameter's window moves `steps` on in one launch of k_shift_windows, its tail the columns of
-// round `round` of its future — on the context's stream: behind the log or the plant step of the round (both hand back to
-// it) and in front of ilqg_dev_shift and the initial roll-out that reads the moved windows.  A library without a per-time-step
-// parameter has nothing to move: both return 0 and launch nothing.
+// ---------------------------------------------------------------------------------------------------------------------
+// The resident receding-horizon loop (ilqg_shim.h ilqg_dev_loop_t): what it is lives in d->loop, written by begin alone; the
+// per-round steps and read ask it.  k_plant runs where k_policy runs: on the stream of the roll-out family, between the two
+// hand-overs with the context's stream, so behind the iteration that made the plan and in front of the k_shift_* that moves
+// it.  k_shift_windows runs on the context's stream: behind the log or the plant step of the round (both hand back to it) and
+// in front of ilqg_dev_shift and the initial roll-out that reads the moved windows.
+// ---------------------------------------------------------------------------------------------------------------------
 static int slot_index(int s) {  // the paramdesc[] index of the s-th size -1 parameter
     constexpr int sizes[ILQG_NP > 0 ? ILQG_NP : 1] = ILQG_PSIZES;
     for(int i = 0; i < ILQG_NP; i++)
@@ -1721,22 +1584,15 @@ static int slot_index(int s) {  // the paramdesc[] index of the s-th size -1 par
 }
 }  // extern "C"
 // (templates on the slot count: the discarded branch, and with it the kernel, is not instantiated where there is no slot)
-template <int n_slots>
-static int windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *const *future) {
+// each(s, f, bytes) for every slot s the caller gave a future f of the open loop's shape
+template <int n_slots, class Each>
+static int each_future(ilqg_dev_t *d, const double *const *future, Each &&each) {
     if constexpr(n_slots > 0) {
-        NEED_PARAMS(d);
-        const size_t per = (size_t)rounds * (size_t)steps;
-        bool sent = false;
+        const size_t per = (size_t)d->loop.rounds * (size_t)d->loop.steps;
         for(int s = 0; s < n_slots; s++) {
             const double *f = future ? future[slot_index(s)] : nullptr;
-            d->win_given[s] = f != nullptr;
-            if(!f) continue;
-            const size_t bytes = (d->sr_on[s] ? (size_t)d->B : (size_t)1) * per * sizeof(double);
-            if(d->win_future[s].reserve(bytes, d->stream)) return 1;
-            HIP_TRY(hipMemcpyAsync(d->win_future[s].get(), f, bytes, hipMemcpyHostToDevice, d->stream));
-            sent = true;
+            if(f && each(s, f, (d->sr_on[s] ? (size_t)d->B : (size_t)1) * per * sizeof(double))) return 1;
         }
-        if(sent) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
     }
     return 0;
 }
@@ -1750,40 +1606,146 @@ static int windows_move(ilqg_dev_t *d, int round) {
             const bool rows = d->sr_on[s];
             S.w[s].base = rows ? d->sr_rows[s].get() : d->param_bufs[slot_index(s)].get();
             S.w[s].rows = rows ? d->B : 1;
-            S.w[s].future = d->win_given[s] ? d->win_future[s].get() : nullptr;
-            S.w[s].stride = rows ? (size_t)d->win_rounds * (size_t)d->win_steps : 0;
+            S.w[s].future = d->loop.given[s] ? d->win_future[s].get() : nullptr;
+            S.w[s].stride = rows ? (size_t)d->loop.rounds * (size_t)d->loop.steps : 0;
             if(S.w[s].rows > most) most = S.w[s].rows;
         }
         {
             Timed t(d, ILQG_K_SHIFT_WINDOWS);
-            hipLaunchKernelGGL(k_shift_windows<n_slots>, dim3(most, n_slots), dim3(PARAM_BLOCK), 0, d->stream, S, d->N + 1, d->win_steps,
-                               round * d->win_steps);
+            hipLaunchKernelGGL(k_shift_windows<n_slots>, dim3(most, n_slots), dim3(PARAM_BLOCK), 0, d->stream, S, d->N + 1, d->loop.steps,
+                               round * d->loop.steps);
         }
         HIP_TRY(hipGetLastError());
         d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
     }
     return 0;
 }
+// no loop, no log and no plant: as before the first begin
+static int loop_close(ilqg_dev_t *d) {
+    d->loop.rounds = 0;
+    return d->log_x.release() | d->log_u.release() | d->log_c.release() | plant_release(d);
+}
+static int loop_round_ok(const ilqg_dev_t *d, int round, const char *who) {
+    if(round >= 0 && round < d->loop.rounds) return 1;
+    g_err = std::string(who) + ": no such round of an open loop (ilqg_dev_loop_begin)";
+    return 0;
+}
 extern "C" {
-int ilqg_dev_windows_begin(ilqg_dev_t *d, int rounds, int steps, const double *const *future) {
+int ilqg_dev_loop_begin(ilqg_dev_t *d, const ilqg_dev_loop_t *loop) {
     HIP_TRY(hipSetDevice(d->device));
-    if(rounds < 1 || steps < 1 || steps >= d->N) {
-        g_err = "ilqg_dev_windows_begin: need rounds >= 1 and 1 <= steps < n_hor";
+    const ilqg_dev_loop_t &L = *loop;
+    const bool windows = L.windows && N_STEP_PARAMS > 0, named = L.plant && L.n_named > 0;
+    if(L.rounds < 1 || L.steps < 1 || L.steps >= d->N) {
+        g_err = "ilqg_dev_loop_begin: need rounds >= 1 and 1 <= steps < n_hor";
         return 1;
     }
-    if(windows_begin<N_STEP_PARAMS>(d, rounds, steps, future)) return 1;
-    d->win_rounds = rounds;
-    d->win_steps = steps;
+    if(L.plant || windows) NEED_PARAMS(d);
+    PolicyParamMap map;
+    if(L.plant && L.n_named < 0) {
+        g_err = "ilqg_dev_loop_begin: n_names must not be negative";
+        return 1;
+    }
+    if(named && !policy_param_map(L.n_named, L.named, L.values, map)) return 1;
+    // nothing in flight reads what is made anew or grows below
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if(L.plant && d->roll) HIP_TRY(hipStreamSynchronize(d->roll));
+    d->loop.rounds = L.rounds, d->loop.steps = L.steps, d->loop.plant = L.plant != 0, d->loop.windows = L.windows != 0;
+    for(bool &given : d->loop.given) given = false;
+    const size_t B = (size_t)d->B, rounds = (size_t)L.rounds, per = B * rounds * (size_t)L.steps;
+    // the logs and the plants anew, the futures grow-only; all or none
+    if(d->log_x.renew(per * NX * sizeof(double)) || d->log_u.renew(per * NU * sizeof(double)) || d->log_c.renew(B * rounds * sizeof(double)) ||
+       (L.plant && (plant_release(d) || d->plant_xp.renew(B * NX * sizeof(double)) || d->plant_failed.renew(B * sizeof(int)) ||
+                    d->plant_cost.renew(B * rounds * sizeof(double)) || (named && d->plant_values.renew(B * (size_t)map.W * sizeof(double))) ||
+                    (L.disturbance && d->plant_dist.renew(per * NX * sizeof(double))))) ||
+       (windows && each_future<N_STEP_PARAMS>(d, L.future, [&](int s, const double *, size_t bytes) {
+            d->loop.given[s] = true;
+            return d->win_future[s].reserve(bytes);
+        }))) {
+        (void)loop_close(d);
+        return 1;
+    }
+    bool sent = L.plant != 0;
+    if(L.plant) {
+        HIP_TRY(hipMemsetAsync(d->plant_failed.get(), 0, B * sizeof(int), d->stream));
+        // (what a failed plant leaves unwritten reaches the host as zeros)
+        HIP_TRY(hipMemsetAsync(d->log_x.get(), 0, per * NX * sizeof(double), d->stream));
+        HIP_TRY(hipMemsetAsync(d->log_u.get(), 0, per * NU * sizeof(double), d->stream));
+        HIP_TRY(hipMemsetAsync(d->plant_cost.get(), 0, B * rounds * sizeof(double), d->stream));
+        if(named) {
+            d->loop.map = map;
+            d->loop.named = true;
+            HIP_TRY(hipMemcpyAsync(d->plant_values.get(), L.values, B * (size_t)map.W * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        }
+        if(L.disturbance) HIP_TRY(hipMemcpyAsync(d->plant_dist.get(), L.disturbance, per * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        if(L.x_plant) HIP_TRY(hipMemcpyAsync(d->plant_xp.get(), L.x_plant, B * NX * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        else if(launch_head(d, 1, d->plant_xp.get(), nullptr, nullptr, nullptr, nullptr)) return 1;  // x_0 of every plan, where it lives
+    }
+    if(windows && each_future<N_STEP_PARAMS>(d, L.future, [&](int s, const double *f, size_t bytes) {
+           HIP_TRY(hipMemcpyAsync(d->win_future[s].get(), f, bytes, hipMemcpyHostToDevice, d->stream));
+           sent = true;
+           return 0;
+       }))
+        return 1;
+    if(sent) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait: the caller's arrays are its own again
     return 0;
 }
 
-int ilqg_dev_windows_move(ilqg_dev_t *d, int round) {
+int ilqg_dev_loop_apply(ilqg_dev_t *d, int round, int feedback) {
     HIP_TRY(hipSetDevice(d->device));
-    if(round < 0 || round >= d->win_rounds) {
-        g_err = "ilqg_dev_windows_move: no such round (ilqg_dev_windows_begin)";
+    if(!loop_round_ok(d, round, "ilqg_dev_loop_apply")) return 1;
+    const int steps = d->loop.steps, rounds = d->loop.rounds;
+    if(!d->loop.plant) {
+        {
+            Timed t(d, ILQG_K_LOG);
+            hipLaunchKernelGGL(k_log_steps, grid1((size_t)d->B * steps * (NX + NU), 256), dim3(256), 0, d->stream, d->P, d->log_x.get(), d->log_u.get(),
+                               d->log_c.get(), round, rounds, steps);
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    NEED_PARAMS(d);
+    if(roll_enter(d)) return 1;
+    {
+        Timed t(d, ILQG_K_PLANT, roll_stream(d));
+        // (with a per-trajectory table the trajectory's row — the model's — goes first, the plant's behind it)
+        with_rows(d, [&](auto... tr) {
+            with_own_rows(d->loop.named, [&](auto... own) {
+                hipLaunchKernelGGL((k_plant<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid1((size_t)d->B, ROLL_BLOCK), dim3(ROLL_BLOCK), 0,
+                                   roll_stream(d), d->P, d->O, d->pv, steps, feedback ? 1 : 0, d->plant_xp.get(), d->plant_failed.get(),
+                                   (const double *)d->plant_dist.get(), round * steps, rounds * steps, round, rounds, d->log_x.get(), d->log_u.get(),
+                                   d->plant_cost.get(), d->log_c.get(), tr..., own...);
+            }, (const double *)d->plant_values.get(), d->loop.map);
+        });
+    }
+    HIP_TRY(hipGetLastError());
+    return roll_leave(d);
+}
+
+int ilqg_dev_loop_shift(ilqg_dev_t *d, int round) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!loop_round_ok(d, round, "ilqg_dev_loop_shift")) return 1;
+    if(d->loop.windows && windows_move<N_STEP_PARAMS>(d, round)) return 1;
+    if(ilqg_dev_shift(d, d->loop.steps, !d->loop.plant)) return 1;
+    return d->loop.plant ? ilqg_dev_put_x0_device(d, d->plant_xp.get()) : 0;
+}
+
+int ilqg_dev_loop_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(d->loop.rounds < 1 || ((x_plant || cost_applied || ok) && !d->loop.plant)) {
+        g_err = "ilqg_dev_loop_read: no loop, or none with plants (ilqg_dev_loop_begin)";
         return 1;
     }
-    return windows_move<N_STEP_PARAMS>(d, round);
+    const size_t B = (size_t)d->B, rounds = (size_t)d->loop.rounds, per = B * rounds * (size_t)d->loop.steps;
+    if(x_plant) HIP_TRY(hipMemcpyAsync(x_plant, d->plant_xp.get(), B * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(cost_applied) HIP_TRY(hipMemcpyAsync(cost_applied, d->plant_cost.get(), B * rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(ok) HIP_TRY(hipMemcpyAsync(ok, d->plant_failed.get(), B * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    if(x) HIP_TRY(hipMemcpyAsync(x, d->log_x.get(), per * NX * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(u) HIP_TRY(hipMemcpyAsync(u, d->log_u.get(), per * NU * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if(plan_cost) HIP_TRY(hipMemcpyAsync(plan_cost, d->log_c.get(), B * rounds * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if(ok)
+        for(size_t b = 0; b < B; b++) ok[b] = ok[b] ? 0 : 1;  // the device keeps failure flags
+    return 0;
 }
 
 #if ILQG_WAVE_MAP

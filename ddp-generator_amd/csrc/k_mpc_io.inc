@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param_rows(double *__rest
 }
 
 // ALL windows of a context move with the horizon in ONE launch, fed from futures that already lie on the device
-// (ilqg_dev_windows_move: the resident loops ilqg_batch_receding_windows / _receding_plant_windows).  Per size -1 parameter of
+// (ilqg_dev_loop_shift: the resident loops ilqg_batch_receding_windows / _receding_plant_windows).  Per size -1 parameter of
 // the problem — its slot, grid.y — a descriptor by value: the window's base, its row count (B for a parameter with rows per
 // trajectory, 1 for the shared window), the base of its future or null (hold the last value, per row) and the future's row
 // stride (rounds * steps, or 0 for a shared future).  grid.x is the row; the workgroups beyond a slot's row count return at

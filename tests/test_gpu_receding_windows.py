@@ -319,22 +319,63 @@ def test_groups_shards_and_the_reversed_batch_give_the_same_bits(ilqg):
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("form", ["rows", "shared"])
 def test_one_launch_per_round_and_group_moves_every_window(ilqg, form):
-    """the launches by kernel over one call: k_shift_windows rounds x groups, and not one k_shift_param / k_shift_param_rows —
-    the loop does not go through the entries that stage a tail from the host"""
-    groups = 2
-    c = WindowCase(ilqg, "almix", 1, groups=groups, batch=200, count=2)
-    a, b = c.start(form, b=0)
-    given, _ = futures_of(c, form, b=0)
-    X = plant_starts(c.x0)
-    for s, call in ((a, lambda: a.receding(ROUNDS, STEPS, 1, windows={c.step: given})),
-                    (b, lambda: b.receding_plant(ROUNDS, STEPS, 1, True, X, windows={c.step: given}))):
-        s.timing(True)
+    """the launches by kernel over one call of each of the four forms of the resident loop, g the solver's stream groups: the
+    round's record is k_log_steps (receding) or k_plant (receding_plant), never both, rounds x g of it; k_shift rounds x g;
+    k_shift_windows rounds x g in the windowed forms and none in the others; and not one k_shift_param / k_shift_param_rows —
+    the loop does not go through the entries that stage a tail from the host.
+    Shapes: receding / receding_plant on CarParking FULL_DDP 0, n_hor = 6; the windowed forms on almix FULL_DDP 1, n_hor = 8,
+    `vref` with rows per trajectory or shared (`form`); rounds = 3, steps = 1 and 5, one iteration a round; groups = 1 and 2
+    asked for at B = 9 — where a stream group is whole tiles of 64 trajectories, so both are ONE group and g = 1 (the 5 + 4
+    split of nine trajectories is MultiSolver's, over shards, and a shard is a batch of its own) — and at B = 73 = 64 + 9, the
+    smallest batch at which two groups exist."""
+    from oracle.harness import CAR_PARAMS, almix_case
+    from conftest import load_package
+    rounds, n_car, n_mix = 3, 6, 8
+    names = ("k_log_steps", "k_plant", "k_shift", "k_shift_windows", "k_shift_param", "k_shift_param_rows")
+
+    def counted(s, call):
         before = launches(s)
         call()
         after = launches(s)
-        assert after["k_shift_windows"] - before["k_shift_windows"] == ROUNDS * groups
-        assert after["k_shift_param"] == before["k_shift_param"] and after["k_shift_param_rows"] == before["k_shift_param_rows"]
-    c.close()
+        return {k: after[k] - before[k] for k in names}
+
+    for batch, groups in ((9, 1), (9, 2), (73, 1), (73, 2)):
+        x0, u0 = load_package().synth.car_batch(batch, n_car, first=40)
+        params, opts, y0, v0 = almix_case(batch=batch)
+        v0 = np.ascontiguousarray(v0[:, :n_mix])
+        vref = 0.8 + 0.4 * np.sin(0.2 * np.arange(n_mix + 1 + rounds * 5))
+        tracks = np.ascontiguousarray(vref[None, :] * (1.0 + 0.05 * np.random.default_rng(59).standard_normal((batch, vref.size))))
+        car = ilqg.BatchSolver("carparking", 0, batch=batch, n_hor=n_car, params=CAR_PARAMS, opts=dict(max_iter=40), groups=groups)
+        mix = ilqg.BatchSolver("almix", 1, batch=batch, n_hor=n_mix, params=dict(params, vref=vref[:n_mix + 1]), opts=dict(opts, max_iter=40), groups=groups)
+        assert car.groups() == mix.groups() == (groups if batch > 64 else 1)
+        g = car.groups()
+        car.timing(True), mix.timing(True)
+        for steps in (1, 5):
+            more = slice(n_mix + 1, n_mix + 1 + rounds * steps)
+            given = np.ascontiguousarray(tracks[:, more] if form == "rows" else vref[more])
+
+            def start_mix():
+                if form == "rows":
+                    mix.set_param_steps_batch("vref", tracks[:, :n_mix + 1])
+                else:
+                    mix.set_param("vref", vref[:n_mix + 1])
+                mix.init(y0, v0)
+
+            got = {}
+            car.init(x0, u0)
+            got["receding"] = counted(car, lambda: car.receding(rounds, steps, 1))
+            car.init(x0, u0)
+            got["receding_plant"] = counted(car, lambda: car.receding_plant(rounds, steps, 1, True))
+            start_mix()
+            got["receding, windows"] = counted(mix, lambda: mix.receding(rounds, steps, 1, windows=dict(vref=given)))
+            start_mix()
+            got["receding_plant, windows"] = counted(mix, lambda: mix.receding_plant(rounds, steps, 1, True, windows=dict(vref=given)))
+            for what, n in got.items():
+                plant, windowed = "plant" in what, "windows" in what
+                want = dict(k_log_steps=0 if plant else rounds * g, k_plant=rounds * g if plant else 0, k_shift=rounds * g,
+                            k_shift_windows=rounds * g if windowed else 0, k_shift_param=0, k_shift_param_rows=0)
+                assert n == want, "%s, B = %d, %d group(s), steps = %d: launches %r, expected %r" % (what, batch, g, steps, n, want)
+        car.close(), mix.close()
 
 
 # ---------------------------------------------------------------------------

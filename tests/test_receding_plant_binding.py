@@ -137,14 +137,18 @@ def test_methods_of_an_old_library_say_rebuild(ilqg):
 def test_the_multi_entry_offsets_every_array_by_the_shards_first_trajectory():
     """read off the C source: the host code cannot run without a GPU, and the shards' offsets are one expression each"""
     text = open(os.path.join(ROOT, "ddp-generator_amd", "csrc", "ilqg_host.c")).read()
-    body = text[text.index("int ilqg_multi_receding_plant("):]
-    body = " ".join(body[:body.index("\nint ilqg_multi_init(")].split())
+    body = text[text.index("static int multi_receding_plant("):]  # the one worker of both multi entries
+    body = " ".join(body[body.index("{"):body.index("\n}\n")].split())
+    entry = text[text.index("\nint ilqg_multi_receding_plant("):]
+    entry = " ".join(entry[entry.index("{") + 1:entry.index("\n}\n")].split())
     assert "at = (size_t)m->first[g]" in body and "per = rn * (steps > 0 ? (size_t)steps : 0)" in body
     for piece in ("x_plant ? x_plant + at * N_X : NULL", "values ? values + at * W : NULL", "disturbance ? disturbance + at * per * N_X : NULL",
                   "x_applied ? x_applied + at * per * N_X : NULL", "u_applied ? u_applied + at * per * N_U : NULL",
                   "cost_applied ? cost_applied + at * rn : NULL", "plan_cost ? plan_cost + at * rn : NULL", "ok ? ok + at : NULL"):
-        assert piece in body, piece
-    assert "ilqg_batch_receding_plant(m->shard[g], rounds, steps, iterations, feedback," in body
+        assert body.count(piece) == 1, piece
+    # the entry reaches the shard's ilqg_batch_receding_plant through the worker: its not-windowed branch, fed the offset pointers
+    assert entry.startswith("return multi_receding_plant(m, 0, rounds, steps, iterations, feedback, x_plant, n_names, names, values, disturbance, 0, NULL, NULL,")
+    assert ": ilqg_batch_receding_plant(m->shard[g], rounds, steps, iterations, feedback, xp, n_names, names, v, w, xa, ua, ca, pc, okg)" in body
 
 
 def test_public_header_declares_the_entries_and_states_the_semantics():
