@@ -148,6 +148,29 @@ struct DevBuffers {
     Buffer<char, PinnedMem> pinned;
 };
 
+// What a launch of a wave-mapped derivative or sweep kernel is, stated ONCE per instantiation (wave_kernels_fill): dev_fill
+// walks the descriptions for the scratch question and the LDS limit, wave_backward launches what derivs_kernel / sweep_kernel
+// pick.  A launch over n items (trajectories; records for the derivatives) takes ceil(n / per_wg) workgroups, at most
+// cap * CUs of them.
+template <class Fn>
+struct WaveKernel {
+    Fn fn;
+    int block;
+    size_t lds;        // dynamic LDS of a launch
+    int per_wg;        // items a workgroup takes
+    int cap;           // most workgroups per CU in the grid (0: no cap; 1: the kernel's LDS leaves a CU one workgroup at a time)
+    size_t lds_limit;  // hipFuncAttributeMaxDynamicSharedMemorySize where the kernel needs more than the default 64 KB (0: not set)
+    bool scratch;      // the runtime gives it scratch memory (uses_scratch on the context's device): it runs on the shared roll-out stream
+    dim3 grid(size_t n, int cus) const {
+        const size_t wgs = (n + per_wg - 1) / per_wg, most = (size_t)cap * cus;
+        return dim3((unsigned)(cap && most < wgs ? most : wgs));
+    }
+};
+struct WaveKernels {
+    WaveKernel<void (*)(DevPtrs, ilqg_dev_opts_t, ParamValues, int, int, int, int, int)> derivs[2];  // records: [factored, general]
+    WaveKernel<void (*)(DevPtrs, ilqg_dev_opts_t, int, int, int)> sweep[6];  // quad, quad with speculative retries, row: [factored, general] each
+};
+
 }  // namespace
 
 struct ilqg_dev : DevBuffers {
@@ -165,17 +188,14 @@ struct ilqg_dev : DevBuffers {
     struct PendingRead { void *dst; const void *src; size_t bytes; int transpose_w; };
     std::vector<PendingRead> pending;
     bool keep_first;      // the roll-out launch in progress keeps the first stage's roll-outs in P.cand1
-    size_t roll_lds;              // wave mapping: dynamic LDS asked for by the second-stage roll-outs (one workgroup per CU)
-    size_t roll_pad;              //   ... on top of the records' buffer when the records go through LDS
+    size_t roll_pad;              // wave mapping: LDS on top of the records' buffer when the roll-outs' records go through LDS
     bool roll_dma;                // wave mapping: k_rollout_parts fetches the nominal records through LDS
     int loc_set;          // the set of planes current trajectories may live in (-1: none, all in X / U)
     bool defer_commit, commit_pending, pending_zero;  // ls_keep = 2: k_update commits / clears the pending counter
     int commit_s1, commit_set;
     bool winner_done;     // the last search ended with the accepted trajectories in place (two-stage search)
     int cus;              // compute units of the device
-    int chunk;            // wave mapping: trajectories whose derivative records fit the work buffer
     bool work_consts;     // wave mapping: constant entries of the records written (init_running)
-    bool work_factored;   // wave mapping: the records in the work buffer are factored ones (see FACTORED)
     bool half_consts[2];  // wave mapping: the same per half of the work buffer (chunks alternate between the halves)
     hipStream_t stream2;  // wave mapping: second stream of the chunk pipeline, fork / join events
     hipEvent_t fork, join;
@@ -187,7 +207,6 @@ struct ilqg_dev : DevBuffers {
     hipStream_t roll;
     hipEvent_t roll_in, roll_out;
     struct SharedWork *shared;  // wave mapping: the device's derivative work buffer (see SharedWork)
-    int own_chunk;              // trajectories whose records fit the context's private buffer P.work (stage-by-stage calls)
     bool per_step_params;       // some problem parameter has one value per time step
     // The resident loop that is open (ilqg_dev_loop_begin; rounds = 0: none): the shape of its logs and futures, and what its
     // per-round steps do
@@ -212,10 +231,9 @@ struct ilqg_dev : DevBuffers {
     hipEvent_t ext_in, ext_out;  // ordering with a stream of the caller (ilqg_dev_stream_in / _out), made with the context
     // Switches of the environment (comparison runs, tests), read ONCE when the context is made: a change of the environment
     // between two calls of a solve does not switch mappings or piece layouts under it.
-    struct EnvSwitches { bool no_quad, quad_stored, two_pieces, deriv_parts, no_dma, no_rollout_parts, quad_spec; } env;
-    // kernels of the wave mapping that ask the runtime for scratch memory (hipFuncGetAttributes on THIS context's device;
-    // they run on the device's one shared roll-out stream, see `roll`)
-    struct ScratchUse { bool derivs_f, derivs_g, quad_f, quad_g, quad_sf, quad_sg, wave_f, wave_g; } scratch;
+    // (read_env; roll_lds: wave mapping, the dynamic LDS asked for by the second-stage roll-outs — one workgroup per CU)
+    struct EnvSwitches { bool no_quad, quad_stored, two_pieces, deriv_parts, no_dma, no_rollout_parts, quad_spec, second_stream; size_t roll_lds; } env;
+    WaveKernels wave_kernels;  // wave mapping: the derivative and sweep kernels as THIS context's device runs them
     bool timing;
     struct Span { int kernel; hipEvent_t a, b; };
     std::vector<Span> spans;
@@ -480,6 +498,53 @@ static void with_own_rows(bool on, Launch &&launch, Own... own) {
 #define LAUNCH_TWIN(d, K, grid, block, lds, stream, ...) hipLaunchKernelGGL(K, grid, block, lds, stream, __VA_ARGS__)
 #endif
 
+// The ONE place that reads the environment's switches (dev_fill, first thing): presence switches, but for two
+static ilqg_dev::EnvSwitches read_env() {
+    const auto set = [](const char *name) { return getenv(name) != nullptr; };
+    const auto number = [](const char *name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+    ilqg_dev::EnvSwitches e;
+    e.no_quad = set("ILQG_NO_QUAD");
+    // stored tensors in the quad mapping (ilqg_quad.hpp): measured behind the row mapping at config 5 (1.66-1.71 against 1.82
+    // iterations/s, profiles/r6_stored_path.txt — both kernels share the HBM with k_derivs_wave of the other half of the
+    // buffer, and four trajectories' loads per wavefront gain nothing there); kept, tested, off unless ILQG_QUAD_STORED=1
+    e.quad_stored = number("ILQG_QUAD_STORED", 0) != 0;
+    e.two_pieces = set("ILQG_TWO_PIECES");
+    e.deriv_parts = set("ILQG_DERIV_PARTS");
+    e.no_dma = set("ILQG_NO_DMA");
+    e.no_rollout_parts = set("ILQG_NO_ROLLOUT_PARTS");
+    e.quad_spec = number("ILQG_QUAD_SPEC", 1) != 0;  // on unless ILQG_QUAD_SPEC=0
+    e.second_stream = set("ILQG_SECOND_STREAM");
+    // measured (config 5, ~300 busy workgroups in the second stage): 32.9 / 40.3 ms without, 33.0 / 28.5 ms with;
+    // with fewer than 256 busy workgroups every one of them gets a CU to itself (ILQG_ROLL_LDS_KB=0: off)
+    e.roll_lds = (size_t)number("ILQG_ROLL_LDS_KB", 84) * 1024;
+    return e;
+}
+
+#if ILQG_WAVE_MAP
+// The descriptions, in the order the code object lays the kernels out (the order of first reference in this file: another one
+// moves pc-relative call offsets in the kernels' code).  FACTORED = false builds name the general kernel twice; nothing
+// selects the first of a pair there (`fact` needs FACTORED).
+static void wave_kernels_fill(WaveKernels &k) {
+    constexpr size_t D = sizeof(double);
+    constexpr size_t quad_rows = QUAD_WAVES * 4 * QRow::SIZE * D, quad_limit = QUAD_STEP ? TABLE_DOUBLES * D + quad_rows : 0;
+    constexpr size_t fact_lds = (TABLE_DOUBLES + ILQG_FACT_WAVES * WAVE_LDS_DOUBLES) * D;
+    k.derivs[0] = {k_derivs_wave<FACTORED>, ILQG_DERIVS_BLOCK, 0, ILQG_DERIVS_BLOCK, 0, 0};
+    k.derivs[1] = {k_derivs_wave<false>, ILQG_DERIVS_BLOCK, DERIVS_DYN_LDS, ILQG_DERIVS_BLOCK, 0, 0};
+    // quad mapping: four trajectories to a wavefront, one workgroup per CU at a time
+    k.sweep[0] = {k_backward_quad<FACTORED>, 64 * QUAD_WAVES, TABLE_DOUBLES * D + quad_rows, 4 * QUAD_WAVES, 1, quad_limit};
+    k.sweep[1] = {k_backward_quad<false>, 64 * QUAD_WAVES, quad_rows, 4 * QUAD_WAVES, 1, quad_limit};
+    k.sweep[2] = {k_backward_quad<FACTORED, true>, 64 * QUAD_WAVES, TABLE_DOUBLES * D + quad_rows, 4 * QUAD_WAVES, 1, quad_limit};
+    k.sweep[3] = {k_backward_quad<false, true>, 64 * QUAD_WAVES, quad_rows, 4 * QUAD_WAVES, 1, quad_limit};
+    // row mapping: a wavefront per trajectory; the factored kernel's workgroups share the coefficient tables (one per CU at a time)
+    k.sweep[4] = {k_backward_wave<FACTORED>, 64 * ILQG_FACT_WAVES, fact_lds, ILQG_FACT_WAVES, 1, FACTORED ? fact_lds : 0};
+    k.sweep[5] = {k_backward_wave<false>, 64, WAVE_LDS_DOUBLES * D, 1, 8, 0};
+}
+static const auto &derivs_kernel(const ilqg_dev_t *d, bool fact) { return d->wave_kernels.derivs[fact ? 0 : 1]; }
+static const auto &sweep_kernel(const ilqg_dev_t *d, bool fact, bool quad, bool spec) {
+    return d->wave_kernels.sweep[(quad ? (spec ? 2 : 0) : 4) + (fact ? 0 : 1)];
+}
+#endif
+
 extern "C" {
 
 const char *ilqg_dev_error(void) { return g_err.c_str(); }
@@ -542,6 +607,7 @@ int ilqg_dev_create(ilqg_dev_t **out, int device, int batch, int n_hor) {
 }
 
 static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
+    d->env = read_env();
     d->device = device;
     d->B = batch;
     d->Bp = (batch + WAVE - 1) / WAVE * WAVE;
@@ -553,65 +619,33 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
     HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d->ext_in, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d->ext_out, hipEventDisableTiming));
-    d->env.no_quad = getenv("ILQG_NO_QUAD") != nullptr;
-    // stored tensors in the quad mapping (ilqg_quad.hpp): measured behind the row mapping at config 5 (1.66-1.71 against 1.82
-    // iterations/s, profiles/r6_stored_path.txt — both kernels share the HBM with k_derivs_wave of the other half of the
-    // buffer, and four trajectories' loads per wavefront gain nothing there); kept, tested, off unless ILQG_QUAD_STORED=1
-    d->env.quad_stored = getenv("ILQG_QUAD_STORED") != nullptr && atoi(getenv("ILQG_QUAD_STORED")) != 0;
-    d->env.two_pieces = getenv("ILQG_TWO_PIECES") != nullptr;
-    d->env.deriv_parts = getenv("ILQG_DERIV_PARTS") != nullptr;
-    d->env.no_dma = getenv("ILQG_NO_DMA") != nullptr;
-    d->env.no_rollout_parts = getenv("ILQG_NO_ROLLOUT_PARTS") != nullptr;
-    d->env.quad_spec = !(getenv("ILQG_QUAD_SPEC") != nullptr && atoi(getenv("ILQG_QUAD_SPEC")) == 0);  // on unless ILQG_QUAD_SPEC=0
 #if ILQG_WAVE_MAP
-    d->scratch.derivs_f = uses_scratch(k_derivs_wave<FACTORED>);
-    d->scratch.derivs_g = uses_scratch(k_derivs_wave<false>);
-    d->scratch.quad_f = QUAD_STEP && uses_scratch(k_backward_quad<FACTORED>);
-    d->scratch.quad_g = QUAD_STEP && uses_scratch(k_backward_quad<false>);
-    d->scratch.quad_sf = QUAD_STEP && uses_scratch(k_backward_quad<FACTORED, true>);
-    d->scratch.quad_sg = QUAD_STEP && uses_scratch(k_backward_quad<false, true>);
-    d->scratch.wave_f = uses_scratch(k_backward_wave<FACTORED>);
-    d->scratch.wave_g = uses_scratch(k_backward_wave<false>);
+    wave_kernels_fill(d->wave_kernels);
+    const auto prepare = [](auto &k) {
+        k.scratch = uses_scratch(k.fn);
+        if(k.lds_limit) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_limit));
+        return 0;
+    };
+    for(auto &k : d->wave_kernels.derivs)
+        if(prepare(k)) return 1;
+    for(auto &k : d->wave_kernels.sweep)
+        if(prepare(k)) return 1;
 #endif
 #if ILQG_WAVE_MAP && defined(ILQG_ROLLOUT_PARTS)
-    {
-        // measured (config 5, ~300 busy workgroups in the second stage): 32.9 / 40.3 ms without, 33.0 / 28.5 ms with;
-        // with fewer than 256 busy workgroups every one of them gets a CU to itself (ILQG_ROLL_LDS_KB=0: off)
-        const char *e = getenv("ILQG_ROLL_LDS_KB");
-        d->roll_lds = (size_t)(e ? atoi(e) : 84) * 1024;
-        if(d->roll_lds)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_parts<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)d->roll_lds));
-        // records through LDS (see k_rollout_parts; ILQG_NO_DMA=1: per-lane loads).  With them a workgroup takes more than
-        // half of a CU's LDS whenever a record is 640 bytes or more; below that the same is asked for explicitly
-        d->roll_dma = !d->env.no_dma;
-        const size_t need = (size_t)WAVE * RNP * sizeof(double);
-        d->roll_pad = (d->roll_lds > need + 40 * 1024) ? d->roll_lds - need - 40 * 1024 : 0;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_parts<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(need + d->roll_pad)));
-    }
-#endif
-#if ILQG_WAVE_MAP
-    if(FACTORED) {  // the workgroups that share the coefficient tables need more than the default 64 KB of LDS
-        const int lds = (int)((TABLE_DOUBLES + ILQG_FACT_WAVES * WAVE_LDS_DOUBLES) * sizeof(double));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_backward_wave<FACTORED>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    if(QUAD_STEP) {
-        const int lds = (int)((TABLE_DOUBLES + QUAD_WAVES * 4 * QRow::SIZE) * sizeof(double));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_backward_quad<FACTORED>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_backward_quad<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_backward_quad<FACTORED, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_backward_quad<false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
+    if(d->env.roll_lds)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_parts<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)d->env.roll_lds));
+    // records through LDS (see k_rollout_parts; ILQG_NO_DMA=1: per-lane loads).  With them a workgroup takes more than
+    // half of a CU's LDS whenever a record is 640 bytes or more; below that the same is asked for explicitly
+    d->roll_dma = !d->env.no_dma;
+    const size_t roll_need = (size_t)WAVE * RNP * sizeof(double);
+    d->roll_pad = (d->env.roll_lds > roll_need + 40 * 1024) ? d->env.roll_lds - roll_need - 40 * 1024 : 0;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_parts<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(roll_need + d->roll_pad)));
 #endif
     // (the second stream is the wave mapping's chunk pipeline; the lane mapping does not make one: the streams of a process
     // share four hardware queues, and with two streams per context the four groups of a batch sit on two of them in pairs)
-    if(WAVE_MAP || getenv("ILQG_SECOND_STREAM")) HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
+    if(WAVE_MAP || d->env.second_stream) HIP_TRY(hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d->fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d->join, hipEventDisableTiming));
     if(WAVE_MAP) {
@@ -666,12 +700,10 @@ static int dev_fill(ilqg_dev *d, int device, int batch, int n_hor) {
             }
             W.refs++;
             d->shared = &W;
-            size_t c = (W.bytes - sizeof(trajEl_t)) / per_traj;
-            if(c < 1) {
+            if((W.bytes - sizeof(trajEl_t)) / per_traj < 1) {
                 g_err = "ilqg_dev_create: the device's derivative work buffer (made for a shorter horizon) does not hold one trajectory";
                 return 1;
             }
-            d->chunk = (int)(c > (size_t)d->B ? (size_t)d->B : c);
 #endif
             continue;
         }
@@ -983,7 +1015,6 @@ static int own_work(ilqg_dev *d) {
     }
     if(repoint(d->P.work, d->work, d->work.reserve((size_t)d->B * per_traj))) return 1;
     HIP_TRY(hipMemsetAsync(d->P.work, 0, (size_t)d->B * per_traj, d->stream));
-    d->own_chunk = d->B;
     d->work_consts = false;
     return 0;
 }
@@ -1207,7 +1238,7 @@ static void launch_rollout(ilqg_dev_t *d, int mode, int kernel_id, int a0, int n
             hipLaunchKernelGGL(k_rollout_parts<true>, dim3(d->Bp / WAVE, n_alpha), dim3(WAVE * RW), (size_t)WAVE * RNP * sizeof(double) + d->roll_pad,
                                stream, Q, d->O, d->pv, mode, a0);
         } else {
-            const size_t lds = (n_alpha > 1) ? d->roll_lds : 0;
+            const size_t lds = (n_alpha > 1) ? d->env.roll_lds : 0;
             hipLaunchKernelGGL(k_rollout_parts<false>, dim3(d->Bp / WAVE, n_alpha), dim3(WAVE * RW), lds, stream, Q, d->O, d->pv, mode, a0);
         }
     }
@@ -1750,7 +1781,8 @@ int ilqg_dev_loop_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, dou
 
 #if ILQG_WAVE_MAP
 // wave mapping: derivative records are evaluated chunk by chunk into the work buffer and consumed by
-// the backward kernel of the same chunk.  do_derivs = 0 uses the records already in the buffer.
+// the backward kernel of the same chunk (wave_backward: work_plan, then launch_derivs and launch_sweep piece by piece).
+
 // the most backward sweeps one call of the retry loop can make under these options (iLQG.c:261-283): sweep 0 at the lambda the
 // trajectory has, sweep j at the lambda j increases later (lambda_up, the step k_backward_quad's attempts take), while
 // lambda <= lambdaMax.  The longest schedule starts from lambda = 0 with the smallest dlambda (every increase then
@@ -1766,31 +1798,39 @@ static int spec_sweeps_at_most(const ilqg_dev_opts_t &O) {
     return sweeps;
 }
 
-static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_backward) {
+// Where the records of a derivatives / backward call go and how the batch is divided (work_plan)
+struct WorkPlan {
+    SharedWork *shared;          // transient records (made and consumed in this call): the device's buffer; null: the context's private one
+    bool fact, quad;             // factored records; the quad mapping sweeps them
+    char *work;
+    size_t stride;               // bytes between two records
+    int chunk;                   // trajectories whose records the buffer holds
+    bool split;                  // the pieces alternate between the two halves of the buffer, on two streams
+    int half_cap, part, pieces;  // trajectories a half holds, trajectories of a piece, pieces
+    bool *whole, *half;          // which constant entries (init_running) the buffer already holds: all of it, each half
+};
+
+static int work_plan(ilqg_dev_t *d, int do_derivs, int do_backward, WorkPlan &w) {
     // Records produced and consumed in one go use the device's shared work buffer, chunk by chunk; records that are
     // left behind or found (ilqg_dev_derivs, the drop-in back_pass()) the context's private one, whole batch.
-    const bool transient = do_derivs && do_backward;
+    w.shared = do_derivs && do_backward ? d->shared : nullptr;
     // factored records (FACTORED builds, option fuse_derivs): only in the transient case — records the caller reads or
     // writes are always the complete ones
-    const bool fact = FACTORED && d->O.fuse_derivs && transient;
-    SharedWork *W = transient ? d->shared : nullptr;
-    const size_t stride = fact ? FACT_STRIDE : (transient ? STORED_STRIDE : sizeof(trajEl_t));
-    char *work;
-    int chunk;
-    if(transient) {
-        work = reinterpret_cast<char *>(W->buf);
+    w.fact = FACTORED && d->O.fuse_derivs && w.shared;
+    w.stride = w.fact ? FACT_STRIDE : (w.shared ? STORED_STRIDE : sizeof(trajEl_t));
+    if(w.shared) {
+        w.work = reinterpret_cast<char *>(w.shared->buf);
         // (the last record reaches sizeof(trajEl_t) beyond its start whatever the distance between records)
-        const size_t fit = (W->bytes - sizeof(trajEl_t)) / ((size_t)d->N * stride);
-        chunk = (int)(fit > (size_t)d->B ? (size_t)d->B : fit);
-        if(chunk < 1) {
+        const size_t fit = (w.shared->bytes - sizeof(trajEl_t)) / ((size_t)d->N * w.stride);
+        w.chunk = (int)(fit > (size_t)d->B ? (size_t)d->B : fit);
+        if(w.chunk < 1) {
             g_err = "the device's derivative work buffer does not hold one trajectory of this horizon";
             return 1;
         }
-        HIP_TRY(hipStreamWaitEvent(d->stream, W->free_ev, 0));  // the previous owner's pass has finished
     } else {
         if(own_work(d)) return 1;
-        work = reinterpret_cast<char *>(d->P.work);
-        chunk = d->own_chunk;
+        w.work = reinterpret_cast<char *>(d->P.work);
+        w.chunk = d->B;  // (own_work holds the whole batch)
     }
     // A batch that needs several chunks alternates between the two halves of the work buffer on two streams, so that
     // the derivatives of one chunk are evaluated while the other's backward pass runs and the end of one backward
@@ -1800,158 +1840,140 @@ static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_
     // four to a wavefront: the more trajectories a queue holds per worker, the less the workers' last ones — 1 to 4 sweeps
     // each — stick out at the end; measured, config 5: 197.8 ms per iteration in two pieces, 181.6 in one.
     // ILQG_TWO_PIECES=1 restores the halves.)
-    const bool quad_here = QUAD_STEP && d->O.regType == 1 && (fact || !FULL || d->env.quad_stored) && !d->env.no_quad;
-    const bool split = transient && chunk >= 2 && (d->B > chunk || (d->B >= 16 * d->cus && (!quad_here || d->env.two_pieces)));
-    const int half_cap = split ? chunk / 2 : chunk;              // trajectories a half of the buffer holds
-    const int pieces = (d->B + half_cap - 1) / half_cap;
-    int part = chunk;
-    if(split) {
-        part = ((d->B + pieces - 1) / pieces + 7) / 8 * 8;  // whole workgroups of the factored backward kernel
-        if(part > half_cap) part = half_cap;
+    // quad mapping (16 lanes per trajectory) where it applies; ILQG_NO_QUAD=1: the row mapping (comparison)
+    w.quad = QUAD_STEP && d->O.regType == 1 && (w.fact || !FULL || d->env.quad_stored) && !d->env.no_quad;
+    w.split = w.shared && w.chunk >= 2 && (d->B > w.chunk || (d->B >= 16 * d->cus && (!w.quad || d->env.two_pieces)));
+    w.half_cap = w.split ? w.chunk / 2 : w.chunk;
+    w.pieces = (d->B + w.half_cap - 1) / w.half_cap;
+    w.part = w.chunk;
+    if(w.split) {
+        w.part = ((d->B + w.pieces - 1) / w.pieces + 7) / 8 * 8;  // whole workgroups of the factored backward kernel
+        if(w.part > w.half_cap) w.part = w.half_cap;
     }
-    // which constant entries (init_running) the buffer already holds for this context
-    bool *whole = &d->work_consts, *half = d->half_consts;
-    if(transient) {
-        const bool same = W->pv_set && W->N == d->N && W->B == d->B && W->part == part && W->half_cap == half_cap &&
-                          W->factored == fact && !d->per_step_params && memcmp(&W->pv, &d->pv, sizeof(ParamValues)) == 0;
+    w.whole = &d->work_consts, w.half = d->half_consts;
+    if(w.shared) {  // the shared buffer's constants are another context's, or of another division: none count
+        SharedWork *W = w.shared;
+        const bool same = W->pv_set && W->N == d->N && W->B == d->B && W->part == w.part && W->half_cap == w.half_cap &&
+                          W->factored == w.fact && !d->per_step_params && memcmp(&W->pv, &d->pv, sizeof(ParamValues)) == 0;
         if(!same) {
             W->whole = W->half[0] = W->half[1] = false;
-            W->pv = d->pv;
-            W->pv_set = !d->per_step_params;
-            W->N = d->N;
-            W->B = d->B;
-            W->part = part;
-            W->half_cap = half_cap;
-            W->factored = fact;
+            W->pv = d->pv, W->pv_set = !d->per_step_params;
+            W->N = d->N, W->B = d->B, W->part = w.part, W->half_cap = w.half_cap, W->factored = w.fact;
         }
-        whole = &W->whole;
-        half = W->half;
+        w.whole = &W->whole, w.half = W->half;
     }
-    if(split) {
+    return 0;
+}
+
+// the derivative records of one piece (trajectories c0 .. c0 + cnt - 1 into half h of the buffer, P.work)
+static int launch_derivs(ilqg_dev_t *d, const WorkPlan &w, const DevPtrs &P, hipStream_t st, int h, int c0, int cnt) {
+    const auto &k = derivs_kernel(d, w.fact);
+    const bool have_consts = *w.whole || (w.split && w.half[h]);
+    // (transient records are read by the backward pass alone: the limits' signs and gradients, which it does not
+    // use unless the limits depend on the state, are left out of them)
+    const int limit_gradients = (w.shared && !HX) ? 0 : 1;
+#if ILQG_HAVE_DERIV_PARTS
+    // records of the steps assembled on chip, whole lines out (k_derivs_parts) once the buffer holds the constant
+    // entries; the final records from the derivative kernel.  MEASURED SLOWER than the generated code on a struct per lane
+    // (51 against 44 ms per iteration of config 5, see the kernel): off unless ILQG_DERIV_PARTS=1
+    if(w.fact && have_consts && d->env.deriv_parts) {
+        if(on_scratch_stream(d, true, st, [&](hipStream_t q) {
+               Timed t(d, ILQG_K_DERIVS, q);
+               hipLaunchKernelGGL(k_derivs_parts, grid1((size_t)cnt * d->N, 64 * DP_WAVES), dim3(64 * DP_WAVES), 0, q, P, d->O, d->pv, c0, cnt);
+               hipLaunchKernelGGL(k.fn, k.grid((size_t)cnt, d->cus), dim3(k.block), k.lds, q, P, d->O, d->pv, c0, cnt, 0, 0, 1);
+           }))
+            return 1;
+    } else
+#endif
+    if(on_scratch_stream(d, k.scratch, st, [&](hipStream_t q) {
+           Timed t(d, ILQG_K_DERIVS, q);
+           hipLaunchKernelGGL(k.fn, k.grid((size_t)cnt * (d->N + 1), d->cus), dim3(k.block), k.lds, q, P, d->O, d->pv, c0, cnt, have_consts ? 0 : 1,
+                              limit_gradients, 0);
+       }))
+        return 1;
+    if(cnt == w.part) {  // every element of this (half of the) buffer that is ever used has its constants now
+        if(w.split) w.half[h] = true;
+        else *w.whole = w.half[0] = w.half[1] = true;
+    }
+    return 0;
+}
+
+// Speculative retries (k_backward_quad<FACT, true>): rows whose queue is used up run other trajectories' next attempts.
+// The rows of a sweep over cnt trajectories, with the buffers of their protocol reserved; 0 = the device cannot spare them (the
+// rows' gains buffers are 1.1 MB per row at N = 1 000) and the caller sweeps without; -1 = error
+static int spec_rows(ilqg_dev_t *d, int cnt, hipStream_t st) {
+    const int rows = (int)sweep_kernel(d, false, true, true).grid((size_t)cnt, d->cus).x * 4 * QUAD_WAVES;
+    const int ri = d->spec_ints.try_reserve(((size_t)(3 + SPEC_ATTEMPTS) * d->B + rows) * sizeof(unsigned), st);
+    const int rd = ri ? ri : d->spec_doubles.try_reserve((size_t)rows * (SPEC_SLOTS + (size_t)d->N * SPEC_GW) * sizeof(double), st);
+    return rd == 0 ? rows : (rd == 2 ? 0 : -1);
+}
+// P.spec_* into those buffers, and the protocol's words cleared on the stream of the launch
+static void spec_point(ilqg_dev_t *d, DevPtrs &P, int rows, hipStream_t q) {
+    unsigned *w = d->spec_ints.get();
+    const size_t nb = (size_t)d->B;
+    P.spec_word = w;
+    P.spec_done = w + nb;
+    P.spec_out = w + 2 * nb;
+    P.spec_best = w + (2 + SPEC_ATTEMPTS) * nb;
+    P.spec_row_b = reinterpret_cast<int *>(w + (3 + SPEC_ATTEMPTS) * nb);
+    P.spec_res = d->spec_doubles.get();
+    P.spec_gains = d->spec_doubles.get() + (size_t)rows * SPEC_SLOTS;
+    P.spec_rows = rows;
+    g_spec_last = d;
+    (void)hipMemsetAsync(w, 0, (2 + SPEC_ATTEMPTS) * nb * sizeof(unsigned), q);
+    (void)hipMemsetAsync(P.spec_best, 0xff, (nb + (size_t)rows) * sizeof(unsigned), q);
+}
+
+// the backward sweep of one piece
+static int launch_sweep(ilqg_dev_t *d, const WorkPlan &w, DevPtrs &P, hipStream_t st, int single_sweep, int c0, int cnt) {
+    HIP_TRY(hipMemsetAsync(P.queue, 0, sizeof(int), st));
+    // speculative retries: one piece, the retry loop on the device (ILQG_QUAD_SPEC=0: off)
+    // (round 6: in the layout of two wavefronts per SIMD as well, -DILQG_QUAD_LEAN=63: 255 registers, 2 spilled)
+    bool spec = w.quad && d->env.quad_spec && !single_sweep && !w.split && c0 == 0 && cnt == d->B;
+    // the kernel numbers a trajectory's sweeps 0 .. SPEC_ATTEMPTS - 1: options whose lambda schedule (iLQG.c:271-274,
+    // user-settable lambdaFactor / lambdaMin / lambdaMax) allows more sweeps than that take the sequential loop
+    if(spec && spec_sweeps_at_most(d->O) > SPEC_ATTEMPTS) spec = false;
+    const int rows = spec ? spec_rows(d, cnt, st) : 0;
+    if(rows < 0) return 1;
+    // (the product builds' backward kernels have no scratch; the -ffp-contract=off twins of the tests spill)
+    const auto &k = sweep_kernel(d, w.fact, w.quad, rows > 0);
+    return on_scratch_stream(d, k.scratch, st, [&](hipStream_t q) {
+        Timed t(d, ILQG_K_BACKWARD, q);
+        if(rows) spec_point(d, P, rows, q);
+        hipLaunchKernelGGL(k.fn, k.grid((size_t)cnt, d->cus), dim3(k.block), k.lds, q, P, d->O, single_sweep, c0, cnt);
+    });
+}
+
+// The pieces of a call, each on the stream of its half of the buffer.  do_derivs = 0 uses the records already in the buffer.
+static int wave_backward(ilqg_dev_t *d, int single_sweep, int do_derivs, int do_backward) {
+    WorkPlan w;
+    if(work_plan(d, do_derivs, do_backward, w)) return 1;
+    if(w.shared) HIP_TRY(hipStreamWaitEvent(d->stream, w.shared->free_ev, 0));  // the previous owner's pass has finished
+    if(w.split) {
         HIP_TRY(hipEventRecord(d->fork, d->stream));
         HIP_TRY(hipStreamWaitEvent(d->stream2, d->fork, 0));
     }
     int piece = 0;
-    for(int c0 = 0; c0 < d->B; c0 += part, piece++) {
-        const int cnt = (d->B - c0 < part) ? d->B - c0 : part;
-        const int h = split ? (piece & 1) : 0;
+    for(int c0 = 0; c0 < d->B; c0 += w.part, piece++) {
+        const int cnt = (d->B - c0 < w.part) ? d->B - c0 : w.part;
+        const int h = w.split ? (piece & 1) : 0;
         hipStream_t st = h ? d->stream2 : d->stream;
         DevPtrs P = d->P;
-        P.work = reinterpret_cast<trajEl_t *>(work + (size_t)h * half_cap * d->N * stride);
-        P.work_stride = stride;
+        P.work = reinterpret_cast<trajEl_t *>(w.work + (size_t)h * w.half_cap * d->N * w.stride);
+        P.work_stride = w.stride;
         P.queue = d->queues.get() + h * QUEUE_CELL;
-        if(do_derivs) {
-            const bool derivs_scratch = fact ? d->scratch.derivs_f : d->scratch.derivs_g;
-            const size_t total = (size_t)cnt * (d->N + 1);
-            const bool have_consts = *whole || (split && half[h]);
-            // (transient records are read by the backward pass alone: the limits' signs and gradients, which it does not
-            // use unless the limits depend on the state, are left out of them)
-#if ILQG_HAVE_DERIV_PARTS
-            // records of the steps assembled on chip, whole lines out (k_derivs_parts) once the buffer holds the constant
-            // entries.  MEASURED SLOWER than the generated code on a struct per lane (51 against 44 ms per iteration of
-            // config 5, see the kernel): off unless ILQG_DERIV_PARTS=1
-            if(fact && transient && have_consts && d->env.deriv_parts) {
-                if(on_scratch_stream(d, true, st, [&](hipStream_t q) {
-                       Timed t(d, ILQG_K_DERIVS, q);
-                       hipLaunchKernelGGL(k_derivs_parts, grid1((size_t)cnt * d->N, 64 * DP_WAVES), dim3(64 * DP_WAVES), 0, q, P, d->O, d->pv, c0, cnt);
-                       hipLaunchKernelGGL(k_derivs_wave<FACTORED>, grid1((size_t)cnt, ILQG_DERIVS_BLOCK), dim3(ILQG_DERIVS_BLOCK), 0, q, P, d->O, d->pv, c0, cnt, 0, 0, 1);
-                   }))
-                    return 1;
-            } else
-#endif
-            if(on_scratch_stream(d, derivs_scratch, st, [&](hipStream_t q) {
-                   Timed t(d, ILQG_K_DERIVS, q);
-                   if(fact)
-                       hipLaunchKernelGGL(k_derivs_wave<FACTORED>, grid1(total, ILQG_DERIVS_BLOCK), dim3(ILQG_DERIVS_BLOCK), 0, q, P, d->O, d->pv, c0, cnt,
-                                          have_consts ? 0 : 1, (transient && !HX) ? 0 : 1, 0);
-                   else
-                       hipLaunchKernelGGL(k_derivs_wave<false>, grid1(total, ILQG_DERIVS_BLOCK), dim3(ILQG_DERIVS_BLOCK), DERIVS_DYN_LDS, q, P, d->O, d->pv, c0, cnt,
-                                          have_consts ? 0 : 1, (transient && !HX) ? 0 : 1, 0);
-               }))
-                return 1;
-            if(cnt == part) {  // every element of this (half of the) buffer that is ever used has its constants now
-                if(split) half[h] = true;
-                else *whole = half[0] = half[1] = true;
-            }
-        }
-        if(do_backward) {
-            HIP_TRY(hipMemsetAsync(P.queue, 0, sizeof(int), st));
-            // quad mapping (16 lanes per trajectory) where it applies; ILQG_NO_QUAD=1: the row mapping (comparison)
-            const bool quad = quad_here;
-            // speculative retries: one piece, the retry loop on the device (ILQG_QUAD_SPEC=1)
-            // (round 6: in the layout of two wavefronts per SIMD as well, -DILQG_QUAD_LEAN=63: 255 registers, 2 spilled)
-            bool spec = quad && d->env.quad_spec && !single_sweep && !split && c0 == 0 && cnt == d->B;
-            // the kernel numbers a trajectory's sweeps 0 .. SPEC_ATTEMPTS - 1: options whose lambda schedule (iLQG.c:271-274,
-            // user-settable lambdaFactor / lambdaMin / lambdaMax) allows more sweeps than that take the sequential loop
-            if(spec && spec_sweeps_at_most(d->O) > SPEC_ATTEMPTS) spec = false;
-            if(spec) {  // (a device that cannot spare the rows' gains buffers — 1.1 MB per row at N = 1 000 — sweeps without)
-                const int per_wg = 4 * QUAD_WAVES;
-                const int wgs = (cnt + per_wg - 1) / per_wg, rows = (wgs < d->cus ? wgs : d->cus) * per_wg;
-                const int ri = d->spec_ints.try_reserve(((size_t)(3 + SPEC_ATTEMPTS) * d->B + rows) * sizeof(unsigned), st);
-                const int rd = ri ? ri : d->spec_doubles.try_reserve((size_t)rows * (SPEC_SLOTS + (size_t)d->N * SPEC_GW) * sizeof(double), st);
-                if(ri == 1 || rd == 1) return 1;
-                if(ri == 2 || rd == 2) spec = false;
-            }
-            // (the product builds' backward kernels have no scratch; the -ffp-contract=off twins of the tests spill)
-            const bool needs = quad ? (spec ? (fact ? d->scratch.quad_sf : d->scratch.quad_sg) : (fact ? d->scratch.quad_f : d->scratch.quad_g))
-                                    : (fact ? d->scratch.wave_f : d->scratch.wave_g);
-            if(on_scratch_stream(d, needs, st, [&](hipStream_t q) {
-                   Timed t(d, ILQG_K_BACKWARD, q);
-                   if(quad) {
-                       const size_t lds = (size_t)((fact ? TABLE_DOUBLES : 0) + QUAD_WAVES * 4 * QRow::SIZE) * sizeof(double);
-                       const int per_wg = 4 * QUAD_WAVES;
-                       const int wgs = (cnt + per_wg - 1) / per_wg;  // one workgroup per CU at a time
-                       if(spec) {  // rows whose queue is used up run other trajectories' next attempts (k_backward_quad, SPEC)
-                           const int grid = wgs < d->cus ? wgs : d->cus, rows = grid * per_wg;
-                           unsigned *w = d->spec_ints.get();
-                           const size_t nb = (size_t)d->B;
-                           P.spec_word = w;
-                           P.spec_done = w + nb;
-                           P.spec_out = w + 2 * nb;
-                           P.spec_best = w + (2 + SPEC_ATTEMPTS) * nb;
-                           P.spec_row_b = reinterpret_cast<int *>(w + (3 + SPEC_ATTEMPTS) * nb);
-                           P.spec_res = d->spec_doubles.get();
-                           P.spec_gains = d->spec_doubles.get() + (size_t)rows * SPEC_SLOTS;
-                           P.spec_rows = rows;
-                           g_spec_last = d;
-                           (void)hipMemsetAsync(w, 0, (2 + SPEC_ATTEMPTS) * nb * sizeof(unsigned), q);
-                           (void)hipMemsetAsync(P.spec_best, 0xff, (nb + (size_t)rows) * sizeof(unsigned), q);
-                           if(fact)
-                               hipLaunchKernelGGL((k_backward_quad<FACTORED, true>), dim3(grid), dim3(64 * QUAD_WAVES), lds, q, P, d->O, single_sweep, c0, cnt);
-                           else
-                               hipLaunchKernelGGL((k_backward_quad<false, true>), dim3(grid), dim3(64 * QUAD_WAVES), lds, q, P, d->O, single_sweep, c0, cnt);
-                       }
-                       if(spec) {
-                       } else if(fact)
-                           hipLaunchKernelGGL(k_backward_quad<FACTORED>, dim3(wgs < d->cus ? wgs : d->cus), dim3(64 * QUAD_WAVES), lds, q, P, d->O,
-                                              single_sweep, c0, cnt);
-                       else
-                           hipLaunchKernelGGL(k_backward_quad<false>, dim3(wgs < d->cus ? wgs : d->cus), dim3(64 * QUAD_WAVES), lds, q, P, d->O,
-                                              single_sweep, c0, cnt);
-                   } else if(fact) {
-                       constexpr int WV = ILQG_FACT_WAVES;
-                       const size_t lds = (size_t)(TABLE_DOUBLES + WV * WAVE_LDS_DOUBLES) * sizeof(double);
-                       const int wgs = (cnt + WV - 1) / WV;  // one workgroup per CU at a time (LDS)
-                       hipLaunchKernelGGL(k_backward_wave<FACTORED>, dim3(wgs < d->cus ? wgs : d->cus), dim3(64 * WV), lds, q, P, d->O,
-                                          single_sweep, c0, cnt);
-                   } else {
-                       const int cap = d->cus * 8;
-                       hipLaunchKernelGGL(k_backward_wave<false>, dim3(cnt < cap ? cnt : cap), dim3(64),
-                                          (size_t)WAVE_LDS_DOUBLES * sizeof(double), q, P, d->O, single_sweep, c0, cnt);
-                   }
-               }))
-                return 1;
-        }
+        if(do_derivs && launch_derivs(d, w, P, st, h, c0, cnt)) return 1;
+        if(do_backward && launch_sweep(d, w, P, st, single_sweep, c0, cnt)) return 1;
     }
     if(do_derivs) {  // every slot a batch of this size and division uses has been visited
-        if(split) half[0] = half[1] = true;
-        else *whole = half[0] = half[1] = true;
+        if(w.split) w.half[0] = w.half[1] = true;
+        else *w.whole = w.half[0] = w.half[1] = true;
     }
-    if(split) {
+    if(w.split) {
         HIP_TRY(hipEventRecord(d->join, d->stream2));
         HIP_TRY(hipStreamWaitEvent(d->stream, d->join, 0));
     }
-    if(transient) HIP_TRY(hipEventRecord(W->free_ev, d->stream));
+    if(w.shared) HIP_TRY(hipEventRecord(w.shared->free_ev, d->stream));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2008,6 +2030,136 @@ int ilqg_dev_backward(ilqg_dev_t *d, int mode) {
 #endif
 }
 
+// What the three searches below share: the selection among step sizes [a0, a1) (second: of the second stage) ...
+static void launch_select(ilqg_dev_t *d, hipStream_t rs, int a0, int a1, int second) {
+    Timed t(d, ILQG_K_SELECT, rs);
+    hipLaunchKernelGGL(k_select, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, d->O, a0, a1, second);
+}
+// ... and the buffer of the roll-outs a stage of n_alpha step sizes keeps (P.cand, P.cand1)
+static int reserve_kept(ilqg_dev_t *d, double *&view, Buffer<double> &owner, int n_alpha, hipStream_t rs) {
+    return repoint(view, owner, owner.reserve((size_t)d->Bp * n_alpha * (d->N + 1) * CAND_W * sizeof(double), rs));
+}
+
+#if !ILQG_WAVE_MAP
+}  // extern "C"
+// a stage of the search that keeps planes: step sizes [a0, a0 + n), T trajectories to a wavefront
+template <int STAGE>
+static void launch_search_stage(ilqg_dev_t *d, hipStream_t rs, int a0, int n, int set) {
+    Timed t(d, STAGE ? ILQG_K_SEARCH2 : ILQG_K_SEARCH, rs);
+    const int T = WAVE / n;
+    const dim3 grid((d->B + T - 1) / T), block(WAVE);
+    if(T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma)  // the nominal records through LDS
+        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<STAGE, true, decltype(tr)...>), grid, block, SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, a0, n, set, tr...); });
+    else
+        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<STAGE, false, decltype(tr)...>), grid, block, 0, rs, d->P, d->O, d->pv, a0, n, set, tr...); });
+}
+extern "C" {
+
+// Lane mapping, ls_keep = 2: every roll-out of the search is kept and the accepted one becomes the current trajectory by a
+// change of its location index (k_search, k_adopt_home, k_commit; see cur_x).  2 = the device does not have the planes.
+static int search_kept_planes(ilqg_dev_t *d, int A, int s1) {
+    hipStream_t rs = roll_stream(d);
+    const size_t xplane = (size_t)(d->N + 1) * NX * d->Bp, uplane = (size_t)d->N * NU * d->Bp;
+    // Two sets of s1 planes of the size of X resp. U (12.6 GB for the benchmark: 2 x 4 planes of 65 536 x 501 x 6
+    // doubles).  The planes are laid out s1 to a set: a first stage of another size re-homes the trajectories first.
+    // A device that cannot provide them (a larger batch, several contexts sharing it) searches without keeping
+    // every roll-out instead of failing: the ls_keep = 1 form needs none of this memory.
+    if(d->P.plane_n != s1) {
+        if(all_home(d)) return 1;
+        d->P.plane_n = s1;
+    }
+    const int rx = repoint(d->P.xpl, d->xpl, d->xpl.try_reserve(2 * (size_t)s1 * xplane * sizeof(double), rs));
+    const int ru = rx ? rx : repoint(d->P.upl, d->upl, d->upl.try_reserve(2 * (size_t)s1 * uplane * sizeof(double), rs));
+    if(rx == 1 || ru == 1) return 1;
+    if(rx == 2 || ru == 2) {
+        if(repoint(d->P.xpl, d->xpl, d->xpl.release())) return 1;
+        d->loc_set = -1;  // nothing lives in a plane any more — there are none
+        HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
+        return 2;
+    }
+    const int n2 = A - s1, set = (d->loc_set == 0) ? 1 : 0;
+    d->P.xplane = xplane;
+    d->P.uplane = uplane;
+    if(n2 > 0 && reserve_kept(d, d->P.cand, d->cand, n2, rs)) return 1;
+    if(!d->pending_zero) HIP_TRY(hipMemsetAsync(d->P.n_pending, 0, sizeof(int), rs));
+    d->pending_zero = false;
+    launch_search_stage<0>(d, rs, 0, s1, set);
+    if(n2 > 0) {  // the grid covers the worst case; wavefronts beyond the pending count return at once
+        launch_search_stage<1>(d, rs, s1, n2, set);
+        Timed t(d, ILQG_K_ADOPT, rs);
+        hipLaunchKernelGGL(k_adopt_home, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1);
+    } else {
+        Timed t(d, ILQG_K_ADOPT, rs);
+        hipLaunchKernelGGL(k_rejected_home, dim3(8 * d->cus), dim3(256), 0, rs, d->P);
+    }
+    if(d->defer_commit) {  // inside ilqg_dev_iterate: the update kernel of this iteration commits
+        d->commit_pending = true;
+        d->commit_s1 = s1;
+        d->commit_set = set;
+    } else {
+        Timed t(d, ILQG_K_ADOPT, rs);
+        hipLaunchKernelGGL(k_commit, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, s1, set);
+    }
+    d->loc_set = set;
+    d->winner_done = true;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+#endif
+
+#if ILQG_WAVE_MAP && defined(ILQG_ROLLOUT_PARTS)
+// Wave mapping with the roll-outs in parts: BOTH stages keep what they roll out and the accepted roll-outs are
+// copied into the records — no winner pass (16 384 chains of N steps beside the second stage's: the second
+// launch needed two rounds of workgroups, 50 ms; the second stage alone fits one).
+static int search_rollout_parts(ilqg_dev_t *d, int A, int s1) {
+    hipStream_t rs = roll_stream(d);
+    const int n2 = A - s1;
+    if(reserve_kept(d, d->P.cand1, d->cand1, s1, rs)) return 1;
+    if(n2 > 0 && reserve_kept(d, d->P.cand, d->cand, n2, rs)) return 1;
+    d->keep_first = true;
+    launch_rollout(d, ROLL_SEARCH, ILQG_K_ROLLOUT_SEARCH, 0, s1, rs);
+    d->keep_first = false;
+    launch_select(d, rs, 0, s1, 0);
+    if(n2 > 0) {
+        launch_rollout(d, ROLL_LIST_KEEP, ILQG_K_ROLLOUT_SEARCH2, s1, n2, rs);
+        launch_select(d, rs, s1, A, 1);
+        Timed t(d, ILQG_K_ROLLOUT_WINNER, rs);
+        hipLaunchKernelGGL(k_adopt, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1, n2);
+    }
+    {
+        Timed t(d, ILQG_K_ROLLOUT_WINNER, rs);
+        hipLaunchKernelGGL(k_adopt_first, dim3(16 * d->cus), dim3(256), 0, rs, d->P, s1);
+    }
+    d->winner_done = true;
+    return 0;
+}
+#endif
+
+// The plain search: the roll-out kernel per stage; accepted trajectories are stored in place, by the second stage's launch
+// where there is one, else by ilqg_dev_winner
+static int search_plain(ilqg_dev_t *d, int A, int s1) {
+    hipStream_t rs = roll_stream(d);
+    launch_rollout(d, ROLL_SEARCH, ILQG_K_ROLLOUT_SEARCH, 0, s1, rs);
+    launch_select(d, rs, 0, s1, 0);
+    d->winner_done = false;
+    if(s1 < A && !d->O.ls_keep) {
+        // the grid covers the worst case; blocks beyond the pending count return at once
+        launch_rollout(d, ROLL_SEARCH_LIST, ILQG_K_ROLLOUT_SEARCH2, s1, A - s1, rs);
+        launch_select(d, rs, s1, A, 1);
+    } else if(s1 < A) {
+        // Second stage and the winner pass of the trajectories the first stage settled in ONE launch (ROLL_SECOND);
+        // the grid covers the worst case, blocks beyond the pending count return at once.
+        const int n2 = A - s1;
+        if(reserve_kept(d, d->P.cand, d->cand, n2, rs)) return 1;
+        launch_rollout(d, ROLL_SECOND, ILQG_K_ROLLOUT_SEARCH2, s1, n2 + 1, rs);
+        launch_select(d, rs, s1, A, 1);
+        Timed t(d, ILQG_K_ROLLOUT_WINNER, rs);
+        hipLaunchKernelGGL(k_adopt, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1, n2);
+        d->winner_done = true;
+    }
+    return 0;
+}
+
 // Line search (line_search.c:33-78) in up to two stages, see k_select / k_rollout:
 //   stage 1: step sizes [0, s1) for every trajectory; selection
 //   stage 2: step sizes [s1, n_alpha) for the trajectories still without an acceptable one; selection
@@ -2016,142 +2168,22 @@ int ilqg_dev_search(ilqg_dev_t *d) {
     HIP_TRY(hipSetDevice(d->device));
     const int A = d->O.n_alpha;
     const int s1 = (d->O.ls_split > 0 && d->O.ls_split < A) ? d->O.ls_split : A;
-    hipStream_t rs = roll_stream(d);
 #if !ILQG_WAVE_MAP
-    bool keep_all = d->O.ls_keep >= 2 && s1 <= PLANE_A && WAVE / s1 >= 1 && (A == s1 || WAVE / (A - s1) >= 1);
-    const size_t xplane = (size_t)(d->N + 1) * NX * d->Bp, uplane = (size_t)d->N * NU * d->Bp;
-    if(keep_all) {
-        // Two sets of s1 planes of the size of X resp. U (12.6 GB for the benchmark: 2 x 4 planes of 65 536 x 501 x 6
-        // doubles).  The planes are laid out s1 to a set: a first stage of another size re-homes the trajectories first.
-        // A device that cannot provide them (a larger batch, several contexts sharing it) searches without keeping
-        // every roll-out instead of failing: the ls_keep = 1 form below needs none of this memory.
-        if(d->P.plane_n != s1) {
-            if(all_home(d)) return 1;
-            d->P.plane_n = s1;
-        }
-        const int rx = repoint(d->P.xpl, d->xpl, d->xpl.try_reserve(2 * (size_t)s1 * xplane * sizeof(double), rs));
-        const int ru = rx ? rx : repoint(d->P.upl, d->upl, d->upl.try_reserve(2 * (size_t)s1 * uplane * sizeof(double), rs));
-        if(rx == 1 || ru == 1) return 1;
-        if(rx == 2 || ru == 2) {
-            if(repoint(d->P.xpl, d->xpl, d->xpl.release())) return 1;
-            keep_all = false;  // (all_home() below: nothing lives in a plane any more — there are none)
-            d->loc_set = -1;
-            HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
-        }
-    }
-    if(keep_all) {
-        // Every roll-out of the search is kept and the accepted one becomes the current trajectory by a change of its
-        // location index (k_search, k_adopt_home, k_commit; see cur_x).
-        const int n2 = A - s1, set = (d->loc_set == 0) ? 1 : 0;
-        d->P.xplane = xplane;
-        d->P.uplane = uplane;
-        if(n2 > 0 && repoint(d->P.cand, d->cand, d->cand.reserve((size_t)d->Bp * n2 * (d->N + 1) * CAND_W * sizeof(double), rs))) return 1;
-        if(!d->pending_zero) HIP_TRY(hipMemsetAsync(d->P.n_pending, 0, sizeof(int), rs));
-        d->pending_zero = false;
-        {
-            Timed t(d, ILQG_K_SEARCH, rs);
-            const int T = WAVE / s1;
-            const bool dma = T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma;
-            if(dma)
-                with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<0, true, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, 0, s1, set, tr...); });
-            else
-                with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<0, false, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, 0, s1, set, tr...); });
-        }
-        if(n2 > 0) {  // the grid covers the worst case; wavefronts beyond the pending count return at once
-            {
-                Timed t(d, ILQG_K_SEARCH2, rs);
-                const int T = WAVE / n2;
-                const bool dma = T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma;
-                if(dma)
-                    with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<1, true, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, s1, n2, set, tr...); });
-                else
-                    with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<1, false, decltype(tr)...>), dim3((d->B + T - 1) / T), dim3(WAVE), 0, rs, d->P, d->O, d->pv, s1, n2, set, tr...); });
-            }
-            Timed t(d, ILQG_K_ADOPT, rs);
-            hipLaunchKernelGGL(k_adopt_home, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1);
-        } else {
-            Timed t(d, ILQG_K_ADOPT, rs);
-            hipLaunchKernelGGL(k_rejected_home, dim3(8 * d->cus), dim3(256), 0, rs, d->P);
-        }
-        if(d->defer_commit) {  // inside ilqg_dev_iterate: the update kernel of this iteration commits
-            d->commit_pending = true;
-            d->commit_s1 = s1;
-            d->commit_set = set;
-        } else {
-            Timed t(d, ILQG_K_ADOPT, rs);
-            hipLaunchKernelGGL(k_commit, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, s1, set);
-        }
-        d->loc_set = set;
-        d->winner_done = true;
-        HIP_TRY(hipGetLastError());
-        return 0;
+    if(d->O.ls_keep >= 2 && s1 <= PLANE_A && WAVE / s1 >= 1 && (A == s1 || WAVE / (A - s1) >= 1)) {
+        const int rc = search_kept_planes(d, A, s1);
+        if(rc != 2) return rc;
     }
     if(all_home(d)) return 1;  // the searches below store accepted trajectories in place: in X / U
 #endif
     if(roll_enter(d)) return 1;
-    HIP_TRY(hipMemsetAsync(d->P.n_pending, 0, sizeof(int), rs));
+    HIP_TRY(hipMemsetAsync(d->P.n_pending, 0, sizeof(int), roll_stream(d)));
     d->pending_zero = false;
+    bool parts = false;
 #if ILQG_WAVE_MAP && defined(ILQG_ROLLOUT_PARTS)
-    if(d->O.ls_keep >= 2 && !HAS_MUL && !d->env.no_rollout_parts) {
-        // Wave mapping with the roll-outs in parts: BOTH stages keep what they roll out and the accepted roll-outs are
-        // copied into the records — no winner pass (16 384 chains of N steps beside the second stage's: the second
-        // launch needed two rounds of workgroups, 50 ms; the second stage alone fits one).
-        const int n2 = A - s1;
-        const size_t row = (size_t)d->Bp * (d->N + 1) * CAND_W * sizeof(double);
-        if(repoint(d->P.cand1, d->cand1, d->cand1.reserve(row * s1, rs))) return 1;
-        if(n2 > 0 && repoint(d->P.cand, d->cand, d->cand.reserve(row * n2, rs))) return 1;
-        d->keep_first = true;
-        launch_rollout(d, ROLL_SEARCH, ILQG_K_ROLLOUT_SEARCH, 0, s1, rs);
-        d->keep_first = false;
-        {
-            Timed t(d, ILQG_K_SELECT, rs);
-            hipLaunchKernelGGL(k_select, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, d->O, 0, s1, 0);
-        }
-        if(n2 > 0) {
-            launch_rollout(d, ROLL_LIST_KEEP, ILQG_K_ROLLOUT_SEARCH2, s1, n2, rs);
-            {
-                Timed t(d, ILQG_K_SELECT, rs);
-                hipLaunchKernelGGL(k_select, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, d->O, s1, A, 1);
-            }
-            Timed t(d, ILQG_K_ROLLOUT_WINNER, rs);
-            hipLaunchKernelGGL(k_adopt, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1, n2);
-        }
-        {
-            Timed t(d, ILQG_K_ROLLOUT_WINNER, rs);
-            hipLaunchKernelGGL(k_adopt_first, dim3(16 * d->cus), dim3(256), 0, rs, d->P, s1);
-        }
-        d->winner_done = true;
-        HIP_TRY(hipGetLastError());
-        return roll_leave(d);
-    }
+    parts = d->O.ls_keep >= 2 && !HAS_MUL && !d->env.no_rollout_parts;
+    if(parts && search_rollout_parts(d, A, s1)) return 1;
 #endif
-    launch_rollout(d, ROLL_SEARCH, ILQG_K_ROLLOUT_SEARCH, 0, s1, rs);
-    {
-        Timed t(d, ILQG_K_SELECT, rs);
-        hipLaunchKernelGGL(k_select, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, d->O, 0, s1, 0);
-    }
-    d->winner_done = false;
-    if(s1 < A && !d->O.ls_keep) {
-        // the grid covers the worst case; blocks beyond the pending count return at once
-        launch_rollout(d, ROLL_SEARCH_LIST, ILQG_K_ROLLOUT_SEARCH2, s1, A - s1, rs);
-        Timed t(d, ILQG_K_SELECT, rs);
-        hipLaunchKernelGGL(k_select, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, d->O, s1, A, 1);
-    } else if(s1 < A) {
-        // Second stage and the winner pass of the trajectories the first stage settled in ONE launch (ROLL_SECOND);
-        // the grid covers the worst case, blocks beyond the pending count return at once.
-        const int n2 = A - s1;
-        if(repoint(d->P.cand, d->cand, d->cand.reserve((size_t)d->Bp * n2 * (d->N + 1) * CAND_W * sizeof(double), rs))) return 1;
-        launch_rollout(d, ROLL_SECOND, ILQG_K_ROLLOUT_SEARCH2, s1, n2 + 1, rs);
-        {
-            Timed t(d, ILQG_K_SELECT, rs);
-            hipLaunchKernelGGL(k_select, grid1(d->Bp, 256), dim3(256), 0, rs, d->P, d->O, s1, A, 1);
-        }
-        {
-            Timed t(d, ILQG_K_ROLLOUT_WINNER, rs);
-            hipLaunchKernelGGL(k_adopt, dim3(8 * d->cus), dim3(256), 0, rs, d->P, s1, n2);
-        }
-        d->winner_done = true;
-    }
+    if(!parts && search_plain(d, A, s1)) return 1;
     HIP_TRY(hipGetLastError());
     return roll_leave(d);
 }
