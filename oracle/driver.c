@@ -341,6 +341,14 @@ void drv_set_state(drv_t *d, const double *x, const double *u, const double *st)
     d->o.w_pen_f = st[3];
 }
 
+/* what line_search() reads besides the trajectories and gains (line_search.c:42-43): the nominal cost and the two value
+ * changes the backward pass would have left */
+void drv_set_search_state(drv_t *d, double cost, double dV0, double dV1) {
+    d->o.cost = cost;
+    d->o.dV[0] = dV0;
+    d->o.dV[1] = dV1;
+}
+
 void drv_set_multipliers(drv_t *d, const double *el, const double *fin) {
     if(sizeof(multipliersEl_t) > 0) memcpy(d->o.multipliers.t, el, sizeof(multipliersEl_t) * d->n_hor);
     if(sizeof(multipliersFin_t) > 0) memcpy(&d->o.multipliers.f, fin, sizeof(multipliersFin_t));

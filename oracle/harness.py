@@ -187,6 +187,8 @@ def _bind(lib):
     if hasattr(lib, "drv_set_state"):
         lib.drv_set_state.argtypes = [C.c_void_p, _dp, _dp, _dp]
         lib.drv_set_multipliers.argtypes = [C.c_void_p, _dp, _dp]
+    if hasattr(lib, "drv_set_search_state"):
+        lib.drv_set_search_state.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
     if hasattr(lib, "drv_get_step_costs"):
         lib.drv_get_step_costs.argtypes = [C.c_void_p, C.c_int, _dp]
     if hasattr(lib, "drv_solve_many"):
@@ -328,6 +330,10 @@ class Driver:
         """teacher forcing: nominal (x, u), cost, lambda and the penalty weights as another driver has them"""
         st = np.array([cost, lam, w_pen[0], w_pen[1]], dtype=np.float64)
         self.lib.drv_set_state(self.h, np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64), st)
+
+    def set_search_state(self, cost, dV0, dV1):
+        """what line_search() reads besides trajectories and gains: the nominal cost and the backward pass's dV"""
+        self.lib.drv_set_search_state(self.h, float(cost), float(dV0), float(dV1))
 
     def set_multipliers(self, el, fin):
         dims = np.zeros(2, dtype=np.int32)

@@ -486,9 +486,20 @@ def regtype2_case_goldens():
     print("regType 2 cases: %d lines, %d bytes" % (len(R.TABLE), os.path.getsize(R.GOLDEN)))
 
 
+def linesearch_goldens():
+    """tests/linesearch_cases.py: the reference build's roll-outs per step size and its line_search() on every case of that
+    module's batches (index, return value, what the scan leaves behind, the candidate trajectory) — results only"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import linesearch_cases as LS
+    with quiet():
+        out = LS.golden_of("ref")
+    np.savez_compressed(LS.GOLDEN, **out)
+    print("line search cases: %d batches, %d cases, %d bytes" % (len(LS.BATCHES), sum(b[5] for b in LS.BATCHES.values()), os.path.getsize(LS.GOLDEN)))
+
+
 def main(argv):
-    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases synth synthp console
-    vsref"""
+    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases linesearch synth synthp
+    console vsref"""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     groups = {
         "brachi": brachi_goldens,
@@ -499,6 +510,7 @@ def main(argv):
         "hx": lambda: [hx_goldens(fd) for fd in (0, 1)],
         "regtype2": regtype2_goldens,
         "regtype2cases": regtype2_case_goldens,
+        "linesearch": linesearch_goldens,
         "synth": lambda: [synth_goldens(fd) for fd in (0, 1)],
         "synthp": lambda: synth_goldens(1, N=12, problem="synth16p", SYN_PARAMS=SYNP_PARAMS_TIGHT),
         "console": console_goldens,
