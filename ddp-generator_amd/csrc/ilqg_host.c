@@ -85,6 +85,7 @@ struct ilqg_batch {
     int trace_n;                     /* the last solve, poll by poll: iterations done, trajectories active, slots iterated */
     int trace_it[ILQG_TRACE_MAX], trace_active[ILQG_TRACE_MAX], trace_slots[ILQG_TRACE_MAX];
     int compactions;
+    long long stream_counts[4];      /* the last stream of starts: polls, harvest launches, harvested bytes, contexts made */
     double *scratch;                 /* host arrays of the drop-in entry points, kept between calls */
     size_t scratch_doubles;
     char err[512];
@@ -1286,6 +1287,7 @@ static ilqg_batch_t *working_copy(ilqg_batch_t *c, int n) {
     if(getenv("ILQG_COMPACT_GROUPS")) groups = atoi(getenv("ILQG_COMPACT_GROUPS"));
     w = ilqg_batch_create_groups(c->device, n, c->N, groups);
     if(!w) return NULL;
+    c->stream_counts[3] += 1;  /* (every context made on c's behalf is counted here; a stream clears the count when it starts) */
     w->opt = c->opt;
     memcpy(w->alpha_store, c->opt.alpha, sizeof(double) * c->opt.n_alpha);
     w->opt.alpha = w->alpha_store;
@@ -1385,16 +1387,327 @@ int ilqg_batch_solve(ilqg_batch_t *c) {
  * caller wants it) and, once enough are free, refilled: the new starts are initialised in a small staging context
  * (initial roll-out + solver entry state, exactly ilqg_batch_init) and moved into the free slots (ilqg_dev_move).  A
  * trajectory's iterations depend on nothing but its own state, so every start gets the result a plain ilqg_batch_solve
- * of a batch holding it would give, bit for bit (tests/test_gpu_solve.py). */
+ * of a batch holding it would give, bit for bit (tests/test_gpu_solve.py).
+ *
+ * The starts may each bring a row of fixed-size parameters, a window per per-time-step parameter and a history of their own
+ * (ilqg_batch_solve_stream_rows; ilqg_batch_solve_stream is that entry with nothing named — the loop is stated once, in
+ * stream_solve).  The rows reach the staging context through the setters every caller uses (its first m slots the starts'
+ * rows, the others the batch's shared values: lanes of slots that are not live still run the callbacks), ilqg_batch_init
+ * clears its history, and ilqg_dev_move carries all three with the trajectory.  The resident batch gets the same map and a
+ * table of the shared values ONCE, before the first refill: every move is then the move's "same map" case, allocates nothing,
+ * and no slot ever holds zeros.  What has finished comes back through ilqg_dev_harvest: per group and poll one launch and one
+ * copy of exactly what the caller asked for — nothing beyond the status read when nothing finished. */
 #define ILQG_STREAM_ROUND 8
 #define ILQG_STREAM_STAGE 8192
-int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const double *u0, double *cost, int *status,
-                            int *iterations, double *x, double *u) {
-    int dims[8], NXd, NUd, B = c->B, N = c->N, j, rc = 0, next = 0, n_done = 0, it = 0, active = 0, n_free;
-    int *slot = NULL, *st = NULL, *its = NULL, *freel = NULL, *ident = NULL, *fin = NULL;
-    double *cst = NULL, *xs = NULL, *us = NULL, *hx = NULL, *hu = NULL;
+#define STREAM_MAX_HIST 13 /* the names of history_names[] */
+typedef struct {
+    int total;
+    const double *x0, *u0;
+    int n_names;
+    const char *const *names;
+    const double *values;
+    int n_step_names;
+    const char *const *step_names;
+    const double *const *step_values;
+    int hist_cap, n_hist;
+    const char *const *hist_names;
+    void *const *hist_out;
+    double *cost;
+    int *status, *iterations;
+    double *x, *u;
+} stream_t;
+/* what the entry resolves of its names before anything is touched */
+typedef struct {
+    int named[POLICY_MAX_NAMES], W;
+    int step[64];
+    int hist_int[STREAM_MAX_HIST], hist_field[STREAM_MAX_HIST];
+} stream_names_t;
+static int stream_history_name(ilqg_batch_t *c, const char *who, int i, const char *name, const void *out, int *is_int, int *field);
+
+/* every refusal of ilqg_batch_solve_stream_rows, in the order of include/ilqg_batch.h; touches nothing */
+static int stream_refused(ilqg_batch_t *c, const char *who, const stream_t *a, stream_names_t *r) {
+    int i, j;
+    if(a->total < 1) {
+        snprintf(c->err, sizeof(c->err), "%s: total = %d, must be at least 1 (the number of starts)", who, a->total);
+        return 1;
+    }
+    if(!a->x0 || !a->u0) {
+        snprintf(c->err, sizeof(c->err), "%s: %s is NULL (the starts, %s)", who, !a->x0 ? "x0" : "u0", !a->x0 ? "[total][N_X]" : "[total][n_hor][N_U]");
+        return 1;
+    }
+    if(c->pb_n > 0) {
+        snprintf(c->err, sizeof(c->err), "%s: c: the batch already has per-trajectory parameters (ilqg_batch_set_params_batch), which belong to its "
+                 "slots, while the starts of a stream pass through them.  Pass the starts' rows to this call (names, values) and clear the "
+                 "set first: ilqg_batch_set_params_batch(c, 0, NULL, NULL)", who);
+        return 1;
+    }
+    for(i = 0; i < n_params && i < 64; i++)
+        if(c->ps_on[i]) {
+            snprintf(c->err, sizeof(c->err), "%s: c: the batch already has per-trajectory windows of per-time-step parameter '%s' "
+                     "(ilqg_batch_set_param_steps_batch), which belong to its slots, while the starts of a stream pass through them.  Pass the "
+                     "starts' windows to this call (step_names, step_values) and make the name shared again first: "
+                     "ilqg_batch_set_param_steps_batch(c, name, values = NULL)", who, paramdesc[i]->name);
+            return 1;
+        }
+    if(c->hist_cap > 0) {
+        snprintf(c->err, sizeof(c->err), "%s: c: the batch already records an iteration history (ilqg_batch_set_history), which belongs to its "
+                 "slots, while the starts of a stream pass through them.  Pass the capacity to this call (hist_cap) and switch the batch's "
+                 "off first: ilqg_batch_set_history(c, 0)", who);
+        return 1;
+    }
+    if((a->n_names != 0 || a->n_step_names != 0) && wave_mapped(c, who)) return 1;
+    if(a->n_names < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: n_names = %d, must not be negative (0: no parameter rows)", who, a->n_names);
+        return 1;
+    }
+    if(a->n_names > 0 && !a->names) {
+        snprintf(c->err, sizeof(c->err), "%s: names is NULL (n_names parameter names)", who);
+        return 1;
+    }
+    if(a->n_names > 0 && !a->values) {
+        snprintf(c->err, sizeof(c->err), "%s: values is NULL (the parameter rows, [total][W])", who);
+        return 1;
+    }
+    r->W = 0;
+    if(a->n_names > 0 && policy_names(c, who, a->n_names, a->names, a->values, r->named, &r->W)) return 1;
+    if(a->n_step_names < 0 || a->n_step_names > 64) {
+        snprintf(c->err, sizeof(c->err), "%s: n_step_names = %d, must be in 0 .. 64 (0: no windows per start)", who, a->n_step_names);
+        return 1;
+    }
+    if(a->n_step_names > 0 && (!a->step_names || !a->step_values)) {
+        snprintf(c->err, sizeof(c->err), "%s: %s is NULL (n_step_names %s)", who, !a->step_names ? "step_names" : "step_values",
+                 !a->step_names ? "names of per-time-step parameters" : "tables, each [total][n_hor+1]");
+        return 1;
+    }
+    for(i = 0; i < a->n_step_names; i++) {
+        char at[96];
+        snprintf(at, sizeof(at), "%s: step_names[%d]", who, i);
+        if(step_name(c, at, a->step_names[i], 0, &r->step[i])) return 1;
+        for(j = 0; j < i; j++)
+            if(r->step[j] == r->step[i]) {
+                snprintf(c->err, sizeof(c->err), "%s: parameter '%s' is named twice (a duplicate of step_names[%d])", at, a->step_names[i], j);
+                return 1;
+            }
+        if(!a->step_values[i]) {
+            snprintf(c->err, sizeof(c->err), "%s: step_values[%d] is NULL (the windows of parameter '%s', [total][n_hor+1])", who, i, a->step_names[i]);
+            return 1;
+        }
+    }
+    if(a->hist_cap < 0) {
+        snprintf(c->err, sizeof(c->err), "%s: hist_cap = %d, must not be negative (hist_cap > 0: that many entries per start, 0: no history)", who,
+                 a->hist_cap);
+        return 1;
+    }
+    if(a->n_hist < 0 || a->n_hist > STREAM_MAX_HIST) {
+        snprintf(c->err, sizeof(c->err), "%s: n_hist = %d, must be in 0 .. %d (the history has that many names)", who, a->n_hist, STREAM_MAX_HIST);
+        return 1;
+    }
+    if(a->n_hist > 0 && a->hist_cap == 0) {
+        snprintf(c->err, sizeof(c->err), "%s: n_hist = %d with hist_cap = 0: history fields are asked for, but no history is recorded; give the "
+                 "capacity in hist_cap", who, a->n_hist);
+        return 1;
+    }
+    if(a->n_hist > 0 && (!a->hist_names || !a->hist_out)) {
+        snprintf(c->err, sizeof(c->err), "%s: %s is NULL (n_hist %s)", who, !a->hist_names ? "hist_names" : "hist_out",
+                 !a->hist_names ? "names of history fields" : "arrays, one per name");
+        return 1;
+    }
+    for(i = 0; i < a->n_hist; i++)
+        if(stream_history_name(c, who, i, a->hist_names[i], a->hist_out[i], &r->hist_int[i], &r->hist_field[i])) return 1;
+    return 0;
+}
+
+/* the finished slots fin[0..m) of c (ascending) come back: per group one ilqg_dev_harvest, unpacked into the caller's arrays
+ * at the starts slot[] says they hold.  (ilqg_dev_harvest queues, ilqg_dev_harvest_wait waits: the record's layout, words and
+ * off[], is the same for every group of a poll.) */
+static int stream_harvest(ilqg_batch_t *c, const stream_t *a, const stream_names_t *r, int m, const int *fin, const int *slot, int *local,
+                          int NXd, int NUd) {
+    const ilqg_dev_harvest_t what = {a->x != NULL, a->u != NULL, a->n_hist, r->hist_int, r->hist_field};
+    const size_t nx = (size_t)(c->N + 1) * NXd, nu = (size_t)c->N * NUd, cap = (size_t)a->hist_cap;
+    int g, j, i, j0 = 0, words = 0, off[2 + STREAM_MAX_HIST], first[ILQG_MAX_GROUPS + 1];
+    /* every group's launch and copy are queued before any is waited for: the groups' harvests of a poll overlap */
+    EACH_GROUP(g) {
+        int n = 0;
+        first[g] = j0;
+        while(j0 + n < m && group_of(c, fin[j0 + n]) == g) {
+            local[n] = fin[j0 + n] - c->first[g];
+            n++;
+        }
+        j0 += n;
+        if(!n) continue;
+        if(ilqg_dev_harvest(c->dev[g], n, local, &what, &words, off)) return fail(c, "harvesting finished trajectories");
+        c->stream_counts[1] += 1;
+        c->stream_counts[2] += (long long)n * words * 8;
+    }
+    first[c->groups] = j0;
+    EACH_GROUP(g) {
+        const void *records = NULL;
+        const int n = first[g + 1] - first[g];
+        if(!n) continue;
+        j0 = first[g];
+        if(ilqg_dev_harvest_wait(c->dev[g], &records)) return fail(c, "harvesting finished trajectories");
+        for(j = 0; j < n; j++) {
+            const unsigned long long *rec = (const unsigned long long *)records + (size_t)j * words;
+            const int *ri = (const int *)(rec + 1);
+            const size_t s0 = (size_t)slot[fin[j0 + j]];
+            if(a->cost) memcpy(a->cost + s0, rec, sizeof(double));
+            if(a->status) a->status[s0] = ri[0];
+            if(a->iterations) a->iterations[s0] = ri[1];
+            if(a->x) memcpy(a->x + s0 * nx, rec + off[0], sizeof(double) * nx);
+            if(a->u) memcpy(a->u + s0 * nu, rec + off[1], sizeof(double) * nu);
+            for(i = 0; i < a->n_hist; i++) {
+                if(!r->hist_int[i]) memcpy((double *)a->hist_out[i] + s0 * cap, rec + off[2 + i], sizeof(double) * cap);
+                else if(r->hist_field[i] == ILQG_HI_N) memcpy((int *)a->hist_out[i] + s0, rec + off[2 + i], sizeof(int));
+                else memcpy((int *)a->hist_out[i] + s0 * cap, rec + off[2 + i], sizeof(int) * cap);
+            }
+        }
+    }
+    return 0;
+}
+
+/* rows [rows][w]: the first m from the caller's table at start `next`, the others the shared value(s) `nominal` [w] */
+static void stream_rows(double *rows, int n_rows, size_t w, const double *table, int next, int m, const double *nominal) {
+    int j;
+    if(m > 0) memcpy(rows, table + (size_t)next * w, sizeof(double) * (size_t)m * w);
+    for(j = m; j < n_rows; j++) memcpy(rows + (size_t)j * w, nominal, sizeof(double) * w);
+}
+
+static int stream_solve(ilqg_batch_t *c, const stream_t *a, const stream_names_t *r) {
+    int dims[8], NXd, NUd, B = c->B, N = c->N, j, i, rc = 0, next = 0, n_done = 0, it = 0, active = 0, n_free, total = a->total;
+    int *slot = NULL, *st = NULL, *freel = NULL, *ident = NULL, *fin = NULL, *local = NULL;
+    double *xs = NULL, *us = NULL, *prow = NULL, *srow = NULL, *pnom = NULL;
+    int set_rows = 0, set_steps = 0, set_hist = 0;
+    char err[sizeof(c->err)];
     ilqg_batch_t *stage = NULL;
     const int S = B < ILQG_STREAM_STAGE ? B : ILQG_STREAM_STAGE;
+    const size_t W = (size_t)r->W, n1 = (size_t)N + 1;
+    if(push_config(c)) return 1;
+    ilqg_dev_dims(dims);
+    NXd = dims[0];
+    NUd = dims[1];
+    memset(c->stream_counts, 0, sizeof(c->stream_counts));
+    slot = (int *)malloc(sizeof(int) * B); st = (int *)malloc(sizeof(int) * B); local = (int *)malloc(sizeof(int) * B);
+    freel = (int *)malloc(sizeof(int) * B); ident = (int *)malloc(sizeof(int) * B); fin = (int *)malloc(sizeof(int) * B);
+    xs = (double *)calloc((size_t)S * NXd, sizeof(double));
+    us = (double *)calloc((size_t)S * N * NUd, sizeof(double));
+    if(a->n_names > 0) {  /* the named parameters' shared values, one row; the tables of the staging context and, once, of c */
+        size_t col = 0;
+        pnom = (double *)malloc(sizeof(double) * W);
+        prow = (double *)malloc(sizeof(double) * (size_t)B * W);
+        for(i = 0; i < a->n_names; i++) {
+            memcpy(pnom + col, c->p[r->named[i]], sizeof(double) * (size_t)paramdesc[r->named[i]]->size);
+            col += (size_t)paramdesc[r->named[i]]->size;
+        }
+    }
+    if(a->n_step_names > 0) srow = (double *)malloc(sizeof(double) * (size_t)B * n1);
+    for(j = 0; j < B; j++) { slot[j] = -1; st[j] = ILQG_ST_MAX_ITER; ident[j] = j; }
+    /* the batch's history first: a capacity the device has no memory for fails here, with c's trajectories still what they were */
+    if(a->hist_cap > 0) {
+        set_hist = 1;
+        if(ilqg_batch_set_history(c, a->hist_cap)) { rc = 1; goto done; }
+    }
+    /* every slot is free and says so to the kernels */
+    if(each_write_int(c, ILQG_I_STATUS, st, "status")) { rc = 1; goto done; }
+    stage = working_copy(c, S);
+    if(!stage) { rc = 1; goto done; }
+    c->trace_n = 0;
+    c->compactions = 0;
+    /* c takes the map and the shared values in every row before any start moves in (its history's capacity it has) */
+    if(a->n_names > 0) {
+        stream_rows(prow, B, W, a->values, 0, 0, pnom);
+        set_rows = 1;
+        if(ilqg_batch_set_params_batch(c, a->n_names, a->names, prow)) { rc = 1; goto done; }
+    }
+    for(i = 0; i < a->n_step_names; i++) {
+        stream_rows(srow, B, n1, a->step_values[i], 0, 0, c->p[r->step[i]]);
+        set_steps = i + 1;
+        if(ilqg_batch_set_param_steps_batch(c, a->step_names[i], srow)) { rc = 1; goto done; }
+    }
+    if(a->hist_cap > 0) {
+        if(ilqg_batch_set_history(stage, a->hist_cap)) { snprintf(c->err, sizeof(c->err), "%s", stage->err); rc = 1; goto done; }
+    }
+    for(;;) {
+        /* harvest what has finished */
+        int m = 0;
+        if(each_read_int(c, ILQG_I_STATUS, st, "status")) { rc = 1; break; }
+        c->stream_counts[0] += 1;
+        active = 0;
+        for(j = 0; j < B; j++) {
+            if(slot[j] < 0) continue;
+            if(st[j] == ILQG_ST_ACTIVE) active++;
+            else fin[m++] = j;
+        }
+        if(m) {
+            if(stream_harvest(c, a, r, m, fin, slot, local, NXd, NUd)) { rc = 1; break; }
+            for(j = 0; j < m; j++) slot[fin[j]] = -1;
+            n_done += m;
+        }
+        if(c->trace_n < ILQG_TRACE_MAX) {
+            c->trace_it[c->trace_n] = it;
+            c->trace_active[c->trace_n] = active;
+            c->trace_slots[c->trace_n] = B;
+            c->trace_n++;
+        }
+        if(n_done >= total) break;
+        /* refill: once a sixteenth of the slots is free, or nothing is left to iterate */
+        n_free = 0;
+        for(j = 0; j < B; j++)
+            if(slot[j] < 0) freel[n_free++] = j;
+        while(next < total && n_free > 0 && (n_free >= B / 16 || active == 0 || total - next <= n_free)) {
+            int ok;
+            m = n_free < S ? n_free : S;
+            if(m > total - next) m = total - next;
+            memcpy(xs, a->x0 + (size_t)next * NXd, sizeof(double) * (size_t)m * NXd);
+            memcpy(us, a->u0 + (size_t)next * N * NUd, sizeof(double) * (size_t)m * N * NUd);
+            ok = 1;
+            if(a->n_names > 0) {
+                stream_rows(prow, S, W, a->values, next, m, pnom);
+                ok = !ilqg_batch_set_params_batch(stage, a->n_names, a->names, prow);
+            }
+            for(i = 0; ok && i < a->n_step_names; i++) {
+                stream_rows(srow, S, n1, a->step_values[i], next, m, c->p[r->step[i]]);
+                ok = !ilqg_batch_set_param_steps_batch(stage, a->step_names[i], srow);
+            }
+            if(!ok || ilqg_batch_set_x0(stage, xs) || ilqg_batch_set_u(stage, us) || ilqg_batch_init(stage)) { snprintf(c->err, sizeof(c->err), "%s", stage->err); rc = 1; break; }
+            if(move_between(c, stage, m, freel + (n_free - m), ident)) { rc = 1; break; }
+            for(j = 0; j < m; j++) slot[freel[n_free - m + j]] = next + j;
+            next += m;
+            n_free -= m;
+            active += m;  /* (those whose initial roll-out failed are harvested at the next poll) */
+            c->compactions++;
+        }
+        if(rc) break;
+        if(iterate_groups(c, ILQG_STREAM_ROUND)) { rc = 1; break; }
+        it += ILQG_STREAM_ROUND;
+    }
+done:
+    /* c is again what it was on entry: no set, no rows, no history; a failure of the solve keeps its text */
+    memcpy(err, c->err, sizeof(err));
+    if(set_rows && ilqg_batch_set_params_batch(c, 0, NULL, NULL) && !rc) { rc = 1; memcpy(err, c->err, sizeof(err)); }
+    for(i = 0; i < set_steps; i++)
+        if(ilqg_batch_set_param_steps_batch(c, a->step_names[i], NULL) && !rc) { rc = 1; memcpy(err, c->err, sizeof(err)); }
+    if(set_hist && ilqg_batch_set_history(c, 0) && !rc) { rc = 1; memcpy(err, c->err, sizeof(err)); }
+    memcpy(c->err, err, sizeof(err));
+    if(stage) ilqg_batch_destroy(stage);
+    free(slot); free(st); free(local); free(freel); free(ident); free(fin); free(xs); free(us); free(prow); free(srow); free(pnom);
+    return rc;
+}
+
+int ilqg_batch_solve_stream_rows(ilqg_batch_t *c, int total, const double *x0, const double *u0, int n_names, const char *const *names,
+                                 const double *values, int n_step_names, const char *const *step_names, const double *const *step_values,
+                                 int hist_cap, int n_hist, const char *const *hist_names, void *const *hist_out, double *cost, int *status,
+                                 int *iterations, double *x, double *u) {
+    const stream_t a = {total, x0, u0, n_names, names, values, n_step_names, step_names, step_values, hist_cap, n_hist, hist_names, hist_out,
+                        cost, status, iterations, x, u};
+    stream_names_t r;
+    if(!c) return 1;
+    memset(&r, 0, sizeof(r));
+    if(stream_refused(c, "ilqg_batch_solve_stream_rows", &a, &r)) return 1;
+    return stream_solve(c, &a, &r);
+}
+
+int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const double *u0, double *cost, int *status,
+                            int *iterations, double *x, double *u) {
     if(total < 1) return fail_msg(c, "ilqg_batch_solve_stream: no starts");
     if(c->pb_n > 0)
         return fail_msg(c, "ilqg_batch_solve_stream: the batch has per-trajectory parameters (ilqg_batch_set_params_batch), which belong to "
@@ -1413,89 +1726,12 @@ int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const 
         return fail_msg(c, "ilqg_batch_solve_stream: the batch records an iteration history (ilqg_batch_set_history), which belongs to its "
                            "slots, while the starts of a stream pass through them: a history per start is not supported.  Switch it off "
                            "first: ilqg_batch_set_history(c, 0)");
-    if(push_config(c)) return 1;
-    ilqg_dev_dims(dims);
-    NXd = dims[0];
-    NUd = dims[1];
-    slot = (int *)malloc(sizeof(int) * B); st = (int *)malloc(sizeof(int) * B); its = (int *)malloc(sizeof(int) * B);
-    freel = (int *)malloc(sizeof(int) * B); ident = (int *)malloc(sizeof(int) * B); fin = (int *)malloc(sizeof(int) * B);
-    cst = (double *)malloc(sizeof(double) * B);
-    xs = (double *)calloc((size_t)S * NXd, sizeof(double));
-    us = (double *)calloc((size_t)S * N * NUd, sizeof(double));
-    for(j = 0; j < B; j++) { slot[j] = -1; st[j] = ILQG_ST_MAX_ITER; ident[j] = j; }
-    /* every slot is free and says so to the kernels */
-    if(each_write_int(c, ILQG_I_STATUS, st, "status")) { rc = 1; goto done; }
-    stage = working_copy(c, S);
-    if(!stage) { rc = 1; goto done; }
-    c->trace_n = 0;
-    c->compactions = 0;
-    for(;;) {
-        /* harvest what has finished */
-        if(each_read_int(c, ILQG_I_STATUS, st, "status")) { rc = 1; break; }
-        {
-            int m = 0;
-            active = 0;
-            for(j = 0; j < B; j++) {
-                if(slot[j] < 0) continue;
-                if(st[j] == ILQG_ST_ACTIVE) active++;
-                else fin[m++] = j;
-            }
-            if(m) {
-                if(each_read(c, ILQG_F_COST, cst, "cost") || each_read_int(c, ILQG_I_ITER, its, "iterations")) { rc = 1; break; }
-                if(x || u) {  /* the finished trajectories, through a context of their own */
-                    ilqg_batch_t *h = working_copy(c, m);
-                    if(!h) { rc = 1; break; }
-                    if(move_between(h, c, m, ident, fin)) { ilqg_batch_destroy(h); rc = 1; break; }
-                    hx = (double *)realloc(hx, sizeof(double) * (size_t)m * (N + 1) * NXd);
-                    hu = (double *)realloc(hu, sizeof(double) * (size_t)m * N * NUd);
-                    if((x && ilqg_batch_get_x(h, hx)) || (u && ilqg_batch_get_u(h, hu))) { snprintf(c->err, sizeof(c->err), "%s", h->err); ilqg_batch_destroy(h); rc = 1; break; }
-                    ilqg_batch_destroy(h);
-                }
-                for(j = 0; j < m; j++) {
-                    const int b = fin[j], s0 = slot[b];
-                    if(cost) cost[s0] = cst[b];
-                    if(status) status[s0] = st[b];
-                    if(iterations) iterations[s0] = its[b];
-                    if(x) memcpy(x + (size_t)s0 * (N + 1) * NXd, hx + (size_t)j * (N + 1) * NXd, sizeof(double) * (N + 1) * NXd);
-                    if(u) memcpy(u + (size_t)s0 * N * NUd, hu + (size_t)j * N * NUd, sizeof(double) * N * NUd);
-                    slot[b] = -1;
-                }
-                n_done += m;
-            }
-        }
-        if(c->trace_n < ILQG_TRACE_MAX) {
-            c->trace_it[c->trace_n] = it;
-            c->trace_active[c->trace_n] = active;
-            c->trace_slots[c->trace_n] = B;
-            c->trace_n++;
-        }
-        if(n_done >= total) break;
-        /* refill: once a sixteenth of the slots is free, or nothing is left to iterate */
-        n_free = 0;
-        for(j = 0; j < B; j++)
-            if(slot[j] < 0) freel[n_free++] = j;
-        while(next < total && n_free > 0 && (n_free >= B / 16 || active == 0 || total - next <= n_free)) {
-            int m = n_free < S ? n_free : S;
-            if(m > total - next) m = total - next;
-            memcpy(xs, x0 + (size_t)next * NXd, sizeof(double) * (size_t)m * NXd);
-            memcpy(us, u0 + (size_t)next * N * NUd, sizeof(double) * (size_t)m * N * NUd);
-            if(ilqg_batch_set_x0(stage, xs) || ilqg_batch_set_u(stage, us) || ilqg_batch_init(stage)) { snprintf(c->err, sizeof(c->err), "%s", stage->err); rc = 1; break; }
-            if(move_between(c, stage, m, freel + (n_free - m), ident)) { rc = 1; break; }
-            for(j = 0; j < m; j++) slot[freel[n_free - m + j]] = next + j;
-            next += m;
-            n_free -= m;
-            active += m;  /* (those whose initial roll-out failed are harvested at the next poll) */
-            c->compactions++;
-        }
-        if(rc) break;
-        if(iterate_groups(c, ILQG_STREAM_ROUND)) { rc = 1; break; }
-        it += ILQG_STREAM_ROUND;
-    }
-done:
-    if(stage) ilqg_batch_destroy(stage);
-    free(slot); free(st); free(its); free(freel); free(ident); free(fin); free(cst); free(xs); free(us); free(hx); free(hu);
-    return rc;
+    return ilqg_batch_solve_stream_rows(c, total, x0, u0, 0, NULL, NULL, 0, NULL, NULL, 0, 0, NULL, NULL, cost, status, iterations, x, u);
 }
+
+/* the last stream, counted: out[0] polls (status reads), out[1] harvest launches, out[2] bytes the harvests copied to the host,
+ * out[3] contexts made (counted in working_copy, the one place that makes them: the staging context and nothing else) */
+void ilqg_batch_stream_counts(const ilqg_batch_t *c, long long *out) { memcpy(out, c->stream_counts, sizeof(c->stream_counts)); }
 
 /* the last ilqg_batch_solve, poll by poll (every 4 iterations): iterations done so far, trajectories still active, slots the
  * iterations ran over (the batch, or the smaller context the live trajectories had been gathered into); returns the number
@@ -1653,6 +1889,32 @@ static int history_field(ilqg_batch_t *c, const char *who, const char *name, int
 }
 
 int ilqg_batch_history_cap(const ilqg_batch_t *c) { return c->hist_cap; }
+
+/* hist_names[i] / hist_out[i] of ilqg_batch_solve_stream_rows against the same table: 0 with the field and its kind, or refused */
+static int stream_history_name(ilqg_batch_t *c, const char *who, int i, const char *name, const void *out, int *is_int, int *field) {
+    size_t k;
+    int dims[2];
+    for(k = 0; name && k < sizeof(history_names) / sizeof(history_names[0]); k++) {
+        if(strcmp(history_names[k].name, name) != 0) continue;
+        ilqg_dev_multiplier_dims(dims);
+        if(!history_names[k].is_int && history_names[k].field >= ILQG_H_WPEN_L && dims[0] + dims[1] == 0) {
+            snprintf(c->err, sizeof(c->err), "%s: hist_names[%d]: '%s' is recorded in libraries of problems with multipliers only; this problem has none",
+                     who, i, name);
+            return 1;
+        }
+        if(!out) {
+            snprintf(c->err, sizeof(c->err), "%s: hist_out[%d] is NULL (the array of '%s', %s)", who, i, name,
+                     history_names[k].field == ILQG_HI_N && history_names[k].is_int ? "int [total]" : history_names[k].is_int ? "int [total][hist_cap]" : "double [total][hist_cap]");
+            return 1;
+        }
+        *is_int = history_names[k].is_int;
+        *field = history_names[k].field;
+        return 0;
+    }
+    snprintf(c->err, sizeof(c->err), "%s: hist_names[%d]: no such history field '%s' (cost new_cost z lambda g_norm dV0 dV1 w_pen_l w_pen_f; ints: "
+                                     "alpha_idx bp_calls iterations n)", who, i, name ? name : "(NULL)");
+    return 1;
+}
 
 /* every group's buffers are made before any group changes: a capacity that does not fit leaves the history as it was */
 int ilqg_batch_set_history(ilqg_batch_t *c, int cap) {

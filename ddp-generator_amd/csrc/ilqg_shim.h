@@ -343,6 +343,22 @@ int ilqg_dev_count_active(ilqg_dev_t *d, int *n_active); /* synchronises */
  * x / u (they arrive in dst's arrays X / U), records, scalars, integers, multipliers; with_records: also the stored
  * derivative records (contexts iterated with fuse_derivs = 0).  Synchronises both contexts. */
 int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, const int *from, int with_records);
+/* What a stream of starts reads of its finished trajectories, without reading the batch: of trajectories from[0..count) the
+ * cost, status and iteration count, with x / u != 0 the current trajectory (read where it lives, as ilqg_dev_head reads it), and
+ * the n_hist history fields hist_field[i] — with hist_int[i] = 0 a double field, else an int field or ILQG_HI_N — are gathered
+ * into one packed buffer of the context, which only grows, by ONE launch (k_harvest) and copied to pinned host memory by ONE
+ * copy.  ilqg_dev_harvest queues all of it on the context's stream and returns (`from` is read before it does);
+ * ilqg_dev_harvest_wait waits for that stream.  *records: that memory, valid until the context's next harvest; count records of *words 8-byte words each,
+ * start-major: word 0 the cost, word 1 the ints { status, iterations }, from word offsets[0] x [n_hor+1][N_X], from word
+ * offsets[1] u [n_hor][N_U] (-1: not asked for), from word offsets[2 + i] history field i: cap doubles, or cap ints two to a
+ * word, or the count alone — min(n, cap) entries, zeros behind them.  Refused before anything is queued: an index out of range,
+ * history fields of a context without a history, a field the library does not record.  Timed under ILQG_K_TRANSPOSE. */
+typedef struct {
+    int x, u, n_hist;
+    const int *hist_int, *hist_field;
+} ilqg_dev_harvest_t;
+int ilqg_dev_harvest(ilqg_dev_t *d, int count, const int *from, const ilqg_dev_harvest_t *what, int *words, int *offsets);
+int ilqg_dev_harvest_wait(ilqg_dev_t *d, const void **records);
 
 /* builds with -DILQG_PROFILE_SECTIONS: cycles per section of the fused backward step, summed over wavefronts */
 int ilqg_dev_section_cycles(unsigned long long *out8);

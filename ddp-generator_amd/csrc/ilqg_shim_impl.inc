@@ -144,6 +144,8 @@ struct DevBuffers {
     Buffer<int> hist_i;
     Buffer<double> hist_next_d;            //   ... and those of the capacity it is about to take (ilqg_dev_reserve_history)
     Buffer<int> hist_next_i;
+    Buffer<unsigned long long> harvest;    // the packed records of ilqg_dev_harvest, and their copy on the host; both only grow
+    Buffer<char, PinnedMem> harvest_host;
     Buffer<double> staging;                // see io_deferred
     Buffer<char, PinnedMem> pinned;
 };
@@ -2191,6 +2193,7 @@ int ilqg_dev_search(ilqg_dev_t *d) {
 // the two launches of the iteration history, defined at the end of this file (see k_history in k_common.inc for why there)
 static void launch_history(ilqg_dev_t *d, hipStream_t stream);
 static void launch_move_history(ilqg_dev_t *dst, ilqg_dev_t *src, const int *to, const int *from, int count);
+static void launch_harvest(ilqg_dev_t *d, const HarvestPlan &plan, const int *from);
 
 int ilqg_dev_winner(ilqg_dev_t *d) {
     NEED_PARAMS(d);
@@ -2308,6 +2311,75 @@ int ilqg_dev_move(ilqg_dev_t *dst, ilqg_dev_t *src, int count, const int *to, co
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
+// A stream of starts brings its finished trajectories back (ilqg_host.c stream_solve): what `what` asks for of trajectories
+// from[0..count) is gathered into the context's packed buffer by ONE launch (k_harvest, which states the record's layout) and
+// reaches pinned host memory by ONE copy.  Everything is checked before anything is queued; ilqg_dev_harvest queues and
+// returns, ilqg_dev_harvest_wait waits for the context's stream and hands the records out — a caller with several contexts
+// queues on all of them before it waits for any.
+int ilqg_dev_harvest(ilqg_dev_t *d, int count, const int *from, const ilqg_dev_harvest_t *what, int *words, int *offsets) {
+    if(count < 1) return 0;
+    HIP_TRY(hipSetDevice(d->device));
+    if(!from || !what || !words || !offsets) {
+        g_err = "ilqg_dev_harvest: from, what, words or offsets is NULL";
+        return 1;
+    }
+    for(int j = 0; j < count; j++)
+        if(from[j] < 0 || from[j] >= d->B) {
+            g_err = "ilqg_dev_harvest: trajectory index out of range";
+            return 1;
+        }
+    if(what->n_hist < 0 || what->n_hist > HARVEST_FIELDS || (what->n_hist > 0 && (!what->hist_int || !what->hist_field))) {
+        g_err = "ilqg_dev_harvest: n_hist = " + std::to_string(what->n_hist) + ", must be 0 .. " + std::to_string(HARVEST_FIELDS) + " fields, each with its kind and index";
+        return 1;
+    }
+    if(what->n_hist > 0 && d->hist.cap == 0) {
+        g_err = "ilqg_dev_harvest: the context has no history (ilqg_dev_set_history with cap > 0 switches one on)";
+        return 1;
+    }
+    HarvestPlan plan = {};
+    plan.count = count, plan.n_hist = what->n_hist;
+    int w = 2;
+    plan.ox = what->x ? w : -1;
+    w += what->x ? (d->N + 1) * NX : 0;
+    plan.ou = what->u ? w : -1;
+    w += what->u ? d->N * NU : 0;
+    offsets[0] = plan.ox, offsets[1] = plan.ou;
+    for(int i = 0; i < what->n_hist; i++) {
+        const int f = what->hist_field[i], is_int = what->hist_int[i];
+        if(is_int ? (f != ILQG_HI_N && (f < 0 || f >= ILQG_HI_COUNT)) : (f < 0 || f >= HIST_DOUBLES)) {
+            g_err = "ilqg_dev_harvest: no such history field (w_pen_l / w_pen_f are recorded in libraries of problems with multipliers only)";
+            return 1;
+        }
+        plan.kind[i] = !is_int ? HARVEST_DOUBLE : f == ILQG_HI_N ? HARVEST_N : HARVEST_INT;
+        plan.field[i] = f == ILQG_HI_N ? 0 : f;
+        plan.off[i] = offsets[2 + i] = w;
+        w += !is_int ? d->hist.cap : f == ILQG_HI_N ? 1 : (d->hist.cap + 1) / 2;
+    }
+    for(int i = what->n_hist; i <= HARVEST_FIELDS; i++) plan.off[i] = w;
+    plan.W = *words = w;
+    const size_t bytes = (size_t)count * w * sizeof(unsigned long long), index_bytes = (size_t)count * sizeof(int);
+    if(io_flush(d)) return 1;
+    if(d->harvest.reserve(bytes + index_bytes, d->stream) || d->harvest_host.reserve(bytes, d->stream)) return 1;
+    int *idx = reinterpret_cast<int *>(d->harvest.get() + (size_t)count * w);  // (behind the records: 8-byte aligned)
+    // (the list goes up from the pinned buffer, which the records overwrite behind the kernel in stream order: `from` is the
+    // caller's again when this returns)
+    memcpy(d->harvest_host.get(), from, index_bytes);
+    HIP_TRY(hipMemcpyAsync(idx, d->harvest_host.get(), index_bytes, hipMemcpyHostToDevice, d->stream));
+    {
+        Timed t(d, ILQG_K_TRANSPOSE);
+        launch_harvest(d, plan, idx);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d->harvest_host.get(), d->harvest.get(), bytes, hipMemcpyDeviceToHost, d->stream));
+    return 0;
+}
+int ilqg_dev_harvest_wait(ilqg_dev_t *d, const void **records) {
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    *records = d->harvest_host.get();
     return 0;
 }
 
@@ -2572,6 +2644,11 @@ static void launch_history(ilqg_dev_t *d, hipStream_t stream) {
 }
 static void launch_move_history(ilqg_dev_t *dst, ilqg_dev_t *src, const int *to, const int *from, int count) {
     hipLaunchKernelGGL(k_move_history<>, grid1((size_t)count * dst->hist.cap, 256), dim3(256), 0, dst->stream, dst->hist, src->hist, to, from, count);
+}
+// ... and of k_harvest, behind them for the same reason.  Grid: x = blocks of HARVEST_WAVES entries, y = blocks of 64 words.
+static void launch_harvest(ilqg_dev_t *d, const HarvestPlan &plan, const int *from) {
+    hipLaunchKernelGGL(k_harvest<>, dim3((unsigned)((plan.count + HARVEST_WAVES - 1) / HARVEST_WAVES), (unsigned)((plan.W + WAVE - 1) / WAVE)),
+                       dim3(WAVE * HARVEST_WAVES), 0, d->stream, d->P, d->hist, plan, from, d->harvest.get());
 }
 
 // rows: 0 box_qp (one problem per lane), 1 the cooperative form of the wave mapping (one per wavefront), 2 box_qp with the

@@ -414,6 +414,69 @@ __global__ void k_move_history(Hist D, Hist S, const int *to, const int *from, i
     for(int f = 0; f < ILQG_HI_COUNT; f++) D.ints()[D.at(f, e, bd)] = held ? S.ints()[S.at(f, e, bs)] : 0;
 }
 
+// The harvest of a stream of starts (ilqg_dev_harvest; ilqg_host.c stream_solve): what the caller wants of the finished
+// trajectories from[0..count) leaves the solver's layouts for ONE packed buffer, a record of W 8-byte words per entry behind
+// each other (start-major), so that a poll costs one launch and one copy to the host whatever it asks for.  A record:
+//   word 0 the cost, word 1 the ints { status, iterations };
+//   words [ox, ox + (N + 1) NX) the current x [N + 1][NX], words [ou, ou + N NU) the current u [N][NU] (each only if asked
+//   for: o* < 0 = left out), read where the trajectory lives — cur_x / cur_u as in k_head and k_move_traj: the tiled X / U or a
+//   kept plane by the location index in the lane mapping, the packed records in the wave mapping;
+//   per requested history field i the words [off[i], off[i + 1]): a double field's cap entries, an int field's cap entries two
+//   to a word, or the count n alone in a word — min(n, cap) entries as recorded, zero behind them (the rule of k_move_history).
+// Thread-to-element map: a wavefront takes 64 consecutive WORDS of one record, so every store instruction of it writes 512
+// contiguous bytes, whole lines.  The reads are the gather: x, u and the history are laid out along the trajectory, one
+// wavefront's words of them are 64 different lines, 8 useful bytes each: a load instruction fetches 64 lines for 512 bytes.
+// That price is paid as it stands (measured 0.025 ms for 4.5 MB of whole trajectories, about 180 GB/s): a transposing form needs
+// LDS, for a kernel that moves a few kilobytes per finished start once every eight iterations.  (The four wavefronts of a
+// workgroup take the SAME words of four consecutive entries of the ascending list, so neighbouring slots that finished in the
+// same poll share lines; with CarParking's spread of iteration counts they mostly are no neighbours, and nothing relies on
+// it.)  No arithmetic, no LDS, no scratch: the plan's arrays are indexed by unrolled constants only.
+// A template for the reason k_history is one: it is emitted where the shim first uses it (launch_harvest).
+constexpr int HARVEST_FIELDS = ILQG_H_COUNT + ILQG_HI_COUNT + 1;
+enum { HARVEST_DOUBLE = 0, HARVEST_INT = 1, HARVEST_N = 2 };
+struct HarvestPlan {
+    int count, W, ox, ou, n_hist;
+    int off[HARVEST_FIELDS + 1], kind[HARVEST_FIELDS], field[HARVEST_FIELDS];
+};
+constexpr int HARVEST_WAVES = 4;
+template <class Hist = History>
+__global__ void __launch_bounds__(WAVE * HARVEST_WAVES) k_harvest(DevPtrs P, Hist H, HarvestPlan A, const int *__restrict__ from,
+                                                                  unsigned long long *__restrict__ out) {
+    const int j = (int)blockIdx.x * HARVEST_WAVES + (int)(threadIdx.x >> 6);  // wave-uniform
+    const int q = (int)blockIdx.y * WAVE + (int)(threadIdx.x & 63);
+    if(j >= A.count || q >= A.W) return;
+    const int b = from[j];
+    const int NXW = (P.N + 1) * NX, NUW = P.N * NU;
+    unsigned long long word = 0ull;
+    auto ints = [](int lo, int hi) { return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32); };
+    if(q == 0) {
+        word = (unsigned long long)__double_as_longlong(P.f[ILQG_F_COST][b]);
+    } else if(q == 1) {
+        word = ints(P.i[ILQG_I_STATUS][b], P.i[ILQG_I_ITER][b]);
+    } else if(A.ox >= 0 && q >= A.ox && q < A.ox + NXW) {
+        const int e = q - A.ox;
+        word = (unsigned long long)__double_as_longlong(cur_x(P, e / NX, b)[(size_t)(e % NX) * XSI]);
+    } else if(A.ou >= 0 && q >= A.ou && q < A.ou + NUW) {
+        const int e = q - A.ou;
+        word = (unsigned long long)__double_as_longlong(cur_u(P, e / NU, b)[(size_t)(e % NU) * XSI]);
+    } else {
+#pragma unroll
+        for(int i = 0; i < HARVEST_FIELDS; i++) {
+            if(i >= A.n_hist || q < A.off[i] || q >= A.off[i + 1]) continue;
+            const int n = H.i[b], held = n < H.cap ? n : H.cap, e = q - A.off[i];
+            if(A.kind[i] == HARVEST_N) {
+                word = ints(n, 0);
+            } else if(A.kind[i] == HARVEST_DOUBLE) {
+                if(e < held) word = (unsigned long long)__double_as_longlong(H.d[H.at(A.field[i], e, b)]);
+            } else {
+                const int *hi = H.ints();
+                word = ints(2 * e < held ? hi[H.at(A.field[i], 2 * e, b)] : 0, 2 * e + 1 < held ? hi[H.at(A.field[i], 2 * e + 1, b)] : 0);
+            }
+        }
+    }
+    out[(size_t)j * A.W + q] = word;
+}
+
 __global__ void k_count_active(const int *status, int B, int *out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     const int active = (b < B && status[b] == ILQG_ST_ACTIVE) ? 1 : 0;

@@ -554,6 +554,12 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_multi_get_history.argtypes = [v, C.c_char_p, v]
         lib.ilqg_multi_get_history_int.argtypes = [v, C.c_char_p, v]
         lib.ilqg_multi_history_cap.argtypes = [v]
+    if hasattr(lib, "ilqg_batch_solve_stream_rows"):  # (and for a stream whose starts bring rows, windows and a history)
+        names = C.POINTER(C.c_char_p)
+        lib.ilqg_batch_solve_stream_rows.argtypes = [v, C.c_int, v, v, C.c_int, names, v, C.c_int, names, C.POINTER(v),
+                                                     C.c_int, C.c_int, names, C.POINTER(v), v, v, v, v, v]
+        lib.ilqg_batch_stream_counts.argtypes = [v, C.POINTER(C.c_longlong)]
+        lib.ilqg_batch_stream_counts.restype = None
     lib.ilqg_batch_back_pass.argtypes = [v, C.c_int]
     lib.ilqg_batch_active.argtypes = [v, _ip]
     lib.ilqg_batch_get_x.argtypes = [v, _dp]
@@ -898,9 +904,16 @@ class BatchSolver:
         `steps` on, then the plans shift; without it a problem with a per-time-step parameter is refused."""
         return _receding_plant(self, "ilqg_batch_receding_plant", rounds, steps, iterations, feedback, x_plant, params, disturbance, windows)
 
-    def solve_stream(self, x0, u0, with_trajectories=False):
+    def solve_stream(self, x0, u0, with_trajectories=False, params=None, param_steps=None, history=0):
         """a stream of len(x0) starts through this batch's slots (ilqg_batch_solve_stream): dict of cost, status, iterations
-        per start, and x / u if asked for"""
+        per start, and x / u if asked for.
+        Each start may bring its own (ilqg_batch_solve_stream_rows): params = {name: array [total, size]} (the last axis may
+        be left out for size 1), rows of fixed-size parameters as in set_params_batch; param_steps = {name: array
+        [total, n_hor+1]}, windows of per-time-step parameters as in set_param_steps_batch; history = a capacity: the result
+        gains `history`, a dict like history()'s with `total` in place of B.  Start s gets, bit for bit, what solve() gives
+        it in a batch that holds it under set_params_batch / set_param_steps_batch with its rows.  The solver itself must
+        have no set, no rows and no history, and has none afterwards.  Without the three keywords the call is the one it has
+        always been; with one of them on a library built before the entry existed it says so ("rebuild")."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         u0 = np.ascontiguousarray(u0, dtype=np.float64)
         total = x0.shape[0]
@@ -910,11 +923,53 @@ class BatchSolver:
         x = np.zeros((total, self.N + 1, self.problem.nx)) if with_trajectories else None
         u = np.zeros((total, self.N, self.problem.nu)) if with_trajectories else None
         vp = C.c_void_p
-        self.lib.ilqg_batch_solve_stream.argtypes = [vp, C.c_int, _dp, _dp, _dp, _ip, _ip, vp, vp]
-        self._ck(self.lib.ilqg_batch_solve_stream(self.h, total, x0, u0, cost, status, iters,
-                                                  x.ctypes.data_as(vp) if with_trajectories else None,
-                                                  u.ctypes.data_as(vp) if with_trajectories else None))
-        return dict(cost=cost, status=status, iterations=iters, x=x, u=u)
+        xp, up = (x.ctypes.data_as(vp), u.ctypes.data_as(vp)) if with_trajectories else (None, None)
+        if params is None and param_steps is None and isinstance(history, (int, np.integer)) and not isinstance(history, bool) and history == 0:
+            self.lib.ilqg_batch_solve_stream.argtypes = [vp, C.c_int, _dp, _dp, _dp, _ip, _ip, vp, vp]
+            self._ck(self.lib.ilqg_batch_solve_stream(self.h, total, x0, u0, cost, status, iters, xp, up))
+            return dict(cost=cost, status=status, iterations=iters, x=x, u=u)
+        who = "solve_stream"
+        entry = _receding_entry(self.lib, "ilqg_batch_solve_stream_rows")
+        for what, d in (("params", params), ("param_steps", param_steps)):
+            if d is not None and not isinstance(d, dict):
+                raise IlqgError("%s: %s must be a dict of parameter name -> array with a row per start, or None" % (who, what))
+        if isinstance(history, bool) or not isinstance(history, (int, np.integer)):
+            raise IlqgError("%s: history must be an integer (a capacity: that many entries per start, 0: no history), not %r" % (who, history))
+        if history < 0:
+            raise IlqgError("%s: history = %d, must not be negative (a capacity: that many entries per start, 0: no history)" % (who, history))
+        names, values = None, None
+        if params:
+            names, values, _ = _pack_arrays(who, self.problem, params, ((total,),), "all starts", hint=", with total = %d as in x0" % total)
+        step_names, step_ptrs, keep = None, None, []
+        if param_steps:
+            cnames = [_param_steps_name(self.problem, who, name) for name in param_steps]
+            for name, a in param_steps.items():
+                keep.append(_param_steps_rows(who, "param_steps['%s']" % name, a, (total, self.N + 1), False, self.device)[1])
+            step_names = (C.c_char_p * len(cnames))(*cnames)
+            step_ptrs = (vp * len(keep))(*[a.ctypes.data for a in keep])
+        cap, hist, hist_names, hist_ptrs = int(history), None, None, None
+        if cap > 0:
+            me, mf = self.multiplier_dims()
+            known = HISTORY_DOUBLES + (HISTORY_PENALTIES if me + mf else ()) + HISTORY_INTS + ("n",)
+            hist = {name: np.zeros(total, dtype=np.int32) if name == "n" else
+                    np.zeros((total, cap), dtype=np.int32 if name in HISTORY_INTS else np.float64) for name in known}
+            hist_names = (C.c_char_p * len(known))(*[name.encode() for name in known])
+            hist_ptrs = (vp * len(known))(*[hist[name].ctypes.data for name in known])
+        self._ck(entry(self.h, total, _address(x0), _address(u0), 0 if names is None else len(names), names, _address(values),
+                       0 if step_names is None else len(step_names), step_names, step_ptrs,
+                       cap, 0 if hist is None else len(hist), hist_names, hist_ptrs, _address(cost), _address(status), _address(iters), xp, up))
+        out = dict(cost=cost, status=status, iterations=iters, x=x, u=u)
+        if hist is not None:
+            out["history"] = hist
+        return out
+
+    def stream_counts(self):
+        """the last solve_stream, counted (ilqg_batch_stream_counts): dict of polls (status reads), harvests (launches of
+        k_harvest), harvest_bytes (what they copied to the host) and contexts (contexts made: the staging context)"""
+        entry = _receding_entry(self.lib, "ilqg_batch_stream_counts")
+        out = (C.c_longlong * 4)()
+        entry(self.h, out)
+        return dict(zip(("polls", "harvests", "harvest_bytes", "contexts"), (int(v) for v in out)))
 
     def solve_trace(self):
         """the last solve(), poll by poll: (iterations done, trajectories active, slots iterated over) arrays and the number

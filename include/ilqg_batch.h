@@ -117,7 +117,7 @@ int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value,
  * Option "compact": the rows travel with their trajectories, a compacted solve stays bit for bit the plain one.
  * ilqg_batch_solve_stream is REFUSED while a per-trajectory set exists: the rows belong to slots, the starts of a stream pass
  * through them, and a table per start is out of scope.  Option bw_split runs the one-wavefront backward pass while a set
- * exists.
+ * exists.  (A row per START of a stream is an argument of ilqg_batch_solve_stream_rows.)
  *
  * ilqg_batch_set_params_batch takes host memory and waits once per group; ilqg_batch_set_params_batch_device takes DEVICE
  * memory under the stream contract of ilqg_batch_head_device (event in, one event per group out, no host wait, no allocation
@@ -135,7 +135,8 @@ int ilqg_batch_set_param(ilqg_batch_t *c, const char *name, const double *value,
  * ilqg_batch_set_params_batch(c, 0, NULL, NULL)); and every library of the WAVE MAPPING (one wavefront per trajectory: the
  * *_wave libraries and the problems with N_X = 10 or 16 — the text names the mapping): those kernels do not carry parameters
  * per lane.  Not supported, beside the wave, row and quad mappings: a table per start in ilqg_batch_solve_stream, the
- * drop-in iLQG().  (Per-trajectory values of per-time-step parameters: ilqg_batch_set_param_steps_batch, below.) */
+ * drop-in iLQG().  (Per-trajectory values of per-time-step parameters: ilqg_batch_set_param_steps_batch, below; the table per
+ * start that ilqg_batch_solve_stream leaves out: ilqg_batch_solve_stream_rows.) */
 int ilqg_batch_set_params_batch(ilqg_batch_t *c, int n_names, const char *const *names, const double *values /* [B][W] host */);
 int ilqg_batch_set_params_batch_device(ilqg_batch_t *c, int n_names, const char *const *names, const double *values /* [B][W] device */, void *stream);
 int ilqg_batch_get_params_batch(ilqg_batch_t *c, const char *name, double *out /* [B][size] host */);
@@ -350,7 +351,7 @@ int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const d
  * stays refused, and ilqg_batch_receding / _receding_plant still refuse a problem that has a per-time-step parameter.
  * Not supported: the wave, row and quad mappings; the drop-in iLQG(); rows per start in ilqg_batch_solve_stream; the
  * resident closed loops receding / receding_plant for problems with per-time-step parameters (moving windows inside those
- * loops). */
+ * loops).  (A window per START of a stream is an argument of ilqg_batch_solve_stream_rows.) */
 int ilqg_batch_set_param_steps_batch(ilqg_batch_t *c, const char *name, const double *values /* [B][n_hor+1] host, or NULL */);
 int ilqg_batch_set_param_steps_batch_device(ilqg_batch_t *c, const char *name, const double *values /* device, or NULL */, void *stream);
 int ilqg_batch_get_param_steps_batch(ilqg_batch_t *c, const char *name, double *out /* [B][n_hor+1] host */);
@@ -424,6 +425,45 @@ int ilqg_batch_active(ilqg_batch_t *c, int *n_active);
  * refills).  No reference counterpart (the reference solves one trajectory per call, iLQG.c:224). */
 int ilqg_batch_solve_stream(ilqg_batch_t *c, int total, const double *x0, const double *u0, double *cost, int *status,
                             int *iterations, double *x, double *u);
+/* The same stream with what the three notes above leave out of ilqg_batch_solve_stream: every start may bring a ROW of
+ * fixed-size parameters, a WINDOW per per-time-step parameter and an iteration HISTORY of its own.  ilqg_batch_solve_stream is
+ * this entry with nothing named: one loop, the same results, trace and refill rule (a refill once a sixteenth of the slots is
+ * free, polls every 8 iterations).
+ * The starts: start s is solved as a plain ilqg_batch_solve solves it in a batch that holds it at slot b, after
+ * ilqg_batch_set_params_batch(names, ...) with row values[s] at b and ilqg_batch_set_param_steps_batch(step_names[i], ...)
+ * with row step_values[i][s] at b: the plain solve's result bit for bit, in every build.  names, their order, W and the row
+ * layout are those of ilqg_batch_set_params_batch, values [total][W] (n_names = 0: none, names and values are not read);
+ * step_names are parameters of size -1, step_values[i] [total][n_hor+1] (n_step_names = 0: none).  A parameter not named stays
+ * the batch's shared value or window.
+ * The history: with hist_cap > 0 every start records its own iteration history under the one rule of
+ * ilqg_batch_set_history (the staging context's init clears it, the move carries it).  hist_names are the names of
+ * ilqg_batch_get_history / _get_history_int; hist_out[i] is double [total][hist_cap] for a double name, int [total][hist_cap]
+ * for an int name and int [total] for "n".  Unwritten entries read as zero, and n may exceed hist_cap (dropped but counted).
+ * Before and after: on entry c has no per-trajectory set, no step rows and no history; on return, success or failure, c is as
+ * on entry: it has none again — ilqg_batch_get_params_batch gives the shared values, ilqg_batch_history_cap gives 0.  Its
+ * trajectories are overwritten.  ilqg_batch_solve_trace reports polls and refills as for ilqg_batch_solve_stream.
+ * How: the rows reach the staging context through the setters above (slots beyond the starts it initialises hold the shared
+ * values, never zeros), c gets the same map and a table of the shared values once, before the first refill.  Finished starts
+ * come back through a gather kernel (k_harvest): per stream group and poll one launch and one copy of exactly what was asked
+ * for; a poll in which nothing finished reads the statuses and nothing else.  No context is made per poll.
+ * REFUSED, with the argument (and the parameter) named in the error text, before anything is launched, allocated or changed —
+ * c's trajectories are still what they were: total < 1; x0 or u0 NULL; a c that already has a set, rows or a history (the
+ * text tells the caller to pass them to this call); what ilqg_batch_set_params_batch refuses of names / values; what
+ * ilqg_batch_set_param_steps_batch refuses of a name (fixed-size, unknown, given twice, a NULL table); hist_cap < 0; n_hist > 0
+ * with hist_cap = 0; an unknown history name; w_pen_* without multipliers; a NULL hist_out[i]; and in a library of the WAVE
+ * MAPPING n_names > 0 or n_step_names > 0 (the text names the mapping) — a history alone is served there.
+ * No such refusal, but a FAILURE of the call: device memory that runs out.  A history capacity the batch's device has no memory
+ * for fails with c's trajectories still what they were; the staging context or its history failing to fit fails behind that,
+ * with c's trajectories already overwritten (c is as on entry in every other respect).
+ * Not supported: ilqg_multi_* (no stream); option "compact" inside a stream; rows in device memory; the drop-in iLQG(). */
+int ilqg_batch_solve_stream_rows(ilqg_batch_t *c, int total, const double *x0, const double *u0,
+                                 int n_names, const char *const *names, const double *values,
+                                 int n_step_names, const char *const *step_names, const double *const *step_values,
+                                 int hist_cap, int n_hist, const char *const *hist_names, void *const *hist_out,
+                                 double *cost, int *status, int *iterations, double *x, double *u);
+/* the last stream, counted: out[0] polls (status reads), out[1] launches of k_harvest, out[2] bytes the harvests copied to the
+ * host, out[3] contexts made (the staging context: 1) */
+void ilqg_batch_stream_counts(const ilqg_batch_t *c, long long *out /* [4] */);
 /* the last ilqg_batch_solve, poll by poll (it polls every 4 iterations): iterations done so far, trajectories still
  * active, slots the iterations ran over (the batch, or the smaller context of option "compact"); returns the number of
  * polls (at most cap entries are written; any pointer may be NULL), *compactions = how often the active set was gathered */
@@ -489,7 +529,8 @@ int ilqg_batch_set_int(ilqg_batch_t *c, const char *name, const int *in);
  * get_int: name "n" gives [B] (it may exceed cap), the others [B][cap].  Refused, with the batch and its history left as
  * they were and nothing launched: cap < 0; a capacity the device has no memory for; a getter without a history; an unknown
  * name; w_pen_* without multipliers; out = NULL.  ilqg_batch_solve_stream refuses a batch with a history: it belongs to
- * slots, starts pass through them — switch it off first, ilqg_batch_set_history(c, 0). */
+ * slots, starts pass through them — switch it off first, ilqg_batch_set_history(c, 0).  (A history per START of a stream is
+ * an argument of ilqg_batch_solve_stream_rows: hist_cap.) */
 int ilqg_batch_set_history(ilqg_batch_t *c, int cap);
 int ilqg_batch_get_history(ilqg_batch_t *c, const char *name, double *out /* [B][cap] */);
 int ilqg_batch_get_history_int(ilqg_batch_t *c, const char *name, int *out /* "n": [B]; else [B][cap] */);
