@@ -198,6 +198,10 @@ int drv_forward_pass(drv_t *d, double alpha, double *cost) {
     return forward_pass(d->o.candidates[0], &d->o, alpha, cost, 0);
 }
 void drv_set_lambda(drv_t *d, double lambda) { d->o.lambda = lambda; }
+/* iLQG.c:237 (init = 1) and :337 (init = 0): the generated update of multipliers and penalty weights on its own */
+int drv_update_multipliers(drv_t *d, int init) { return update_multipliers(&d->o, init); }
+/* iLQG.c:338 and :348: the nominal's cost swept again under the multipliers and weights of now */
+int drv_cost_resweep(drv_t *d) { return forward_pass(d->o.nominal, &d->o, 0.0, &d->o.cost, 1); }
 
 int drv_solve(drv_t *d) {
     int r;

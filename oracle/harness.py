@@ -191,6 +191,9 @@ def _bind(lib):
         lib.drv_set_search_state.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
     if hasattr(lib, "drv_get_step_costs"):
         lib.drv_get_step_costs.argtypes = [C.c_void_p, C.c_int, _dp]
+    if hasattr(lib, "drv_update_multipliers"):
+        lib.drv_update_multipliers.argtypes = [C.c_void_p, C.c_int]
+        lib.drv_cost_resweep.argtypes = [C.c_void_p]
     if hasattr(lib, "drv_solve_many"):
         lib.drv_solve_many.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _ip, _ip]
     return lib
@@ -262,6 +265,15 @@ class Driver:
         c = np.zeros(1)
         ok = self.lib.drv_forward_pass(self.h, float(alpha), c)
         return ok, float(c[0])
+
+    def update_multipliers(self, init=0):
+        """the problem file's update_multipliers(o, init) alone (iLQG.c:237 with init = 1, :337 with 0)"""
+        return self.lib.drv_update_multipliers(self.h, int(init))
+
+    def cost_resweep(self):
+        """forward_pass(nominal, o, 0, &cost, 1): the cost swept again under the present multipliers and weights
+        (iLQG.c:338, :348)"""
+        return self.lib.drv_cost_resweep(self.h)
 
     def set_lambda(self, lam):
         self.lib.drv_set_lambda(self.h, float(lam))

@@ -497,9 +497,20 @@ def linesearch_goldens():
     print("line search cases: %d batches, %d cases, %d bytes" % (len(LS.BATCHES), sum(b[5] for b in LS.BATCHES.values()), os.path.getsize(LS.GOLDEN)))
 
 
+def multiplier_goldens():
+    """tests/multiplier_cases.py: the reference build's update_multipliers() and cost re-sweep on every case of that module's
+    batches, its entry forms and its step-4 sequences through iLQG() — results only"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multiplier_cases as MC
+    with quiet():
+        out = MC.golden_of("ref")
+    np.savez_compressed(MC.GOLDEN, **out)
+    print("multiplier cases: %d arrays, %d bytes" % (len(out), os.path.getsize(MC.GOLDEN)))
+
+
 def main(argv):
-    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases linesearch synth synthp
-    console vsref"""
+    """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases linesearch multipliers
+    synth synthp console vsref"""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     groups = {
         "brachi": brachi_goldens,
@@ -511,6 +522,7 @@ def main(argv):
         "regtype2": regtype2_goldens,
         "regtype2cases": regtype2_case_goldens,
         "linesearch": linesearch_goldens,
+        "multipliers": multiplier_goldens,
         "synth": lambda: [synth_goldens(fd) for fd in (0, 1)],
         "synthp": lambda: synth_goldens(1, N=12, problem="synth16p", SYN_PARAMS=SYNP_PARAMS_TIGHT),
         "console": console_goldens,
