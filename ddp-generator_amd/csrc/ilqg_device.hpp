@@ -407,10 +407,7 @@ ILQG_DEV void chol_pattern_table(const double *H, double (*inv)[tri(M)], bool *p
 // now holds the table and the selects (2 976 -> 3 691); the step stays at 13 035 cycles, the headline 179-180 against
 // 181-182 it/s.  A wavefront factorised ~2 times per step before (once per outer iteration in which some lane's free set
 // changed), each time ONE pattern per lane; the table is three patterns per lane, every step.
-// profiles/r4_sections_qp_table.txt.  Off by default (-DILQG_QP_TABLE=1 turns it on); the unit-test kernel runs both forms.
-#ifndef ILQG_QP_TABLE
-#define ILQG_QP_TABLE 0
-#endif
+// profiles/r4_sections_qp_table.txt.  Off by default (WITH_TABLE of box_qp); the unit-test kernel runs both forms.
 
 // ---------------------------------------------------------------------------
 // boxQP.c
@@ -452,7 +449,7 @@ static_assert(ARMIJO_LAST > 8 && ARMIJO_LAST < 200, "0.6^k falls below 1e-22 nea
 // block's factor and inverse embedded at the original indices (all extra terms
 // are exact zeros), so `invH` is returned in FULL index form: invH[sy(i,j)]
 // for free i,j equals the reference's invHfree[sy(i_free,j_free)].
-template <int M, bool WITH_TABLE = (ILQG_QP_TABLE != 0)>
+template <int M, bool WITH_TABLE = false>
 ILQG_DEV int box_qp(const double *H, const double *g, const double *lower, const double *upper, double *x,
                     int *clamp, int &n_free_out, double *invH, Prof *pf = nullptr) {
     // Control flow.  The reference leaves its loop through seven `return`s; compiled literally for 64 lanes in

@@ -151,7 +151,6 @@ __device__ __forceinline__ int ilqg_note_nonfinite(double **p, double v) {
 // fdlibm / FreeBSD msun k_sin.c and k_cos.c on [-pi/4, pi/4] with the reduction tail.  Error
 // below 1 ulp, the same class as the host libm and the device library (tests/test_gpu_parity.py
 // checks it against numpy).
-#ifndef ILQG_NO_SHARED_SINCOS
 struct ilqg_sc { double s, c; };
 
 __device__ __attribute__((noinline)) static ilqg_sc ilqg_sincos_slow(double x) {
@@ -230,23 +229,15 @@ __device__ __attribute__((noinline, const)) static ilqg_sc ilqg_sincos_call(doub
 #define cos(x) (ilqg_sincos_call(x).c)
 // ... except in the parts of a roll-out step (ilqg_step_part, a few dozen call sites): there they are inline, the
 // library behind a branch for what the straight-line path cannot reduce.  A call makes the caller wait for every memory
-// operation in flight — the operands of the NEXT step, requested a step ahead — once per step (ILQG_PART_INLINE_SINCOS=0:
-// calls there too).
-#ifndef ILQG_PART_INLINE_SINCOS
-#define ILQG_PART_INLINE_SINCOS 1
-#endif
-#if ILQG_PART_INLINE_SINCOS
+// operation in flight — the operands of the NEXT step, requested a step ahead — once per step.
 #define ILQG_PART_SIN(v) (ilqg_sincos(v).s)
 #define ILQG_PART_COS(v) (ilqg_sincos(v).c)
-#endif
 #else
 #define sin(x) (ilqg_sincos_hooked(p, (x)).s)
 #define cos(x) (ilqg_sincos_hooked(p, (x)).c)
 #endif
-#endif
 
 // sin and cos of one argument at once for the derivative record in parts (ilqg_deriv_prepare)
-#ifndef ILQG_NO_SHARED_SINCOS
 // (straight-line form with the hooks, see ilqg_sincos_hooked: a call to the library on the spot would make every value
 // alive at that point travel through scratch memory around it — 32 call sites in ilqg_deriv_prepare)
 #define ILQG_DERIV_SINCOS(ARG_, SIN_, COS_)               \
@@ -255,7 +246,6 @@ __device__ __attribute__((noinline, const)) static ilqg_sc ilqg_sincos_call(doub
         (SIN_) = r_.s;                                    \
         (COS_) = r_.c;                                    \
     } while(0)
-#endif
 
 // Both functions of the derivative record in parts are inlined (what they hand over stays in registers), and every part
 // begins with a statement the optimiser must take as having an effect: a switch over 30 cheap side-effect-free cases is
@@ -405,15 +395,7 @@ __device__ __forceinline__ void set_record(void *rec) { record_lds[threadIdx.x &
 __device__ __forceinline__ double &slot(unsigned e) { return ring_lds[(e & 63u) * LD + (threadIdx.x & 63)]; }
 
 // entries [first, first + count) of the lanes' records, from the ring to HBM (count <= 64, one aligned window of 64)
-#ifndef ILQG_DEV_FLUSH_INLINE
-#define ILQG_DEV_FLUSH_INLINE 1
-#endif
-#if ILQG_DEV_FLUSH_INLINE
-#define ILQG_DEV_FLUSH_ATTR __device__ __forceinline__
-#else
-#define ILQG_DEV_FLUSH_ATTR __device__ __attribute__((noinline))
-#endif
-ILQG_DEV_FLUSH_ATTR void flush(int m, unsigned first, int count) {
+__device__ __forceinline__ void flush(int m, unsigned first, int count) {
     typedef __attribute__((address_space(1))) double gdouble;
     asm volatile("" ::: "memory");
     const unsigned lane = threadIdx.x & 63;
@@ -555,7 +537,7 @@ extern "C" {
 #ifndef ILQG_WAVE_MAP
 #define ILQG_WAVE_MAP (N_X > 8)
 #endif
-#if ILQG_WAVE_MAP && !defined(ILQG_NO_STAGED_RECORDS)
+#if ILQG_WAVE_MAP
 #define ILQG_REC(member, index) ilqg_stage_at((unsigned)((offsetof(trajEl_t, member) / sizeof(double) + (index)) & 63u))
 #define ILQG_REC_DONE(member, first, count) ilqg_stage_flush(p, (unsigned)(offsetof(trajEl_t, member) / sizeof(double) + (first)), count);
 // (the products of the factored tensors: bp_tensor_basis(t->fxx, t, ...) — the kernel passes the start of fxx)

@@ -22,23 +22,9 @@ struct ParamTable {
 // searches hold more wave-uniform values than there are scalar registers; what does not fit travels through
 // v_writelane / v_readlane — vector instructions with wait states, inside the step loops — while vector registers are
 // to spare there.  Per kernel, where that kernel's launch time gained by it (profiles/r14_vector_params.txt), and only for
-// a problem with few parameter doubles: each costs two vector registers.  -DILQG_VECTOR_PARAMS=0: scalar everywhere, as before.
-#ifndef ILQG_VECTOR_PARAMS
-#define ILQG_VECTOR_PARAMS 1
-#endif
-#ifndef ILQG_VECTOR_PARAMS_MAX  // parameter doubles up to which a kernel may hold them per lane (CarParking: 20)
-#define ILQG_VECTOR_PARAMS_MAX 24
-#endif
-#ifndef ILQG_VECTOR_PARAMS_BACKWARD  // k_backward<2>
-#define ILQG_VECTOR_PARAMS_BACKWARD 1
-#endif
-#ifndef ILQG_VECTOR_PARAMS_SEARCH0  // k_search<0, true>
-#define ILQG_VECTOR_PARAMS_SEARCH0 1
-#endif
-#ifndef ILQG_VECTOR_PARAMS_SEARCH1  // k_search<1, true>
-#define ILQG_VECTOR_PARAMS_SEARCH1 1
-#endif
-constexpr bool VECTOR_PARAMS = ILQG_VECTOR_PARAMS && !ILQG_WAVE_MAP && ILQG_PTOTAL <= ILQG_VECTOR_PARAMS_MAX;
+// a problem with few parameter doubles: each costs two vector registers.  The kernels that do: k_backward<2>, k_search<0, true>, k_search<1, true>.
+constexpr int VECTOR_PARAMS_MAX = 24;  // parameter doubles up to which a kernel may hold them per lane (CarParking: 20)
+constexpr bool VECTOR_PARAMS = !ILQG_WAVE_MAP && ILQG_PTOTAL <= VECTOR_PARAMS_MAX;
 template <bool VECTOR = false>
 __device__ __forceinline__ void load_params(ParamValues &V, ParamTable &T, ilqg_hooks &H, const ParamValues &A,
                                             double **p) {

@@ -527,10 +527,7 @@ __device__ __forceinline__ int back_step_quad(const unsigned rb, const unsigned 
             for(int q = 0; q < NTC; q += 2) pair_of(R::fxu, NXU, q, t[NTX + NTU + q], t[NTX + NTU + q + 1]);
         };
         static_assert(SXX % 2 == 0 && SUU % 2 == 0 && NXU % 2 == 0, "a pair of entries does not straddle two slices");
-#ifndef ILQG_QUAD_STORED_DEPTH
-#define ILQG_QUAD_STORED_DEPTH 4
-#endif
-        constexpr int DEPTH = ILQG_QUAD_STORED_DEPTH < NX ? ILQG_QUAD_STORED_DEPTH : NX;
+        constexpr int DEPTH = 4 < NX ? 4 : NX;
         double buf[DEPTH][PER];
         static_for<0, DEPTH>([&](auto ic) { fetch(ic, buf[decltype(ic)::value]); });
         static_for<0, NX>([&](auto ic) {

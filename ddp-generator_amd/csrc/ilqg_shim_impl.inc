@@ -251,13 +251,6 @@ struct ilqg_dev : DevBuffers {
 
 namespace {
 
-// measurement builds (tools/experiments/wave_places.py): LDS per search workgroup, which bounds the search wavefronts per CU
-#ifdef ILQG_SEARCH_LDS_PAD
-#define SEARCH_LDS(bytes) ((size_t)(bytes) > (size_t)(ILQG_SEARCH_LDS_PAD) ? (size_t)(bytes) : (size_t)(ILQG_SEARCH_LDS_PAD))
-#else
-#define SEARCH_LDS(bytes) (bytes)
-#endif
-
 static ilqg_dev *g_spec_last;  // the context whose backward pass ran with speculative retries last (measurement: ilqg_dev_spec_words)
 struct FieldInfo { int steps_plus; int wd, wh; };  // steps = steps_plus<0 ? 1 : N + steps_plus
 
@@ -2051,7 +2044,7 @@ static void launch_search_stage(ilqg_dev_t *d, hipStream_t rs, int a0, int n, in
     const int T = WAVE / n;
     const dim3 grid((d->B + T - 1) / T), block(WAVE);
     if(T * (RN / 2) <= WAVE * DMA_LOADS && !d->env.no_dma)  // the nominal records through LDS
-        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<STAGE, true, decltype(tr)...>), grid, block, SEARCH_LDS(2 * T * RN * sizeof(double)), rs, d->P, d->O, d->pv, a0, n, set, tr...); });
+        with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<STAGE, true, decltype(tr)...>), grid, block, 2 * T * RN * sizeof(double), rs, d->P, d->O, d->pv, a0, n, set, tr...); });
     else
         with_rows(d, [&](auto... tr) { hipLaunchKernelGGL((k_search<STAGE, false, decltype(tr)...>), grid, block, 0, rs, d->P, d->O, d->pv, a0, n, set, tr...); });
 }

@@ -67,10 +67,6 @@ struct WaveLds {
 // keeps that order.  (No s_barrier: a workgroup may hold several wavefronts, each working on a trajectory of its own at
 // its own pace.)
 ILQG_DEV void wave_sync() {
-#ifdef ILQG_WAVE_SYNC_BARRIER
-    __syncthreads();
-    return;
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

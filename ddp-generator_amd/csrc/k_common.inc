@@ -488,13 +488,9 @@ __global__ void k_count_active(const int *status, int B, int *out) {
 __global__ void k_sincos_test(int n, const double *x, double *s, double *c) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= n) return;
-#ifndef ILQG_NO_SHARED_SINCOS
     const ilqg_sc r = ilqg_sincos(x[i]);
     s[i] = r.s;
     c[i] = r.c;
-#else
-    sincos(x[i], &s[i], &c[i]);
-#endif
 }
 
 // The reference's small dense helpers as callable entry points (matMult.h:11-14, cholesky.h:4-6), executed by

@@ -81,12 +81,9 @@ __device__ __forceinline__ int derivs_final(trajFin_t &fin, multipliersFin_t *m,
 #endif
 
 // The entries of a step's record that are identically 0, for the fused sweep (ilqg_device.hpp, NoZeros): the generated
-// header's list ILQG_STRUCTURAL_ZERO in RecLayout's numbering.  A header without the list (Maxima-generated), the FMA-free
-// twin and -DILQG_FOLD_ZEROS=0 keep the dense products.
-#ifndef ILQG_FOLD_ZEROS
-#define ILQG_FOLD_ZEROS 1
-#endif
-#if defined(ILQG_STRUCTURAL_ZERO) && !defined(ILQG_STRICT_FP) && ILQG_FOLD_ZEROS
+// header's list ILQG_STRUCTURAL_ZERO in RecLayout's numbering.  A header without the list (Maxima-generated) and the
+// FMA-free twin keep the dense products.
+#if defined(ILQG_STRUCTURAL_ZERO) && !defined(ILQG_STRICT_FP)
 struct RecZeros {
     static constexpr bool at(int i) {
         bool z = false;
@@ -384,17 +381,12 @@ __device__ __forceinline__ int backward_sweep_fused(const DevPtrs &P, Callbacks 
 // mode: 0 = records from HBM, lambda retry loop and gradient test (iLQG.c:261-303)
 //       1 = records from HBM, ONE sweep (the drop-in back_pass(): the caller owns the retry loop)
 //       2 = as 0 with the derivatives evaluated on the fly (k_derivs is not needed)
-#ifndef ILQG_BACKWARD_OCC  // wavefronts of k_backward per SIMD the register allocation must allow
-#define ILQG_BACKWARD_OCC 1
-#endif
 template <int mode, class... Rows>
-__global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
+__global__ __launch_bounds__(WAVE, 1)  // (1: wavefronts of k_backward per SIMD the register allocation must allow)
+void k_backward(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, Rows... rows) {
     // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
     constexpr bool PER_TRAJECTORY = RowPack<OWN_NONE, Rows...>::has_trajectory_rows;
     const Place place(1);
-#ifdef ILQG_BACKWARD_PRIO  // measurement builds: issue priority of the sweep's wavefront over search wavefronts on its SIMD
-    __builtin_amdgcn_s_setprio(ILQG_BACKWARD_PRIO);
-#endif
     const int b = blockIdx.x * WAVE + threadIdx.x;
     if(b >= P.B) return;
     if(P.i[ILQG_I_STATUS][b] != ILQG_ST_ACTIVE) return;
@@ -405,7 +397,7 @@ __global__ __launch_bounds__(WAVE, ILQG_BACKWARD_OCC) void k_backward(DevPtrs P,
         return;
     }
     // (the shared fused sweep: parameters per lane, where measured faster — load_params)
-    ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && mode == 2 && ILQG_VECTOR_PARAMS_BACKWARD);
+    ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && mode == 2);
     apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
     load_penalty_weights_der(C, P, b);
     double lambda = P.f[ILQG_F_LAMBDA][b], dlambda = P.f[ILQG_F_DLAMBDA][b];

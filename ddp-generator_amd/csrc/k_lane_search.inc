@@ -20,9 +20,6 @@
 // accepted ones (few) into X / U.
 // The scan state (last cnew / dcost / expected) is carried from stage to stage exactly as k_select does, so the
 // accepted index and the values left behind are those of one sequential scan (line_search.c:37-75).
-#ifndef ILQG_SEARCH_OCC  // wavefronts of k_search per SIMD the register allocation must allow
-#define ILQG_SEARCH_OCC 1
-#endif
 // DMA: the nominal records of the wavefront's T trajectories reach the lanes through LDS.  Every lane needs the whole
 // record of its trajectory (x, u, l, L: 128 bytes for CarParking) in every step, and with per-lane loads the n lanes of
 // a trajectory each pull it through the CU's vector-memory path: 8 KB per wavefront and step for 2 KB of data, on the
@@ -34,8 +31,8 @@
 // step k+1's are read.  Used when a step's pieces fit DMA_LOADS loads (T * RN / 2 <= 64 DMA_LOADS).
 constexpr int DMA_LOADS = 3;
 template <int stage, bool DMA, class... Rows>
-__global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int a0, int n, int set,
-                                                                  Rows... rows) {
+__global__ __launch_bounds__(WAVE, 1)  // (1: wavefronts of k_search per SIMD the register allocation must allow)
+void k_search(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int a0, int n, int set, Rows... rows) {
     // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map
     constexpr bool PER_TRAJECTORY = RowPack<OWN_NONE, Rows...>::has_trajectory_rows;
     extern __shared__ __attribute__((aligned(16))) double s_rec[];  // DMA: [2][T * RN] doubles
@@ -59,7 +56,7 @@ __global__ __launch_bounds__(WAVE, ILQG_SEARCH_OCC) void k_search(DevPtrs P, ilq
     const bool feedback = (alpha != 0.0);  // alpha == 0.0: u = u_nom without feedback (iLQG_func.tem:156-158)
 
     // (the shared kernels with the records through LDS: parameters per lane, where measured faster — load_params)
-    ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && DMA && (stage ? ILQG_VECTOR_PARAMS_SEARCH1 : ILQG_VECTOR_PARAMS_SEARCH0));
+    ILQG_CALLBACKS_IN(C, H, VECTOR_PARAMS && !PER_TRAJECTORY && DMA);
     // (b = pending[ee] or ee: lanes beyond the end repeat the last entry, and read its row)
     apply_rows<OWN_NONE>(C_values, C_table, P, b, 0, 0, rows...);
     load_penalty_weights(C, P, b);

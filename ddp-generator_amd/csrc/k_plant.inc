@@ -27,11 +27,11 @@
 // NOTHING of the batch is written.
 
 template <bool PLANT_PARAMS, class... Rows>
-__global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_plant(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int steps, int feedback,
-                                                                        double *__restrict__ xp, int *__restrict__ failed,
-                                                                        const double *__restrict__ dist, int at0, int total, int round, int rounds,
-                                                                        double *__restrict__ lx, double *__restrict__ lu, double *__restrict__ lc,
-                                                                        double *__restrict__ lp, Rows... rows) {
+__global__ __launch_bounds__(ROLL_BLOCK) void k_plant(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int steps, int feedback,
+                                                      double *__restrict__ xp, int *__restrict__ failed,
+                                                      const double *__restrict__ dist, int at0, int total, int round, int rounds,
+                                                      double *__restrict__ lx, double *__restrict__ lu, double *__restrict__ lc,
+                                                      double *__restrict__ lp, Rows... rows) {
     // the pack: [the context's per-trajectory table, its map,] [the plants' table, its map] (RowPack)
     const int b = (int)(blockIdx.x * ROLL_BLOCK + threadIdx.x);
     if(b >= P.B) return;

@@ -80,10 +80,10 @@ __device__ __forceinline__ void policy_control(double (&uin)[NU], const NomStep 
 }
 
 template <bool PER_ROLLOUT_PARAMS, class... Rows>
-__global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
-                                                                         double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
-                                                                         double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
-                                                                         const double *__restrict__ dist, int dist_shared, Rows... rows) {
+__global__ __launch_bounds__(ROLL_BLOCK) void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
+                                                       double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
+                                                       double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
+                                                       const double *__restrict__ dist, int dist_shared, Rows... rows) {
     // the pack: [the context's per-trajectory table, its map,] [values, shared, map of the roll-outs' own rows] (RowPack)
     const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
     if(g >= (size_t)P.B * (size_t)R) return;

@@ -60,27 +60,20 @@ __device__ __forceinline__ void load_nominal(NomStep &s, const NomPtrs &q) {
 // The time step itself is straight-line code: the generated callbacks' NaN/Inf guards and the
 // huge-argument case of sin/cos are hooks (see ilqg_hooks), tested once per step (run_step).
 enum { RK_GENERAL = 0, RK_INIT = 1, RK_COST = 2 };
-#ifdef ILQG_ROLLOUT_WAVES  // experiments: force that many wavefronts of the roll-out kernels per SIMD (register cap)
-#define ILQG_ROLLOUT_ATTR __attribute__((amdgpu_waves_per_eu(ILQG_ROLLOUT_WAVES)))
-#else
-#define ILQG_ROLLOUT_ATTR
-#endif
 
-// Wavefronts per workgroup of the roll-outs (experiments).  One: in the wave mapping a roll-out wavefront fills the
+// Wavefronts per workgroup of the roll-outs.  One: in the wave mapping a roll-out wavefront fills the
 // register file of its SIMD and the backward kernel's workgroup needs a whole CU, so four per workgroup (one CU
 // instead of four blocked) was tried to let the roll-outs of one group of trajectories share the chip with the
 // backward pass of another — 1.86 it/s (one group) and 1.92 (two groups, 8 hardware queues) against 1.98 as is:
 // the backward kernel keeps the SIMDs it runs on busy, there is little idle issue time to give away.
-#ifndef ILQG_ROLL_WAVES
-#define ILQG_ROLL_WAVES 1
-#endif
-constexpr int ROLL_BLOCK = WAVE * ILQG_ROLL_WAVES;
+constexpr int ROLL_WAVES = 1;
+constexpr int ROLL_BLOCK = WAVE * ROLL_WAVES;
 #if ILQG_DEV_EL
-static_assert(ILQG_ROLL_WAVES == ilqgdev::WAVES, "ilqgdev's ring is that of ONE wavefront per workgroup");
+static_assert(ROLL_WAVES == ilqgdev::WAVES, "ilqgdev's ring is that of ONE wavefront per workgroup");
 #endif
 
 template <int KIND, class... Rows>
-__global__ __launch_bounds__(ROLL_BLOCK) ILQG_ROLLOUT_ATTR void k_rollout(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int mode, int a0, Rows... rows) {
+__global__ __launch_bounds__(ROLL_BLOCK) void k_rollout(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int mode, int a0, Rows... rows) {
     // Rows: empty — the kernel as it always was, under its old name — or the context's per-trajectory table and its map (RowPack)
     int b = blockIdx.x * ROLL_BLOCK + threadIdx.x;
     int ai = a0 + blockIdx.y;

@@ -15,10 +15,7 @@
 constexpr size_t fact_stride() {
     const size_t A = offsetof(trajEl_t, fxx) + NBASIS * sizeof(double);
     const size_t TAIL = offsetof(trajEl_t, fxu) + sizeof(double) * NX * NXU, T = sizeof(trajEl_t) - TAIL;
-#ifndef ILQG_FACT_ALIGN
-#define ILQG_FACT_ALIGN 128
-#endif
-    constexpr size_t AL = ILQG_FACT_ALIGN;  // whole cache lines (measured against 8: k_derivs_wave 116 -> 113 ms per iteration)
+    constexpr size_t AL = 128;  // whole cache lines (measured against 8: k_derivs_wave 116 -> 113 ms per iteration)
     if(T == 0) return (A + AL - 1) / AL * AL;
     for(size_t S = (A + T + AL - 1) / AL * AL; S < sizeof(trajEl_t); S += AL) {
         const size_t r = TAIL % S;
@@ -52,11 +49,6 @@ __device__ __forceinline__ trajEl_t *work_rec(const DevPtrs &P, int bw, int k) {
 static_assert(ILQG_DERIVS_BLOCK == 64 * ilqgdev::WAVES, "ilqgdev's ring is that of ONE wavefront per workgroup");
 #endif
 constexpr size_t DERIVS_DYN_LDS = 0;
-#ifdef ILQG_DERIVS_WAVES  // experiments: that many wavefronts per SIMD (register cap)
-#define ILQG_DERIVS_ATTR __attribute__((amdgpu_waves_per_eu(ILQG_DERIVS_WAVES, ILQG_DERIVS_WAVES)))
-#else
-#define ILQG_DERIVS_ATTR
-#endif
 #if ILQG_STAGED_RECORDS
 // runs of staged entries may cross from one member into the next (tools/gen_problem.py record_offsets(): the layout of
 // iLQG_problem.tem:23-51)
@@ -67,9 +59,6 @@ static_assert(offsetof(trajEl_t, cxx) == offsetof(trajEl_t, cx) + sizeof(double)
 #endif
 // the general record (tensors stored): a function of its own, so that k_derivs_wave can take everything else inline
 __device__ __attribute__((noinline)) static int derivs_with_tensors(el_t *t, int k, double **p) { return bp_derivsL(t, k, p); }
-#ifndef ILQG_DEV_INLINE
-#define ILQG_DEV_INLINE 1
-#endif
 #if ILQG_DEV_EL
 // a plain member of the private element into its place in the lanes' records, through the ring (runs cut at multiples of 64 entries)
 template <int COUNT>
@@ -87,14 +76,6 @@ __device__ __forceinline__ void stage_member(int m, unsigned first, const double
 }
 #endif
 
-#ifndef ILQG_DERIVS_FLATTEN
-#define ILQG_DERIVS_FLATTEN 1
-#endif
-#if ILQG_DERIVS_FLATTEN
-#define ILQG_DERIVS_INLINE [[clang::always_inline]]
-#else
-#define ILQG_DERIVS_INLINE
-#endif
 // FACT: the records the factored backward step reads (first-order part + the products).  That instantiation takes every
 // generated function inline: nothing of the callbacks' surroundings (the parameter table, the parameter values, the
 // hooks) has its address passed on, all of it dissolves into registers — the parameters into scalar ones.  While one
@@ -103,8 +84,8 @@ __device__ __forceinline__ void stage_member(int m, unsigned first, const double
 // (the wave-uniform guards end a block at every assignment): 20 memory round trips in front of the first 64 entries
 // of fx alone, 100 000 of a wavefront's 290 000 cycles.
 template <bool FACT>
-__global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_wave(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int chunk_first,
-                                                    int chunk_count, int init_consts, int limit_gradients, int final_only) {
+__global__ __launch_bounds__(ILQG_DERIVS_BLOCK) void k_derivs_wave(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int chunk_first, int chunk_count,
+                                                                  int init_consts, int limit_gradients, int final_only) {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     // (final_only: lane = trajectory, the final record alone — the steps' records come from k_derivs_parts)
     const int bw = final_only ? (int)tid : (int)(tid / (P.N + 1));
@@ -115,7 +96,7 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
     // registers once everything is inline — 45 doubles, 90 of 104 registers, for the n = 16 problem: spilled through
     // vector lanes that are spilled themselves.  A parameter read is then one LDS read of one address by all lanes.
     // (the same where the callbacks work on a private element with proxies, ILQG_DEV_EL: everything inline there as well)
-    constexpr bool LDS_PARAMS = FACT || (ILQG_DEV_EL && ILQG_DEV_INLINE);
+    constexpr bool LDS_PARAMS = FACT || ILQG_DEV_EL;
     __shared__ double s_params[LDS_PARAMS && ILQG_PTOTAL > 0 ? ILQG_PTOTAL : 1];
     if constexpr(LDS_PARAMS) {
         for(int i = threadIdx.x; i < ILQG_PTOTAL; i += blockDim.x) s_params[i] = A.v[i];
@@ -156,7 +137,7 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
         [[clang::always_inline]] init_running(&own, &C.o1);
     }
 #else
-    if(init_consts && inside && k < P.N) ILQG_DERIVS_INLINE init_running(work_rec(P, bw, k), &C.o1);
+    if(init_consts && inside && k < P.N) [[clang::always_inline]] init_running(work_rec(P, bw, k), &C.o1);
 #endif
     const bool live = inside && P.i[ILQG_I_STATUS][inside ? b : chunk_first] == ILQG_ST_ACTIVE;
     // The step records.  Runs of their entries are collected in LDS and written out by the whole wavefront
@@ -199,21 +180,16 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
 #if ILQG_DEV_EL
             ilqgdev::set_mode(H.alone != 0.0 ? ilqgdev::ALONE : ilqgdev::TOGETHER);
 #endif
-#ifndef ILQG_ABLATE  // timing experiments: leave parts of the evaluation out (profiles/README.md)
-#define ILQG_ABLATE 0
-#endif
             ILQG_DPROBE(0);
-            if(!(ILQG_ABLATE & 32)) {
-                for(int i = 0; i < NX; i++) t->x[i] = nomp(P, k_s, b_s)[NOM_X + i];
-                for(int i = 0; i < NU; i++) t->u[i] = nomp(P, k_s, b_s)[NOM_U + i];
-            }
+            for(int i = 0; i < NX; i++) t->x[i] = nomp(P, k_s, b_s)[NOM_X + i];
+            for(int i = 0; i < NU; i++) t->u[i] = nomp(P, k_s, b_s)[NOM_U + i];
             ILQG_DPROBE();
             ok = 1;
-            if(!(ILQG_ABLATE & 1)) ILQG_DERIVS_INLINE ok = calcXVariableAux(t, mp, k_s, &o);
+            [[clang::always_inline]] ok = calcXVariableAux(t, mp, k_s, &o);
             ILQG_DPROBE();
-            if(!(ILQG_ABLATE & 1)) ILQG_DERIVS_INLINE ok &= calcXUVariableAux(t, mp, k_s, &o);
+            [[clang::always_inline]] ok &= calcXUVariableAux(t, mp, k_s, &o);
             ILQG_DPROBE();
-            if(!(ILQG_ABLATE & 2)) ILQG_DERIVS_INLINE ok &= calcLAuxDeriv(t, mp, k_s, &o);
+            [[clang::always_inline]] ok &= calcLAuxDeriv(t, mp, k_s, &o);
             ILQG_DPROBE();
 #if ILQG_FACTORED
             if constexpr(FACT) {
@@ -223,23 +199,23 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
                 // (the products first: both functions begin with the sines and cosines of the auxiliaries, evaluated once
                 // for the two — by the one that runs first; behind the first derivatives, the 64 values would have to
                 // stay alive through their 400 assignments: 110 registers spilled)
-                if(!(ILQG_ABLATE & 8)) ILQG_DERIVS_INLINE ok &= bp_tensor_basis(t->fxx, t, k_s, o.p);
+                [[clang::always_inline]] ok &= bp_tensor_basis(t->fxx, t, k_s, o.p);
                 ILQG_DPROBE();
-                if(!(ILQG_ABLATE & 4)) ILQG_DERIVS_INLINE ok &= bp_derivsL_first(t, k_s, o.p);
+                [[clang::always_inline]] ok &= bp_derivsL_first(t, k_s, o.p);
                 ILQG_DPROBE();
             } else
 #endif
-#if ILQG_DEV_EL && ILQG_DEV_INLINE
+#if ILQG_DEV_EL
                 // (inline: x, u, the auxiliaries and the parameters are registers / LDS then.  As a call, the function reads them
                 // from scratch memory in between its stores — and a load, waited for, waits for every store issued before it:
                 // 550 such round trips per wavefront were 1.1 of its 1.26 ms, profiles/r6_stored_path.txt)
-                ILQG_DERIVS_INLINE ok &= bp_derivsL(t, k_s, o.p);
+                [[clang::always_inline]] ok &= bp_derivsL(t, k_s, o.p);
 #else
                 ok &= derivs_with_tensors(t, k_s, o.p);
 #endif
             // (the limits — which re-read u behind the 400 stores of the derivatives — moved in front of them, and the
             // products in front of the first derivatives: measured, no difference)
-            if(!(ILQG_ABLATE & 16)) ILQG_DERIVS_INLINE limitsU(t, k_s, o.p, P.N);
+            [[clang::always_inline]] limitsU(t, k_s, o.p, P.N);
 #if ILQG_DEV_EL
             {  // the limits (and, where somebody reads them, their signs and gradients) from the private element into the record
                 const int m = H.alone != 0.0 ? ilqgdev::ALONE : ilqgdev::TOGETHER;
@@ -269,12 +245,6 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
             }
 #endif
             ILQG_DPROBE();
-            if(ILQG_ABLATE & 64) {  // (timing experiment: the limits' 16 stores without the function)
-                for(int i = 0; i < NU; i++) {
-                    t->lower[i] = -1.0 - t->u[i];
-                    t->upper[i] = 1.0 - t->u[i];
-                }
-            }
         };
 #if ILQG_UNIFORM_GUARDS
         ok = run_guarded([&]() { body(); return ok; }, &H.alone);
@@ -302,12 +272,12 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
         multipliersFin_t mfin;
         load_mul_fin(P, b, mfin);
         multipliersFin_t *const mfp = HAS_MUL ? &mfin : nullptr;
-        ILQG_DERIVS_INLINE init_final(&fin, &o);
+        [[clang::always_inline]] init_final(&fin, &o);
         auto body = [&]() {
             for(int i = 0; i < NX; i++) fin.x[i] = nomp(P, P.N, b)[NOM_X + i];
-            ILQG_DERIVS_INLINE ok = calcFVariableAux(&fin, mfp, &o);
-            ILQG_DERIVS_INLINE ok &= calcFAuxDeriv(&fin, mfp, &o);
-            ILQG_DERIVS_INLINE ok &= bp_derivsF(&fin, P.N, o.p);
+            [[clang::always_inline]] ok = calcFVariableAux(&fin, mfp, &o);
+            [[clang::always_inline]] ok &= calcFAuxDeriv(&fin, mfp, &o);
+            [[clang::always_inline]] ok &= bp_derivsF(&fin, P.N, o.p);
         };
 #if ILQG_UNIFORM_GUARDS
         ok = run_guarded([&]() { body(); return ok; });
@@ -351,7 +321,7 @@ __global__ __launch_bounds__(ILQG_DERIVS_BLOCK) ILQG_DERIVS_ATTR void k_derivs_w
 // (test_derivative_records_in_parts_equal_the_per_lane_ones) and off by default (ILQG_DERIV_PARTS=1 turns it on).
 // ---------------------------------------------------------------------------
 // (compiled into the -DILQG_EXPERIMENTS libraries only, lib*_exp.so, which its test loads)
-#if ILQG_FACTORED && defined(ILQG_DERIV_PARTS) && !defined(ILQG_NO_SHARED_SINCOS) && ILQG_EXPERIMENTS
+#if ILQG_FACTORED && defined(ILQG_DERIV_PARTS) && ILQG_EXPERIMENTS
 #define ILQG_HAVE_DERIV_PARTS 1
 constexpr int DP_OUT = ILQG_DERIV_PART_OUT, DP_PARTS = ILQG_DERIV_PARTS, DP_NOUT = ILQG_DERIV_NOUT, DP_NPROD = ILQG_DERIV_NPROD;
 static_assert(DP_OUT == 16, "a part's outputs are stored by the 16 lanes of a DPP row");
@@ -475,15 +445,9 @@ struct FactoredSource : RecordSource<NX, NU, true, RecOffsets> {
             for(int q = 0; q < NTC; q++) t[NTX + NTU + q] = p.fetch(i * FACT_SLICE + SXX + SUU + 64 * q);
             // (entries of constant tables: folded when the loop is unrolled, as are the comparisons below)
             const int sxx = ilqg_tensor_slice_xx[i], suu = ilqg_tensor_slice_uu[i], sxu = ilqg_tensor_slice_xu[i];
-#ifdef ILQG_BASIS_READLANE  // (comparison build: the products by v_readlane)
-            g[0] = lane_bcast(product, sxx);
-            g[1] = lane_bcast(product, suu);
-            g[2] = lane_bcast(product, sxu);
-#else
             g[0] = pg.fetch(sxx);
             g[1] = (suu == sxx) ? g[0] : pg.fetch(suu);
             g[2] = (sxu == sxx) ? g[0] : ((sxu == suu) ? g[1] : pg.fetch(sxu));
-#endif
         };
         double cur[PER], nxt[PER], gc[3], gn[3];
         fetch(std::integral_constant<int, 0>{}, cur, gc);
@@ -611,14 +575,6 @@ __device__ __forceinline__ int backward_sweep_wave(StepLds &S, const double *tab
 
 // back_pass + retry loop, one wavefront (= one block) per trajectory of the chunk.  single_sweep: 1 = the
 // drop-in back_pass() (caller owns the retry loop)
-#ifndef ILQG_WAVE_OCC
-#define ILQG_WAVE_OCC 1
-#endif
-#ifdef ILQG_WAVE_OCC_MAX
-#define ILQG_WAVE_ATTR __attribute__((amdgpu_waves_per_eu(ILQG_WAVE_OCC, ILQG_WAVE_OCC_MAX)))
-#else
-#define ILQG_WAVE_ATTR
-#endif
 // FACT: factored records (see FactoredSource); ILQG_FACT_WAVES wavefronts per workgroup share the coefficient tables
 // back_pass + retry loop of ONE trajectory (b; slot bw of the chunk's records) on the calling wavefront
 template <bool FACT>
@@ -657,7 +613,7 @@ __device__ __forceinline__ void backward_of_trajectory(StepLds &S, const double 
 // trajectory was quick does not wait for the slow ones of its workgroup.  Every wavefront leaves the loop: the counter
 // only grows.
 template <bool FACT>
-__global__ __launch_bounds__(64 * (FACT ? ILQG_FACT_WAVES : 1), FACT ? 1 : ILQG_WAVE_OCC) ILQG_WAVE_ATTR
+__global__ __launch_bounds__(64 * (FACT ? ILQG_FACT_WAVES : 1), 1)
 void k_backward_wave(DevPtrs P, ilqg_dev_opts_t O, int single_sweep, int chunk_first, int chunk_count) {
     extern __shared__ double wave_lds[];  // [coefficient tables][per wavefront: step block, products]
     constexpr int WAVES = FACT ? ILQG_FACT_WAVES : 1;
@@ -972,12 +928,6 @@ __global__ __launch_bounds__(64 * QUAD_WAVES) void k_backward_quad(DevPtrs P, il
                 }
             }
             if(!any_lane(busy)) break;  // every row is out of work and the queue is used up
-#if defined(ILQG_QUAD_PRIO) && ILQG_QUAD_PRIO
-            // (experiment: a wavefront with a row on its second or later sweep — a long trajectory, the kernel's critical path —
-            // issues ahead of its SIMD's other wavefront)
-            if(any_lane(busy && calls > 0)) __builtin_amdgcn_s_setprio(3);
-            else __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef ILQG_PROFILE_SECTIONS
             prof.wave_steps++;
 #endif
