@@ -360,6 +360,10 @@ void drv_set_multipliers(drv_t *d, const double *el, const double *fin) {
 
 int drv_get_log_linesearch(drv_t *d, int iter) { return d->o.log_linesearch[iter]; }
 
+/* back_pass() calls of the last drv_solve() that no line search followed: the sweeps in front of an exit from the retry
+ * loop (iLQG.c:274) or of the gradient exit (iLQG.c:297-303); the trace has the others, iteration by iteration */
+int drv_get_bp_calls_pending(drv_t *d) { return d->bp_calls_pending; }
+
 /* trace of the last drv_solve(): returns count; each array has room for `cap` */
 int drv_get_trace(drv_t *d, int cap, double *lambda, double *gnorm, double *dV0, double *dV1,
                   double *cost, double *newcost, int *alpha_idx, int *bp_calls) {

@@ -194,6 +194,8 @@ def _bind(lib):
     if hasattr(lib, "drv_update_multipliers"):
         lib.drv_update_multipliers.argtypes = [C.c_void_p, C.c_int]
         lib.drv_cost_resweep.argtypes = [C.c_void_p]
+    if hasattr(lib, "drv_get_bp_calls_pending"):
+        lib.drv_get_bp_calls_pending.argtypes = [C.c_void_p]
     if hasattr(lib, "drv_solve_many"):
         lib.drv_solve_many.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _ip, _ip]
     return lib
@@ -358,6 +360,11 @@ class Driver:
 
     def log_linesearch(self, it=0):
         return self.lib.drv_get_log_linesearch(self.h, it)
+
+    def bp_calls_pending(self):
+        """back_pass() calls of the last solve() behind which no line search ran (an exit of the retry loop, the gradient
+        exit); trace()["bp_calls"] has those of every iteration that reached its line search"""
+        return int(self.lib.drv_get_bp_calls_pending(self.h))
 
     def trace(self, cap=4096):
         arrs = [np.zeros(cap) for _ in range(6)]

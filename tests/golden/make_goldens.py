@@ -508,9 +508,20 @@ def multiplier_goldens():
     print("multiplier cases: %d arrays, %d bytes" % (len(out), os.path.getsize(MC.GOLDEN)))
 
 
+def lambda_goldens():
+    """tests/lambda_cases.py: the reference build's iLQG() from every case's entry (return value, iterations, lambdas, sweeps,
+    the last sweep's scalars; gains for one case per problem), its sequences and its mixed batches — results only"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lambda_cases as LC
+    with quiet():
+        out = LC.golden_of("ref")
+    np.savez_compressed(LC.GOLDEN, **out)
+    print("lambda cases: %d cases, %d sequences, %d arrays, %d bytes" % (len(LC.CASES), len(LC.SEQS), len(out), os.path.getsize(LC.GOLDEN)))
+
+
 def main(argv):
     """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases linesearch multipliers
-    synth synthp console vsref"""
+    lambda synth synthp console vsref"""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     groups = {
         "brachi": brachi_goldens,
@@ -523,6 +534,7 @@ def main(argv):
         "regtype2cases": regtype2_case_goldens,
         "linesearch": linesearch_goldens,
         "multipliers": multiplier_goldens,
+        "lambda": lambda_goldens,
         "synth": lambda: [synth_goldens(fd) for fd in (0, 1)],
         "synthp": lambda: synth_goldens(1, N=12, problem="synth16p", SYN_PARAMS=SYNP_PARAMS_TIGHT),
         "console": console_goldens,
