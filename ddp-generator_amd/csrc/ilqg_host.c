@@ -603,6 +603,102 @@ int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, co
     return shift(c, "ilqg_batch_shift_device", 1, steps, x0_new, u_tail, stream);
 }
 
+/* Candidates per agent: the batch as segments of K consecutive slots (include/ilqg_batch.h).  The kernels rely on a segment
+ * never straddling a group, a tile or a wavefront: K is a power of two up to 64 and divides B, and every group starts at a
+ * multiple of 64 (ilqg_batch_create_groups), hence of K; both are checked here, before anything is touched. */
+static int segments(ilqg_batch_t *c, const char *who, int K) {
+    int g;
+    if(K < 1 || K > 64 || (K & (K - 1)) != 0) {
+        snprintf(c->err, sizeof(c->err), "%s: K = %d, must be one of 1, 2, 4, 8, 16, 32, 64", who, K);
+        return 1;
+    }
+    if(c->B % K != 0) {
+        snprintf(c->err, sizeof(c->err), "%s: K = %d does not divide the batch of %d trajectories (B %% K must be 0)", who, K, c->B);
+        return 1;
+    }
+    EACH_GROUP(g)
+        if(c->first[g] % K != 0 || c->count[g] % K != 0) {
+            snprintf(c->err, sizeof(c->err), "%s: K = %d: group %d (trajectories %d .. %d) would cut a segment", who, K, g, c->first[g],
+                     c->first[g] + c->count[g] - 1);
+            return 1;
+        }
+    return 0;
+}
+#define SEG_AT(p, w) ((p) ? (p) + (size_t)(c->first[g] / K) * (w) : NULL)
+#define SLOT_AT(p, w) ((p) ? (p) + (size_t)c->first[g] * (w) : NULL)
+
+static int best_of(ilqg_batch_t *c, const char *who, int on_device, int K, const double *score, int *winner, double *best, int *n_eligible,
+                   void *stream) {
+    const named_ptr_t ptrs[] = {{score, "score"}, {winner, "winner"}, {best, "best"}, {n_eligible, "n_eligible"}};
+    int g;
+    if(segments(c, who, K)) return 1;
+    if(!winner) {
+        snprintf(c->err, sizeof(c->err), "%s: winner is NULL (the output, [B / K])", who);
+        return 1;
+    }
+    if(on_device && (device_ptrs(c, who, ptrs, 4) || stream_in(c, stream, "best_of: stream"))) return 1;
+    EACH_GROUP(g) {
+        if(ilqg_dev_best_of(c->dev[g], K, c->first[g], SLOT_AT(score, 1), SEG_AT(winner, 1), SEG_AT(best, 1), SEG_AT(n_eligible, 1), on_device))
+            return fail(c, who);
+        if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "best_of: stream");
+    }
+    return 0;
+}
+
+int ilqg_batch_best_of(ilqg_batch_t *c, int K, const double *score, int *winner, double *best, int *n_eligible) {
+    return best_of(c, "ilqg_batch_best_of", 0, K, score, winner, best, n_eligible, NULL);
+}
+
+int ilqg_batch_best_of_device(ilqg_batch_t *c, int K, const double *score, int *winner, double *best, int *n_eligible, void *stream) {
+    return best_of(c, "ilqg_batch_best_of_device", 1, K, score, winner, best, n_eligible, stream);
+}
+
+/* ilqg_batch_shift with the winner's plan as every slot's source: one kernel per group moves u, x_0, the caller's tail and du
+ * (ilqg_dev_shift_winners), then exactly ilqg_batch_init's roll-out and entry state */
+static int shift_winners(ilqg_batch_t *c, const char *who, int on_device, int K, const int *winner, int steps, const double *x0_new,
+                         const double *u_tail, const double *du, void *stream) {
+    const named_ptr_t ptrs[] = {{winner, "winner"}, {x0_new, "x0_new"}, {u_tail, "u_tail"}, {du, "du"}};
+    int g, s;
+    if(segments(c, who, K)) return 1;
+    if(steps < 0 || steps >= c->N) {
+        snprintf(c->err, sizeof(c->err), "%s: steps = %d, must be in 0 .. n_hor - 1 = %d", who, steps, c->N - 1);
+        return 1;
+    }
+    if(!winner) {
+        snprintf(c->err, sizeof(c->err), "%s: winner is NULL ([B / K]; -1 for a segment whose slots shift their own plans)", who);
+        return 1;
+    }
+    if(on_device) {
+        if(device_ptrs(c, who, ptrs, 4)) return 1;
+    } else {
+        for(s = 0; s < c->B / K; s++)
+            if(winner[s] != -1 && (winner[s] < s * K || winner[s] >= s * K + K)) {
+                snprintf(c->err, sizeof(c->err), "%s: winner[%d] = %d is outside segment %d (slots %d .. %d; -1: none)", who, s, winner[s], s,
+                         s * K, s * K + K - 1);
+                return 1;
+            }
+    }
+    if(push_config(c)) return 1;
+    if(on_device && stream_in(c, stream, "shift_winners: stream")) return 1;
+    EACH_GROUP(g) {
+        if(ilqg_dev_shift_winners(c->dev[g], K, c->first[g], SEG_AT(winner, 1), steps, SEG_AT(x0_new, N_X), SEG_AT(u_tail, (size_t)steps * N_U),
+                                  SLOT_AT(du, (size_t)c->N * N_U), on_device))
+            return fail(c, who);
+        /* behind the kernel that reads the caller's memory, not behind the roll-out */
+        if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift_winners: stream");
+    }
+    return restart(c);
+}
+
+int ilqg_batch_shift_winners(ilqg_batch_t *c, int K, const int *winner, int steps, const double *x0_new, const double *u_tail, const double *du) {
+    return shift_winners(c, "ilqg_batch_shift_winners", 0, K, winner, steps, x0_new, u_tail, du, NULL);
+}
+
+int ilqg_batch_shift_winners_device(ilqg_batch_t *c, int K, const int *winner, int steps, const double *x0_new, const double *u_tail,
+                                    const double *du, void *stream) {
+    return shift_winners(c, "ilqg_batch_shift_winners_device", 1, K, winner, steps, x0_new, u_tail, du, stream);
+}
+
 /* a batch entry that runs whole rounds cannot move the window of a per-time-step parameter: refused, and the loop named */
 static int no_step_params(ilqg_batch_t *c, const char *who) {
     int i;
@@ -1993,7 +2089,7 @@ int ilqg_batch_timing(ilqg_batch_t *c, int enable) {
     EACH_GROUP(g) if(ilqg_dev_timing(c->dev[g], enable)) return fail(c, "timing");
     return 0;
 }
-int ilqg_batch_kernel_count(void) { return ILQG_K_COUNT; }
+int ilqg_batch_kernel_count(void) { return ILQG_K_TOTAL; }
 const char *ilqg_batch_kernel_name(int k) { return ilqg_dev_kernel_name(k); }
 /* summed over the groups (whose kernels overlap in time) */
 int ilqg_batch_get_timing(ilqg_batch_t *c, int kernel, int *launches, double *total_ms) {
@@ -2548,6 +2644,55 @@ int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const dou
         if(ilqg_batch_shift(m->shard[g], steps, x0_new ? x0_new + (size_t)m->first[g] * N_X : NULL,
                             u_tail ? u_tail + (size_t)m->first[g] * (steps > 0 ? steps : 0) * N_U : NULL))
             return multi_fail(m, g);
+    return 0;
+}
+/* candidates per agent, per shard: a shard boundary must not cut a segment; winner[] is absolute in the whole batch */
+static int multi_segments(ilqg_multi_t *m, const char *who, int K) {
+    int g;
+    if(K < 1 || K > 64 || (K & (K - 1)) != 0) return 0;  /* (the shard refuses, naming the values K may have) */
+    EACH_SHARD(g)
+        if(m->first[g] % K != 0) {
+            snprintf(m->err, sizeof(m->err), "%s: K = %d: the shard of device %d starts at trajectory %d, which is not a multiple of K: the shard "
+                     "boundary would cut a segment (choose a batch whose shards of %d trajectories are whole segments)", who, K, m->device[g],
+                     m->first[g], m->per);
+            return 1;
+        }
+    return 0;
+}
+int ilqg_multi_best_of(ilqg_multi_t *m, int K, const double *score, int *winner, double *best, int *n_eligible) {
+    int g, s;
+    if(multi_segments(m, "ilqg_multi_best_of", K)) return 1;
+    EACH_SHARD(g) {
+        const size_t at = K > 0 ? (size_t)(m->first[g] / K) : 0;
+        if(ilqg_batch_best_of(m->shard[g], K, score ? score + m->first[g] : NULL, winner ? winner + at : NULL, best ? best + at : NULL,
+                              n_eligible ? n_eligible + at : NULL))
+            return multi_fail(m, g);
+        for(s = 0; s < m->count[g] / K; s++)
+            if(winner[at + s] >= 0) winner[at + s] += m->first[g];
+    }
+    return 0;
+}
+int ilqg_multi_shift_winners(ilqg_multi_t *m, int K, const int *winner, int steps, const double *x0_new, const double *u_tail, const double *du) {
+    const size_t st = steps > 0 ? (size_t)steps : 0;
+    int g, s, rc;
+    if(multi_segments(m, "ilqg_multi_shift_winners", K)) return 1;
+    /* every refusal of a winner before the first shard moves (the shards see shard-local indices) */
+    for(s = 0; winner && K >= 1 && K <= 64 && m->B % K == 0 && s < m->B / K; s++)
+        if(winner[s] != -1 && (winner[s] < s * K || winner[s] >= s * K + K)) {
+            snprintf(m->err, sizeof(m->err), "ilqg_multi_shift_winners: winner[%d] = %d is outside segment %d (slots %d .. %d; -1: none)", s,
+                     winner[s], s, s * K, s * K + K - 1);
+            return 1;
+        }
+    EACH_SHARD(g) {
+        const size_t at = K > 0 ? (size_t)(m->first[g] / K) : 0;
+        const int n = (K > 0 && winner) ? m->count[g] / K : 0;
+        int *local = n > 0 ? (int *)malloc(sizeof(int) * (size_t)n) : NULL;
+        for(s = 0; s < n; s++) local[s] = winner[at + s] == -1 ? -1 : winner[at + s] - m->first[g];
+        rc = ilqg_batch_shift_winners(m->shard[g], K, local, steps, x0_new ? x0_new + at * N_X : NULL, u_tail ? u_tail + at * st * N_U : NULL,
+                                      du ? du + (size_t)m->first[g] * (size_t)m->N * N_U : NULL);
+        free(local);
+        if(rc) return multi_fail(m, g);
+    }
     return 0;
 }
 int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l, double *L, double *cost) {

@@ -982,6 +982,8 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 
 #include "k_shift.inc"  // k_shift_lane / k_shift_wave, k_put_u_steps, k_log_steps (receding horizon)
 
+#include "k_best.inc"  // k_best_of, k_shift_winners_lane / k_shift_winners_wave (candidates per agent)
+
 #include "k_mpc_io.inc"  // k_head, k_shift_param (the control interval of a caller with its own plant)
 
 #include "k_policy.inc"  // k_policy (roll-outs of every plan's feedback policy from the caller's starts)

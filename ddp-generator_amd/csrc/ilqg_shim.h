@@ -127,6 +127,12 @@ enum {
     ILQG_K_HISTORY,  /* k_history (ilqg_dev_update of a context with a history) */
     ILQG_K_COUNT
 };
+/* timing slots added since: a second list that continues the first, so that every index above keeps its meaning */
+enum {
+    ILQG_K_BEST_OF = ILQG_K_COUNT, /* candidates per agent: k_best_of (ilqg_dev_best_of) */
+    ILQG_K_SHIFT_WINNERS,          /*                       k_shift_winners_lane / _wave (ilqg_dev_shift_winners) */
+    ILQG_K_TOTAL
+};
 
 /* fields of an entry of the iteration history (ilqg_dev_set_history): doubles ... */
 enum {
@@ -219,6 +225,21 @@ int ilqg_dev_rollout_init(ilqg_dev_t *d);     /* forward_pass(alpha = 0) + swap 
 int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0);
 /* the caller's tail behind a shift: host [batch][steps][N_U] into the last `steps` time steps of the controls */
 int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps);
+/* Candidates per agent: the context's trajectories as batch / K segments of K consecutive slots, K one of 1, 2, 4, .. 64
+ * and a divisor of batch and of `first`, the batch-absolute index of the context's first trajectory (refused otherwise: the
+ * kernels rely on a segment never leaving a tile of 64).  on_device = 0: the arrays are host memory (staged, one wait);
+ * else device memory of the context's device, used on the context's stream without a wait.
+ * best_of: per segment the eligible slot (score finite, status not ILQG_ST_INIT_FAILED) with the smallest score, equal scores
+ * to the lowest index: winner [batch / K] batch-absolute or -1, best [batch / K] its score or NaN, n_eligible [batch / K];
+ * score [batch] or NULL = the current cost; best / n_eligible may be NULL.  Changes nothing of the context (k_best_of).
+ * shift_winners: ilqg_dev_shift with use_plan_x0 = (x0_new == NULL), except that slot b of segment g reads the plan of slot
+ * winner[g] (batch-absolute) wherever that lives, takes x0_new [batch / K][N_X] / u_tail [batch / K][steps][N_U] of its
+ * SEGMENT and adds du [batch][n_hor][N_U] (any of the three NULL).  winner[g] = -1, and on the device any value outside
+ * segment g, makes every slot of the segment its own winner.  One kernel (k_shift_winners_lane / _wave); the location
+ * indices are cleared as ilqg_dev_shift clears them. */
+int ilqg_dev_best_of(ilqg_dev_t *d, int K, int first, const double *score, int *winner, double *best, int *n_eligible, int on_device);
+int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, int steps, const double *x0_new, const double *u_tail, const double *du,
+                           int on_device);
 /* The control interval of a caller with its own plant.  head: the first `steps` steps of every CURRENT plan, read where it
  * lives (nothing moves home), trajectory-major: x [batch][steps][N_X], u / l [batch][steps][N_U], L [batch][steps][N_U*N_X],
  * cost [batch]; any pointer may be NULL; 1 <= steps <= n_hor.  ilqg_dev_head fills host arrays (one wait at most),

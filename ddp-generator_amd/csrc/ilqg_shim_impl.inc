@@ -240,13 +240,13 @@ struct ilqg_dev : DevBuffers {
     struct Span { int kernel; hipEvent_t a, b; };
     std::vector<Span> spans;
     std::vector<hipEvent_t> event_pool;  // events of drained spans, reused: none is created while a window is timed
-    double t_ms[ILQG_K_COUNT];
-    int t_n[ILQG_K_COUNT];
+    double t_ms[ILQG_K_TOTAL];
+    int t_n[ILQG_K_TOTAL];
     // launches of one kernel on the context's two streams overlap in the event clock (the later one waits for the chip):
     // t_busy is the length of the UNION of a kernel's launch intervals, measured against an event recorded when timing
     // was switched on
     hipEvent_t epoch;
-    double t_busy[ILQG_K_COUNT];
+    double t_busy[ILQG_K_TOTAL];
 };
 
 namespace {
@@ -385,7 +385,7 @@ int drain_spans(ilqg_dev *d) {
     HIP_TRY(hipStreamSynchronize(d->stream));
     if(d->stream2) HIP_TRY(hipStreamSynchronize(d->stream2));
     if(d->roll) HIP_TRY(hipStreamSynchronize(d->roll));
-    std::vector<std::pair<float, float>> iv[ILQG_K_COUNT];
+    std::vector<std::pair<float, float>> iv[ILQG_K_TOTAL];
     for(auto &s : d->spans) {
         float ms = 0.f, t0 = 0.f;
         hipEventElapsedTime(&ms, s.a, s.b);
@@ -396,7 +396,7 @@ int drain_spans(ilqg_dev *d) {
         d->event_pool.push_back(s.b);
     }
     (void)hipGetLastError();
-    for(int k = 0; k < ILQG_K_COUNT; k++) {  // union of the intervals of this batch of spans
+    for(int k = 0; k < ILQG_K_TOTAL; k++) {  // union of the intervals of this batch of spans
         std::sort(iv[k].begin(), iv[k].end());
         float end = -1.f;
         for(auto &q : iv[k]) {
@@ -573,6 +573,9 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_multipliers", "k_search[stage 1]", "k_search[stage 2]", "k_adopt_home + k_commit", "k_shift",
                                               "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant", "k_shift_param_rows",
                                               "k_shift_windows", "k_history"};
+    // (the slots behind the history's, in ilqg_shim.h's second list)
+    static const char *later[ILQG_K_TOTAL - ILQG_K_COUNT] = {"k_best_of", "k_shift_winners"};
+    if(k >= ILQG_K_COUNT && k < ILQG_K_TOTAL) return later[k - ILQG_K_COUNT];
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
 
@@ -1295,6 +1298,119 @@ int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps) {
     }
     HIP_TRY(hipGetLastError());
     return io_done(d);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Candidates per agent (k_best.inc): the context's trajectories as segments of K consecutive slots
+// ---------------------------------------------------------------------------------------------------------------------
+// what the kernels rely on: K a power of two up to the wavefront, whole segments in the context (whose tiles are 64 wide)
+static int segments_ok(ilqg_dev_t *d, int K, int first) {
+    if(K < 1 || K > WAVE || (K & (K - 1)) != 0) {
+        g_err = "K must be one of 1, 2, 4, 8, 16, 32, 64";
+        return 0;
+    }
+    if(d->B % K != 0 || first < 0 || first % K != 0) {
+        g_err = "K must divide the group's size and its first trajectory";
+        return 0;
+    }
+    return 1;
+}
+// a piece of `bytes` of a staged transfer that is cut into slices 256 bytes apart: its offset, and the total moves on
+static size_t slice(size_t &total, size_t bytes) {
+    const size_t at = total;
+    total += (bytes + 255) & ~(size_t)255;
+    return at;
+}
+
+// The one launch of k_best_of, on device memory.  Reads costs / the caller's scores and the status; writes nothing of the context.
+static int launch_best_of(ilqg_dev_t *d, int K, int first, const double *score, int *winner, double *best, int *n_eligible) {
+    {
+        Timed t(d, ILQG_K_BEST_OF);
+        hipLaunchKernelGGL(k_best_of, dim3(d->Bp / WAVE), dim3(WAVE), 0, d->stream, d->P, K, first, score, winner, best, n_eligible);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ilqg_dev_best_of(ilqg_dev_t *d, int K, int first, const double *score, int *winner, double *best, int *n_eligible, int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!segments_ok(d, K, first)) return 1;
+    if(!winner) {
+        g_err = "best_of: winner is NULL";
+        return 1;
+    }
+    if(on_device) return launch_best_of(d, K, first, score, winner, best, n_eligible);
+    const size_t G = (size_t)(d->B / K);
+    size_t total = 0;
+    const size_t o_score = slice(total, score ? d->B * sizeof(double) : 0), o_win = slice(total, G * sizeof(int));
+    const size_t o_best = slice(total, best ? G * sizeof(double) : 0), o_n = slice(total, n_eligible ? G * sizeof(int) : 0);
+    void *dev, *pin;
+    if(stage(d, total, &dev, &pin)) return 1;
+    char *const dv = (char *)dev, *const pv = (char *)pin;
+    if(score && stage_in(d, dv + o_score, pin ? pv + o_score : nullptr, score, d->B * sizeof(double))) return 1;
+    if(launch_best_of(d, K, first, score ? (const double *)(dv + o_score) : nullptr, (int *)(dv + o_win), best ? (double *)(dv + o_best) : nullptr,
+                      n_eligible ? (int *)(dv + o_n) : nullptr))
+        return 1;
+    void *const host[3] = {winner, best, n_eligible};
+    const size_t off[3] = {o_win, o_best, o_n}, bytes[3] = {G * sizeof(int), G * sizeof(double), G * sizeof(int)};
+    for(int i = 0; i < 3; i++) {
+        if(!host[i]) continue;
+        void *to = pin ? (void *)(pv + off[i]) : host[i];
+        HIP_TRY(hipMemcpyAsync(to, dv + off[i], bytes[i], hipMemcpyDeviceToHost, d->stream));
+        if(pin) d->pending.push_back({host[i], to, bytes[i], 0});
+    }
+    if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
+    return 0;
+}
+
+// ilqg_dev_shift with the winner's plan as every slot's source: one pass that brings U home, as there, so the location
+// indices are cleared behind it and the all_home() of the initial roll-out that follows has nothing left to copy.
+int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, int steps, const double *x0_new, const double *u_tail, const double *du,
+                           int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!segments_ok(d, K, first)) return 1;
+    if(steps < 0 || steps >= d->N) {
+        g_err = "ilqg_dev_shift_winners: steps must be in 0 .. n_hor - 1";
+        return 1;
+    }
+    if(!winner) {
+        g_err = "ilqg_dev_shift_winners: winner is NULL";
+        return 1;
+    }
+    if(steps == 0) u_tail = nullptr;  // (no tail step to fill)
+    if(!on_device) {
+        const size_t G = (size_t)(d->B / K);
+        size_t total = 0;
+        const size_t b_win = G * sizeof(int), b_x0 = x0_new ? G * NX * sizeof(double) : 0, b_tail = u_tail ? G * steps * NU * sizeof(double) : 0;
+        const size_t b_du = du ? (size_t)d->B * d->N * NU * sizeof(double) : 0;
+        const size_t o_win = slice(total, b_win), o_x0 = slice(total, b_x0), o_tail = slice(total, b_tail), o_du = slice(total, b_du);
+        void *dev, *pin;
+        if(stage(d, total, &dev, &pin)) return 1;
+        char *const dv = (char *)dev, *const pv = (char *)pin;
+        if(stage_in(d, dv + o_win, pin ? pv + o_win : nullptr, winner, b_win)) return 1;
+        if(x0_new && stage_in(d, dv + o_x0, pin ? pv + o_x0 : nullptr, x0_new, b_x0)) return 1;
+        if(u_tail && stage_in(d, dv + o_tail, pin ? pv + o_tail : nullptr, u_tail, b_tail)) return 1;
+        if(du && stage_in(d, dv + o_du, pin ? pv + o_du : nullptr, du, b_du)) return 1;
+        winner = (const int *)(dv + o_win);
+        if(x0_new) x0_new = (const double *)(dv + o_x0);
+        if(u_tail) u_tail = (const double *)(dv + o_tail);
+        if(du) du = (const double *)(dv + o_du);
+    }
+    {
+        Timed t(d, ILQG_K_SHIFT_WINNERS);
+#if ILQG_WAVE_MAP
+        hipLaunchKernelGGL(k_shift_winners_wave, dim3(d->B / K), dim3(SHIFT_BLOCK), 0, d->stream, d->P, K, first, winner, steps, x0_new, u_tail, du);
+#else
+        hipLaunchKernelGGL(k_shift_winners_lane, dim3((unsigned)((size_t)(NX > NU ? NX : NU) * d->Bp / WAVE)), dim3(WAVE * SHIFT_WAVES), 0, d->stream, d->P, K,
+                           first, winner, steps, x0_new, u_tail, du);
+#endif
+    }
+    HIP_TRY(hipGetLastError());
+#if !ILQG_WAVE_MAP
+    if(d->loc_set >= 0) HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
+    d->loc_set = -1;
+#endif
+    return on_device ? 0 : io_done(d);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2575,7 +2691,7 @@ int ilqg_dev_timing(ilqg_dev_t *d, int enable) {
 /* length of the union of the launch intervals of a kernel since timing was switched on (ms): what the kernel occupied
  * of the wall clock, however its launches on different streams overlap in the event clock */
 int ilqg_dev_get_busy(ilqg_dev_t *d, int kernel, double *busy_ms) {
-    if(kernel < 0 || kernel >= ILQG_K_COUNT) {
+    if(kernel < 0 || kernel >= ILQG_K_TOTAL) {
         g_err = "ilqg_dev_get_busy: bad kernel id";
         return 1;
     }
@@ -2585,7 +2701,7 @@ int ilqg_dev_get_busy(ilqg_dev_t *d, int kernel, double *busy_ms) {
 }
 
 int ilqg_dev_get_timing(ilqg_dev_t *d, int kernel, int *launches, double *total_ms) {
-    if(kernel < 0 || kernel >= ILQG_K_COUNT) {
+    if(kernel < 0 || kernel >= ILQG_K_TOTAL) {
         g_err = "ilqg_dev_get_timing: bad kernel id";
         return 1;
     }

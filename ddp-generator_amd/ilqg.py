@@ -111,6 +111,99 @@ def _cuda_address(a, shape, device, what):
     return C.c_void_p(a.data_ptr() or None)
 
 
+def _cuda_int_address(a, shape, device, what):
+    """_cuda_address for an int32 tensor (the winners of best_of / shift_winners)"""
+    if "int32" not in str(a.dtype):
+        raise IlqgError("%s: a tensor on the device must be int32, not %s" % (what, a.dtype))
+    if tuple(a.shape) != tuple(shape):
+        raise IlqgError("%s: shape %s, expected %s" % (what, tuple(a.shape), tuple(shape)))
+    if not a.is_contiguous():
+        raise IlqgError("%s: a tensor on the device must be contiguous" % what)
+    if a.device.index != device:
+        raise IlqgError("%s: on %s, the solver is on GPU %d" % (what, a.device, device))
+    return C.c_void_p(a.data_ptr() or None)
+
+
+SEGMENT_SIZES = (1, 2, 4, 8, 16, 32, 64)
+
+
+def _segments(who, B, K):
+    """the number of segments of K consecutive slots in a batch of B (include/ilqg_batch.h, candidates per agent)"""
+    try:
+        ok = int(K) == K and int(K) in SEGMENT_SIZES
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise IlqgError("%s: K = %r, must be one of 1, 2, 4, 8, 16, 32, 64" % (who, K))
+    if B % int(K):
+        raise IlqgError("%s: K = %d does not divide the batch of %d trajectories (B %% K must be 0)" % (who, int(K), B))
+    return B // int(K)
+
+
+def _host_shaped(who, what, a, shape, dtype=np.float64):
+    """an optional host array argument of exactly that shape (no broadcasting, no reshaping of another size)"""
+    if a is None:
+        return None
+    if _is_cuda(a):
+        raise IlqgError("%s: %s is a tensor on the device and another argument is in host memory: pass all of them the same way" % (who, what))
+    a = np.asarray(a)
+    if a.shape != tuple(shape):
+        raise IlqgError("%s: %s has shape %s, expected %s" % (who, what, a.shape, tuple(shape)))
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _best_of(solver, prefix, K, score, device):
+    """BatchSolver.best_of / MultiSolver.best_of"""
+    who = "best_of"
+    G = _segments(who, solver.B, K)
+    if not device:
+        entry = _receding_entry(solver.lib, prefix + "best_of")
+        if _is_cuda(score):
+            raise IlqgError("best_of: score is a tensor on the device: pass device=True")
+        score = _host_shaped(who, "score", score, (solver.B,))
+        winner, best, n = np.full(G, -1, dtype=np.int32), np.zeros(G), np.zeros(G, dtype=np.int32)
+        solver._ck(entry(solver.h, int(K), _address(score), _address(winner), _address(best), _address(n)))
+        return winner, best, n
+    entry = _receding_entry(solver.lib, prefix + "best_of_device")
+    if score is not None and not _is_cuda(score):
+        raise IlqgError("best_of: score is in host memory: with device=True it is a float64 torch tensor on the solver's GPU")
+    ps = _cuda_address(score, (solver.B,), solver.device, "best_of: score")
+    torch, dev, stream = _torch_stream(solver.device)
+    winner = torch.empty(G, dtype=torch.int32, device=dev)
+    best = torch.empty(G, dtype=torch.float64, device=dev)
+    n = torch.empty(G, dtype=torch.int32, device=dev)
+    solver._ck(entry(solver.h, int(K), ps, *[C.c_void_p(t.data_ptr() or None) for t in (winner, best, n)], stream))
+    return winner, best, n
+
+
+def _shift_winners(solver, prefix, K, winner, steps, x0, u_tail, du, may_be_device):
+    """BatchSolver.shift_winners / MultiSolver.shift_winners"""
+    who = "shift_winners"
+    G = _segments(who, solver.B, K)
+    nx, nu, n = solver.problem.nx, solver.problem.nu, max(int(steps), 0)
+    if winner is None:
+        raise IlqgError("shift_winners: winner is None (one slot index per segment, [B / K]; -1 for a segment whose slots keep their own plans)")
+    args = (("winner", winner, (G,)), ("x0", x0, (G, nx)), ("u_tail", u_tail, (G, n, nu)), ("du", du, (solver.B, solver.N, nu)))
+    if any(_is_cuda(a) for _, a, _ in args):
+        if not may_be_device:
+            raise IlqgError("shift_winners: MultiSolver takes host arrays only")
+        entry = _receding_entry(solver.lib, prefix + "shift_winners_device")
+        for what, a, _ in args:
+            if a is not None and not _is_cuda(a):
+                raise IlqgError("shift_winners: %s is in host memory and another argument on the device: pass all of them the same way" % what)
+        pw = _cuda_int_address(winner, (G,), solver.device, "shift_winners: winner")
+        ptr = [_cuda_address(a, shape, solver.device, "shift_winners: " + what) for what, a, shape in args[1:]]
+        solver._ck(entry(solver.h, int(K), pw, int(steps), *ptr, _torch_stream(solver.device)[2]))
+        return
+    entry = _receding_entry(solver.lib, prefix + "shift_winners")
+    w = np.asarray(winner)
+    if w.shape != (G,) or not np.issubdtype(w.dtype, np.integer):
+        raise IlqgError("shift_winners: winner must be %d integers (one per segment, [B / K]), not %s of shape %s" % (G, w.dtype, w.shape))
+    w = np.ascontiguousarray(w, dtype=np.int32)
+    host = [_host_shaped(who, what, a, shape) for what, a, shape in args[1:]]
+    solver._ck(entry(solver.h, int(K), _address(w), int(steps), *[_address(a) for a in host]))
+
+
 def _outputs(shapes, order, torch=None, dev=None):
     """(the outputs of one library call, their addresses in the entry's order — None for one left out): numpy arrays, or
     with torch tensors on `dev`; float64 but for `ok`"""
@@ -554,6 +647,13 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_multi_get_history.argtypes = [v, C.c_char_p, v]
         lib.ilqg_multi_get_history_int.argtypes = [v, C.c_char_p, v]
         lib.ilqg_multi_history_cap.argtypes = [v]
+    if hasattr(lib, "ilqg_batch_best_of"):  # (and for the candidates per agent)
+        lib.ilqg_batch_best_of.argtypes = [v, C.c_int, v, v, v, v]
+        lib.ilqg_batch_best_of_device.argtypes = [v, C.c_int, v, v, v, v, v]
+        lib.ilqg_batch_shift_winners.argtypes = [v, C.c_int, v, C.c_int, v, v, v]
+        lib.ilqg_batch_shift_winners_device.argtypes = [v, C.c_int, v, C.c_int, v, v, v, v]
+        lib.ilqg_multi_best_of.argtypes = [v, C.c_int, v, v, v, v]
+        lib.ilqg_multi_shift_winners.argtypes = [v, C.c_int, v, C.c_int, v, v, v]
     if hasattr(lib, "ilqg_batch_solve_stream_rows"):  # (and for a stream whose starts bring rows, windows and a history)
         names = C.POINTER(C.c_char_p)
         lib.ilqg_batch_solve_stream_rows.argtypes = [v, C.c_int, v, v, C.c_int, names, v, C.c_int, names, C.POINTER(v),
@@ -789,6 +889,27 @@ class BatchSolver:
             return
         x0, u_tail = _optional(x0, (self.B, nx)), _optional(u_tail, (self.B, n, nu))
         self._ck(_receding_entry(self.lib, "ilqg_batch_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
+
+    def best_of(self, K, score=None, device=False):
+        """candidates per agent: the batch read as G = B / K segments of K consecutive slots (K one of 1, 2, 4, .. 64, B % K == 0),
+        and per segment the eligible slot with the smallest score (ilqg_batch_best_of).  score [B], or None = every slot's
+        current cost.  A slot is eligible iff its score is finite and its status is not 7 (the initial roll-out failed); equal
+        scores resolve to the lowest index (`<` on doubles: -0.0 and 0.0 tie).  Returns (winner [G] int32, batch-absolute, -1
+        where no slot is eligible; best [G], the winner's score, NaN for -1; n_eligible [G] int32).  Nothing in the batch
+        changes.  numpy arrays, or with device=True torch tensors on the solver's GPU (score then None or a float64 CUDA tensor),
+        filled in the order of torch's current stream without a host wait (ilqg_batch_best_of_device)."""
+        return _best_of(self, "ilqg_batch_", K, score, device)
+
+    def shift_winners(self, K, winner, steps, x0=None, u_tail=None, du=None):
+        """shift(), except that every slot b of segment g takes the plan of slot w = winner[g] in place of its own
+        (ilqg_batch_shift_winners): u'_b[k] = u_w[k+steps], tail = u_tail [G,steps,nu] or the winner's last control held, plus
+        du [B,N,nu] where given (one fp64 add; zero one slot's rows to keep the incumbent unperturbed); x0'_b = x0 [G,nx] or the
+        winner's x[steps]; then what init() does.  winner [G] integers, batch-absolute (best_of's); -1: the slots of that segment
+        shift their own plans.  A winner outside its segment is refused — except on the device, which cannot look: there it
+        counts as -1.  0 <= steps < N.  With any argument a CUDA torch tensor all of them must be (winner int32, the others
+        float64, contiguous, on the solver's GPU): they are read where they are, in the order of torch's current stream,
+        without a host copy or a host wait (ilqg_batch_shift_winners_device)."""
+        _shift_winners(self, "ilqg_batch_", K, winner, steps, x0, u_tail, du, True)
 
     def head(self, steps, gains=False, device=False):
         """the first `steps` steps of every current plan, read where it lives (nothing in the batch changes):
@@ -1222,6 +1343,15 @@ class MultiSolver:
         """BatchSolver.shift on every shard (ilqg_multi_shift)"""
         x0, u_tail = _optional(x0, (self.B, self.problem.nx)), _optional(u_tail, (self.B, max(int(steps), 0), self.problem.nu))
         self._ck(_receding_entry(self.lib, "ilqg_multi_shift")(self.h, int(steps), _address(x0), _address(u_tail)))
+
+    def best_of(self, K, score=None):
+        """BatchSolver.best_of of every shard (ilqg_multi_best_of), numpy arrays; winner is absolute in the whole batch.  Refused
+        when a shard's first trajectory is not a multiple of K."""
+        return _best_of(self, "ilqg_multi_", K, score, False)
+
+    def shift_winners(self, K, winner, steps, x0=None, u_tail=None, du=None):
+        """BatchSolver.shift_winners on every shard (ilqg_multi_shift_winners), numpy arrays"""
+        _shift_winners(self, "ilqg_multi_", K, winner, steps, x0, u_tail, du, False)
 
     def head(self, steps, gains=False):
         """BatchSolver.head of every shard (ilqg_multi_head), numpy arrays"""

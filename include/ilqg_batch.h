@@ -194,6 +194,42 @@ int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l,
 int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream);
 /* ilqg_batch_shift with x0_new / u_tail in DEVICE memory of the context's device (same layouts, same NULL meanings) */
 int ilqg_batch_shift_device(ilqg_batch_t *c, int steps, const double *x0_new, const double *u_tail, void *stream);
+/* CANDIDATES PER AGENT.  A batch of B = G * K slots read as G SEGMENTS of K consecutive slots: segment g is slots
+ * gK .. gK + K - 1, one agent's K candidate plans.  K is one of 1, 2, 4, 8, 16, 32, 64 and B % K == 0, anything else is an
+ * error.  (Groups of trajectories and the lane mapping's tiles are whole multiples of 64, so a segment never straddles a
+ * group, a tile or a wavefront; the kernels rely on it and the host checks it.)
+ *
+ * ilqg_batch_best_of chooses each segment's winner.  score [B], or NULL = every slot's current cost (as it stands, penalty
+ * terms included); otherwise the caller's own figure, e.g. a mean closed-loop cost out of ilqg_batch_policy_rollout_device.
+ * A slot is ELIGIBLE iff its score is finite (NaN, +Inf and -Inf are not) and its status is not ILQG_ST_INIT_FAILED.
+ * winner[g] = the batch-absolute index of the eligible slot of segment g with the smallest score; EQUAL SCORES RESOLVE TO
+ * THE LOWEST INDEX, the comparison is `<` on doubles, so -0.0 and 0.0 tie; -1 if no slot is eligible.  best[g] = the
+ * winner's score, NaN for -1; n_eligible[g] = the count of eligible slots; either may be NULL, winner may not.  The call
+ * CHANGES NOTHING in the batch; in particular it moves no trajectory home.  One launch of k_best_of per group.
+ * ilqg_batch_best_of_device: score and the outputs in DEVICE memory of the context's device, under the stream contract of
+ * ilqg_batch_head_device (event in, one event per group out, no host wait, no allocation in steady state, pointers
+ * checked before any launch). */
+int ilqg_batch_best_of(ilqg_batch_t *c, int K, const double *score /* [B] or NULL */, int *winner /* [G] */,
+                       double *best /* [G] or NULL */, int *n_eligible /* [G] or NULL */);
+int ilqg_batch_best_of_device(ilqg_batch_t *c, int K, const double *score, int *winner, double *best, int *n_eligible, void *stream);
+/* ilqg_batch_shift, except that every slot b of segment g takes the plan of slot w = winner[g] in place of its own.  With
+ * (x, u) the winner's current trajectory wherever it lives (a kept roll-out plane included):
+ *     u'_b[k] = (k + steps < n_hor ? u_w[k + steps] : (u_tail ? u_tail[g][k + steps - n_hor] : u_w[n_hor-1])) + (du ? du[b][k] : 0)
+ *     x0'_b   = x0_new ? x0_new[g] : x_w[steps]
+ * (the sum is one fp64 add; without du nothing is added), then exactly what ilqg_batch_shift does: the initial roll-out,
+ * which clamps u', re-initialises multipliers and may set status 7, and the solver entry state.  Gains, derivative
+ * records, histories, parameter rows and windows are left alone as ilqg_batch_shift leaves them.  x0_new and u_tail are
+ * per SEGMENT, du per SLOT; the caller keeps the incumbent unperturbed by zeroing one slot's rows of du.
+ * 0 <= steps < n_hor.  winner == NULL is refused.  winner[g] == -1: every slot of segment g is its own winner, i.e. shifts
+ * its own plan.  The host form refuses a winner outside its segment.  THE DEVICE FORM CANNOT LOOK: there the kernel treats
+ * a value outside segment g as -1.  With K = 1, winner[g] = g and du = NULL the result is ilqg_batch_shift's bit for bit.
+ * ilqg_batch_shift_winners_device: winner, x0_new, u_tail, du in DEVICE memory of the context's device (same layouts, same
+ * NULL meanings), stream contract as ilqg_batch_shift_device. */
+int ilqg_batch_shift_winners(ilqg_batch_t *c, int K, const int *winner /* [G] */, int steps,
+                             const double *x0_new /* [G][N_X] or NULL */, const double *u_tail /* [G][steps][N_U] or NULL */,
+                             const double *du /* [B][n_hor][N_U] or NULL */);
+int ilqg_batch_shift_winners_device(ilqg_batch_t *c, int K, const int *winner, int steps, const double *x0_new, const double *u_tail,
+                                    const double *du, void *stream);
 /* Every plan's feedback POLICY rolled out from n_starts starts per trajectory, on the device (one lane per roll-out).
  *
  * The policy of trajectory b is what ilqg_batch_head(c, n_hor, x, u, l, L, NULL) returns for it: the current trajectory,
@@ -574,6 +610,10 @@ int ilqg_multi_set_x0(ilqg_multi_t *m, const double *x0);
 int ilqg_multi_set_u(ilqg_multi_t *m, const double *u);
 int ilqg_multi_init(ilqg_multi_t *m);
 int ilqg_multi_shift(ilqg_multi_t *m, int steps, const double *x0_new, const double *u_tail);  /* ilqg_batch_shift per shard */
+/* ilqg_batch_best_of / ilqg_batch_shift_winners per shard; winner[] is absolute in the WHOLE batch.  Refused, with the reason
+ * in the text, when a shard's first trajectory is not a multiple of K (the shard boundary would cut a segment). */
+int ilqg_multi_best_of(ilqg_multi_t *m, int K, const double *score, int *winner, double *best, int *n_eligible);
+int ilqg_multi_shift_winners(ilqg_multi_t *m, int K, const int *winner, int steps, const double *x0_new, const double *u_tail, const double *du);
 int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l, double *L, double *cost);  /* ilqg_batch_head per shard */
 int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                               double *x_end, double *x, double *u);  /* ilqg_batch_policy_rollout per shard (host memory) */
