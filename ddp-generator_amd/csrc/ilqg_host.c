@@ -577,7 +577,7 @@ static int shift_groups(ilqg_batch_t *c, int round, int on_device, int steps, co
         const double *const tail_g = (u_tail && steps > 0) ? u_tail + (size_t)c->first[g] * steps * N_U : NULL;
         if(x0_g && (on_device ? ilqg_dev_put_x0_device(c->dev[g], x0_g) : ilqg_dev_write_steps(c->dev[g], ILQG_F_X, x0_g, 1)))
             return fail(c, "shift: x0_new");
-        if(tail_g && (on_device ? ilqg_dev_put_u_tail_device : ilqg_dev_write_u_tail)(c->dev[g], tail_g, steps)) return fail(c, "shift: u_tail");
+        if(tail_g && ilqg_dev_put_u_tail(c->dev[g], tail_g, steps, on_device)) return fail(c, "shift: u_tail");
         /* behind the last kernel that reads the caller's memory, not behind the roll-out */
         if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "shift: stream");
     }
@@ -782,28 +782,26 @@ static int head_steps(ilqg_batch_t *c, const char *who, int steps) {
 }
 #define HEAD_AT(p, w) ((p) ? (p) + (size_t)c->first[g] * steps * (w) : NULL)
 
-int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost) {
+static int head(ilqg_batch_t *c, const char *who, int on_device, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream) {
+    const named_ptr_t ptrs[] = {{x, "x"}, {u, "u"}, {l, "l"}, {L, "L"}, {cost, "cost"}};
     int g;
-    if(head_steps(c, "ilqg_batch_head", steps)) return 1;
-    EACH_GROUP(g)
+    if(head_steps(c, who, steps)) return 1;
+    if(on_device && (device_ptrs(c, who, ptrs, 5) || stream_in(c, stream, "head: stream"))) return 1;
+    EACH_GROUP(g) {
         if(ilqg_dev_head(c->dev[g], steps, HEAD_AT(x, N_X), HEAD_AT(u, N_U), HEAD_AT(l, N_U), HEAD_AT(L, N_U * N_X),
-                         cost ? cost + c->first[g] : NULL))
+                         cost ? cost + c->first[g] : NULL, on_device))
             return fail(c, "head");
+        if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "head: stream");
+    }
     return 0;
 }
 
+int ilqg_batch_head(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost) {
+    return head(c, "ilqg_batch_head", 0, steps, x, u, l, L, cost, NULL);
+}
+
 int ilqg_batch_head_device(ilqg_batch_t *c, int steps, double *x, double *u, double *l, double *L, double *cost, void *stream) {
-    const named_ptr_t ptrs[] = {{x, "x"}, {u, "u"}, {l, "l"}, {L, "L"}, {cost, "cost"}};
-    int g;
-    if(head_steps(c, "ilqg_batch_head_device", steps)) return 1;
-    if(device_ptrs(c, "ilqg_batch_head_device", ptrs, 5) || stream_in(c, stream, "head: stream")) return 1;
-    EACH_GROUP(g) {
-        if(ilqg_dev_head_device(c->dev[g], steps, HEAD_AT(x, N_X), HEAD_AT(u, N_U), HEAD_AT(l, N_U), HEAD_AT(L, N_U * N_X),
-                                cost ? cost + c->first[g] : NULL))
-            return fail(c, "head");
-        if(ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "head: stream");
-    }
-    return 0;
+    return head(c, "ilqg_batch_head_device", 1, steps, x, u, l, L, cost, stream);
 }
 
 /* Every plan's feedback policy rolled out from n_starts starts per trajectory (k_policy.inc): what a late measurement, a
@@ -891,9 +889,9 @@ static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_d
     if(push_config(c)) return 1;
     if(on_device && stream_in(c, stream, what_stream)) return 1;
     EACH_GROUP(g) {
-        if((on_device ? ilqg_dev_policy_rollout : ilqg_dev_policy_rollout_host)(
-               c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared,
-               dist_shared ? dist : POLICY_AT(dist, (size_t)c->N * N_X), dist_shared, alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U)))
+        if(ilqg_dev_policy_rollout(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared,
+                                   dist_shared ? dist : POLICY_AT(dist, (size_t)c->N * N_X), dist_shared, alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1),
+                                   POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U), on_device))
             return fail(c, what);
         if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, what_stream);
     }

@@ -117,7 +117,7 @@ enum {
     ILQG_K_ADOPT,    /*             k_adopt_home / k_rejected_home, k_commit */
     ILQG_K_SHIFT,    /* receding horizon: k_shift_lane / k_shift_wave (ilqg_dev_shift) */
     ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_loop_apply) */
-    ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head, ilqg_dev_head_device) */
+    ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head) */
     ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
     ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout with a table) */
@@ -223,8 +223,10 @@ int ilqg_dev_rollout_init(ilqg_dev_t *d);     /* forward_pass(alpha = 0) + swap 
  * the current trajectory lives, written to the arrays X / U (records in the wave mapping); the location indices are
  * cleared, so the ilqg_dev_rollout_init that follows copies nothing.  0 <= steps < n_hor. */
 int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0);
-/* the caller's tail behind a shift: host [batch][steps][N_U] into the last `steps` time steps of the controls */
-int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps);
+/* the caller's tail behind a shift: tail [batch][steps][N_U] into the last `steps` time steps of the controls.  on_device = 0:
+ * the array is host memory (staged, one wait); else device memory of the context's device, used on the context's stream without
+ * a wait. */
+int ilqg_dev_put_u_tail(ilqg_dev_t *d, const double *tail, int steps, int on_device);
 /* Candidates per agent: the context's trajectories as batch / K segments of K consecutive slots, K one of 1, 2, 4, .. 64
  * and a divisor of batch and of `first`, the batch-absolute index of the context's first trajectory (refused otherwise: the
  * kernels rely on a segment never leaving a tile of 64).  on_device = 0: the arrays are host memory (staged, one wait);
@@ -242,10 +244,9 @@ int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, i
                            int on_device);
 /* The control interval of a caller with its own plant.  head: the first `steps` steps of every CURRENT plan, read where it
  * lives (nothing moves home), trajectory-major: x [batch][steps][N_X], u / l [batch][steps][N_U], L [batch][steps][N_U*N_X],
- * cost [batch]; any pointer may be NULL; 1 <= steps <= n_hor.  ilqg_dev_head fills host arrays (one wait at most),
- * ilqg_dev_head_device writes device memory of the caller on the context's stream and waits for nothing. */
-int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost);
-int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost);
+ * cost [batch]; any pointer may be NULL; 1 <= steps <= n_hor.  on_device = 0: the arrays are host memory (staged, one wait
+ * at most); else device memory of the context's device, used on the context's stream without a wait. */
+int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost, int on_device);
 /* Every plan's feedback policy rolled out from R starts per trajectory (k_policy.inc): forward_pass with the caller's start
  * as x0, the nominal = what ilqg_dev_head hands out (current x / u where they live, l / L of the records), the multipliers
  * and penalty weights the trajectory has, and u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if feedback].
@@ -258,19 +259,17 @@ int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double 
  * twice — the caller has checked names; sizes and range are checked here) replaced by row (b, r) of values:
  * [batch][R][W], or with shared != 0 [R][W] for every trajectory, W = the sum of the named sizes, the named parameters one
  * behind the other in the order of named[].  The policy, multipliers, penalty weights and per-time-step parameters are the
- * context's.  ilqg_dev_policy_rollout takes DEVICE memory (values lives where x0 lives), is asynchronous on the context's
- * stream and waits for nothing; ilqg_dev_policy_rollout_host takes host memory, stages through the context's staging buffer
- * (which only grows) and waits once.  R >= 1; needs ilqg_dev_set_params before it.
+ * context's.  on_device = 0: the arrays are host memory (staged through the context's staging buffer, which only grows, one
+ * wait); else device memory of the context's device (values lives where x0 lives), used on the context's stream without a
+ * wait.  R >= 1; needs ilqg_dev_set_params before it.
  * dist = NULL: no process noise — the same kernels, launches and bits as before the argument existed.  Else behind every step
  * k = 0 .. n_hor-1 the roll-out's state is pushed, x_{k+1} <- x_next + w[b][r][k] (the rule of ilqg_dev_loop_apply):
  * dist [batch][R][n_hor][N_X], or with dist_shared != 0 [R][n_hor][N_X] for every trajectory; it lives where x0 lives (the
  * host form stages it behind the values).  ok = 0 also where a disturbed state is not finite, the one behind row n_hor-1 —
  * which moves x_end, x[n_hor] and the final cost — included.  No new kernel and no new timing slot. */
 int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                            const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                                 const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
-                                 double *u);
+                            const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u,
+                            int on_device);
 /* The receding-horizon loop that stays on the device: `rounds` times { ilqg_dev_iterate; ilqg_dev_loop_apply; ilqg_dev_loop_shift;
  * ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_loop_begin and one ilqg_dev_loop_read — the caller's loop;
  * nothing in it waits or copies.  What the loop is, is stated once, here: */
@@ -316,9 +315,8 @@ int ilqg_dev_loop_begin(ilqg_dev_t *d, const ilqg_dev_loop_t *loop);
 int ilqg_dev_loop_apply(ilqg_dev_t *d, int round, int feedback);
 int ilqg_dev_loop_shift(ilqg_dev_t *d, int round);
 int ilqg_dev_loop_read(ilqg_dev_t *d, double *x_plant, double *x, double *u, double *cost_applied, double *plan_cost, int *ok);
-/* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) / ilqg_dev_write_u_tail with the source in DEVICE memory: no staging, no wait */
+/* ilqg_dev_write_steps(d, ILQG_F_X, x0, 1) with the source in DEVICE memory: no staging, no wait */
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0);
-int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps);
 /* Ordering with a stream of the caller (a hipStream_t, NULL = the null stream), by events made once per context: after
  * stream_in the context's stream runs behind everything enqueued on `stream` so far; after stream_out `stream` runs behind
  * everything enqueued on the context's stream so far.  Neither waits on the host. */

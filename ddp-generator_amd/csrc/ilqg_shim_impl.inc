@@ -349,6 +349,57 @@ int io_done(ilqg_dev *d) {  // end of a single write
     return 0;
 }
 
+// The transfers of one entry.  The entry declares its inputs, then its outputs — in(p, bytes) / out(p, bytes), p its own
+// pointer variable —, opens the plan, launches on what p points to now, and closes the plan.
+// Host form: open() makes ONE stage() reservation for all of them (a second one could, while transfers are deferred, flush and
+// regrow the buffers under addresses already handed out), cut into slices 256 bytes apart in the order declared, sends every
+// input there and points each p at its slice; NULL or 0 bytes takes no room and leaves p NULL.  close() queues one copy per
+// output; deferred, they are delivered by ilqg_dev_io_end; else this is the entry's one wait (without outputs: as io_done).
+// on_device: p is device memory of the caller and stays as it is; nothing is staged, copied or waited for.
+struct Staged {
+    struct Slice { void *var; void *host; size_t bytes, off; bool out; };
+    ilqg_dev *d;
+    Slice s[8];  // (ilqg_dev_policy_rollout declares eight)
+    int n = 0;
+    bool on_device;
+    size_t total = 0;
+    char *dev = nullptr, *pin = nullptr;
+    Staged(ilqg_dev *d, int on_device = 0) : d(d), on_device(on_device != 0) {}
+    template <class T> void add(T *&p, size_t bytes, bool out) {
+        if(on_device) return;
+        if(!p || !bytes) {
+            p = nullptr;
+            return;
+        }
+        s[n++] = {&p, const_cast<void *>((const void *)p), bytes, total, out};
+        total += (bytes + 255) & ~(size_t)255;
+    }
+    template <class T> void in(const T *&p, size_t bytes) { add(p, bytes, false); }
+    template <class T> void out(T *&p, size_t bytes) { add(p, bytes, true); }
+    int open() {
+        void *dv, *pv;
+        if(!n) return 0;
+        if(stage(d, total, &dv, &pv)) return 1;
+        dev = (char *)dv, pin = (char *)pv;
+        for(int i = 0; i < n; i++) {
+            void *at = dev + s[i].off;
+            memcpy(s[i].var, &at, sizeof(at));  // (the entry's pointer, whatever it points to)
+            if(!s[i].out && stage_in(d, at, pin ? pin + s[i].off : nullptr, s[i].host, s[i].bytes)) return 1;
+        }
+        return 0;
+    }
+    int close() {
+        if(!n) return 0;
+        for(int i = 0; i < n; i++) {
+            if(!s[i].out) continue;
+            void *to = pin ? (void *)(pin + s[i].off) : s[i].host;
+            HIP_TRY(hipMemcpyAsync(to, dev + s[i].off, s[i].bytes, hipMemcpyDeviceToHost, d->stream));
+            if(pin) d->pending.push_back({s[i].host, to, s[i].bytes, 0});
+        }
+        return io_done(d);
+    }
+};
+
 struct Timed {
     ilqg_dev *d;
     int kernel;
@@ -973,17 +1024,18 @@ static bool is_traj_major(int field) { return WAVE_MAP && field == ILQG_F_FIN; }
 static int nom_io(ilqg_dev *d, int field, double *host_rw, const double *host_ro, int steps) {
     const FieldInfo fi = field_info(field);
     const size_t n = (size_t)d->B * steps * fi.wh;
-    void *dev, *pin;
-    if(stage(d, n * sizeof(double), &dev, &pin)) return 1;
-    if(host_ro && stage_in(d, dev, pin, host_ro, n * sizeof(double))) return 1;
+    Staged io(d);
+    io.in(host_ro, n * sizeof(double));
+    io.out(host_rw, n * sizeof(double));
+    if(io.open()) return 1;
+    double *const slice = host_ro ? const_cast<double *>(host_ro) : host_rw;  // (one of the two is given)
     {
         Timed t(d, ILQG_K_TRANSPOSE);
-        hipLaunchKernelGGL(k_nom_io, grid1(n, 256), dim3(256), 0, d->stream, d->P.nom, (double *)dev, d->B, d->N, steps,
+        hipLaunchKernelGGL(k_nom_io, grid1(n, 256), dim3(256), 0, d->stream, d->P.nom, slice, d->B, d->N, steps,
                            fi.wh, nom_column(field), host_ro ? 1 : 0);
     }
     HIP_TRY(hipGetLastError());
-    if(host_rw) return stage_out(d, dev, pin, host_rw, n * sizeof(double));
-    return io_done(d);
+    return io.close();
 }
 
 #if ILQG_WAVE_MAP
@@ -1281,23 +1333,23 @@ int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0) {
     return 0;
 }
 
-int ilqg_dev_write_u_tail(ilqg_dev_t *d, const double *host, int steps) {
+int ilqg_dev_put_u_tail(ilqg_dev_t *d, const double *tail, int steps, int on_device) {
     HIP_TRY(hipSetDevice(d->device));
     if(steps < 1 || steps > d->N) {
-        g_err = "ilqg_dev_write_u_tail: bad step count";
+        g_err = "ilqg_dev_put_u_tail: bad step count";
         return 1;
     }
     if(all_home(d)) return 1;
     const size_t n = (size_t)d->B * steps * NU;
-    void *dev, *pin;
-    if(stage(d, n * sizeof(double), &dev, &pin)) return 1;
-    if(stage_in(d, dev, pin, host, n * sizeof(double))) return 1;
+    Staged io(d, on_device);
+    io.in(tail, n * sizeof(double));
+    if(io.open()) return 1;
     {
         Timed t(d, ILQG_K_TRANSPOSE);
-        hipLaunchKernelGGL(k_put_u_steps, grid1(n, 256), dim3(256), 0, d->stream, d->P, (const double *)dev, d->N - steps, steps);
+        hipLaunchKernelGGL(k_put_u_steps, grid1(n, 256), dim3(256), 0, d->stream, d->P, tail, d->N - steps, steps);
     }
     HIP_TRY(hipGetLastError());
-    return io_done(d);
+    return io.close();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1314,12 +1366,6 @@ static int segments_ok(ilqg_dev_t *d, int K, int first) {
         return 0;
     }
     return 1;
-}
-// a piece of `bytes` of a staged transfer that is cut into slices 256 bytes apart: its offset, and the total moves on
-static size_t slice(size_t &total, size_t bytes) {
-    const size_t at = total;
-    total += (bytes + 255) & ~(size_t)255;
-    return at;
 }
 
 // The one launch of k_best_of, on device memory.  Reads costs / the caller's scores and the status; writes nothing of the context.
@@ -1339,28 +1385,14 @@ int ilqg_dev_best_of(ilqg_dev_t *d, int K, int first, const double *score, int *
         g_err = "best_of: winner is NULL";
         return 1;
     }
-    if(on_device) return launch_best_of(d, K, first, score, winner, best, n_eligible);
     const size_t G = (size_t)(d->B / K);
-    size_t total = 0;
-    const size_t o_score = slice(total, score ? d->B * sizeof(double) : 0), o_win = slice(total, G * sizeof(int));
-    const size_t o_best = slice(total, best ? G * sizeof(double) : 0), o_n = slice(total, n_eligible ? G * sizeof(int) : 0);
-    void *dev, *pin;
-    if(stage(d, total, &dev, &pin)) return 1;
-    char *const dv = (char *)dev, *const pv = (char *)pin;
-    if(score && stage_in(d, dv + o_score, pin ? pv + o_score : nullptr, score, d->B * sizeof(double))) return 1;
-    if(launch_best_of(d, K, first, score ? (const double *)(dv + o_score) : nullptr, (int *)(dv + o_win), best ? (double *)(dv + o_best) : nullptr,
-                      n_eligible ? (int *)(dv + o_n) : nullptr))
-        return 1;
-    void *const host[3] = {winner, best, n_eligible};
-    const size_t off[3] = {o_win, o_best, o_n}, bytes[3] = {G * sizeof(int), G * sizeof(double), G * sizeof(int)};
-    for(int i = 0; i < 3; i++) {
-        if(!host[i]) continue;
-        void *to = pin ? (void *)(pv + off[i]) : host[i];
-        HIP_TRY(hipMemcpyAsync(to, dv + off[i], bytes[i], hipMemcpyDeviceToHost, d->stream));
-        if(pin) d->pending.push_back({host[i], to, bytes[i], 0});
-    }
-    if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
-    return 0;
+    Staged io(d, on_device);
+    io.in(score, d->B * sizeof(double));
+    io.out(winner, G * sizeof(int));
+    io.out(best, G * sizeof(double));
+    io.out(n_eligible, G * sizeof(int));
+    if(io.open() || launch_best_of(d, K, first, score, winner, best, n_eligible)) return 1;
+    return io.close();
 }
 
 // ilqg_dev_shift with the winner's plan as every slot's source: one pass that brings U home, as there, so the location
@@ -1378,24 +1410,13 @@ int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, i
         return 1;
     }
     if(steps == 0) u_tail = nullptr;  // (no tail step to fill)
-    if(!on_device) {
-        const size_t G = (size_t)(d->B / K);
-        size_t total = 0;
-        const size_t b_win = G * sizeof(int), b_x0 = x0_new ? G * NX * sizeof(double) : 0, b_tail = u_tail ? G * steps * NU * sizeof(double) : 0;
-        const size_t b_du = du ? (size_t)d->B * d->N * NU * sizeof(double) : 0;
-        const size_t o_win = slice(total, b_win), o_x0 = slice(total, b_x0), o_tail = slice(total, b_tail), o_du = slice(total, b_du);
-        void *dev, *pin;
-        if(stage(d, total, &dev, &pin)) return 1;
-        char *const dv = (char *)dev, *const pv = (char *)pin;
-        if(stage_in(d, dv + o_win, pin ? pv + o_win : nullptr, winner, b_win)) return 1;
-        if(x0_new && stage_in(d, dv + o_x0, pin ? pv + o_x0 : nullptr, x0_new, b_x0)) return 1;
-        if(u_tail && stage_in(d, dv + o_tail, pin ? pv + o_tail : nullptr, u_tail, b_tail)) return 1;
-        if(du && stage_in(d, dv + o_du, pin ? pv + o_du : nullptr, du, b_du)) return 1;
-        winner = (const int *)(dv + o_win);
-        if(x0_new) x0_new = (const double *)(dv + o_x0);
-        if(u_tail) u_tail = (const double *)(dv + o_tail);
-        if(du) du = (const double *)(dv + o_du);
-    }
+    const size_t G = (size_t)(d->B / K);
+    Staged io(d, on_device);
+    io.in(winner, G * sizeof(int));
+    io.in(x0_new, G * NX * sizeof(double));
+    io.in(u_tail, G * steps * NU * sizeof(double));
+    io.in(du, (size_t)d->B * d->N * NU * sizeof(double));
+    if(io.open()) return 1;
     {
         Timed t(d, ILQG_K_SHIFT_WINNERS);
 #if ILQG_WAVE_MAP
@@ -1410,7 +1431,7 @@ int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, i
     if(d->loc_set >= 0) HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
     d->loc_set = -1;
 #endif
-    return on_device ? 0 : io_done(d);
+    return io.close();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1432,38 +1453,19 @@ static int head_steps_ok(ilqg_dev_t *d, int steps) {
     return 0;
 }
 
-int ilqg_dev_head_device(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost) {
+int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost, int on_device) {
     HIP_TRY(hipSetDevice(d->device));
     if(!head_steps_ok(d, steps)) return 1;
     if(!x && !u && !l && !L && !cost) return 0;
-    return launch_head(d, steps, x, u, l, L, cost);
-}
-
-int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, double *L, double *cost) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(!head_steps_ok(d, steps)) return 1;
-    double *const host[5] = {x, u, l, L, cost};
-    const size_t per[5] = {(size_t)steps * NX, (size_t)steps * NU, (size_t)steps * NU, (size_t)steps * NXU, 1};
-    size_t off[5], total = 0;
-    for(int i = 0; i < 5; i++) {
-        off[i] = total;
-        if(host[i]) total += ((size_t)d->B * per[i] + 31) & ~(size_t)31;  // slices 256 bytes apart
-    }
-    if(total == 0) return 0;
-    void *dev, *pin;
-    if(stage(d, total * sizeof(double), &dev, &pin)) return 1;
-    double *dv[5];
-    for(int i = 0; i < 5; i++) dv[i] = host[i] ? (double *)dev + off[i] : nullptr;
-    if(launch_head(d, steps, dv[0], dv[1], dv[2], dv[3], dv[4])) return 1;
-    for(int i = 0; i < 5; i++) {
-        if(!host[i]) continue;
-        const size_t bytes = (size_t)d->B * per[i] * sizeof(double);
-        void *to = pin ? (void *)((double *)pin + off[i]) : (void *)host[i];
-        HIP_TRY(hipMemcpyAsync(to, dv[i], bytes, hipMemcpyDeviceToHost, d->stream));
-        if(pin) d->pending.push_back({host[i], to, bytes, 0});
-    }
-    if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
-    return 0;
+    const size_t n = (size_t)d->B * steps * sizeof(double);
+    Staged io(d, on_device);
+    io.out(x, n * NX);
+    io.out(u, n * NU);
+    io.out(l, n * NU);
+    io.out(L, n * NXU);
+    io.out(cost, d->B * sizeof(double));
+    if(io.open() || launch_head(d, steps, x, u, l, L, cost)) return 1;
+    return io.close();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1533,70 +1535,30 @@ static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyPar
     return roll_leave(d);
 }
 
-// the host form: the starts, then with a map the table of values, then the disturbance table if there is one, then the
-// outputs, in one piece of the staging buffer
-static int policy_rollout_staged(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared,
-                                 const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
-                                 double *u) {
-    const size_t n = (size_t)d->B * (size_t)R;
-    void *const host[5] = {cost, ok, x_end, x, u};
-    const size_t bytes[5] = {n * sizeof(double), n * sizeof(int), n * NX * sizeof(double), n * (size_t)(d->N + 1) * NX * sizeof(double),
-                             n * (size_t)d->N * NU * sizeof(double)};
-    const size_t in_bytes = n * NX * sizeof(double);
-    const size_t val_bytes = map ? (shared ? (size_t)R : n) * (size_t)map->W * sizeof(double) : 0;
-    const size_t val_off = (in_bytes + 255) & ~(size_t)255;  // slices 256 bytes apart, the starts first
-    const size_t dist_bytes = dist ? (dist_shared ? (size_t)R : n) * (size_t)d->N * NX * sizeof(double) : 0;
-    const size_t dist_off = val_off + ((val_bytes + 255) & ~(size_t)255);
-    size_t off[5], total = dist_off + ((dist_bytes + 255) & ~(size_t)255);
-    for(int i = 0; i < 5; i++) {
-        off[i] = total;
-        if(host[i]) total += (bytes[i] + 255) & ~(size_t)255;
-    }
-    void *dev, *pin;
-    if(stage(d, total, &dev, &pin)) return 1;
-    if(stage_in(d, dev, pin, x0, in_bytes)) return 1;
-    if(map && stage_in(d, (char *)dev + val_off, pin ? (char *)pin + val_off : nullptr, values, val_bytes)) return 1;
-    if(dist && stage_in(d, (char *)dev + dist_off, pin ? (char *)pin + dist_off : nullptr, dist, dist_bytes)) return 1;
-    void *dv[5];
-    for(int i = 0; i < 5; i++) dv[i] = host[i] ? (void *)((char *)dev + off[i]) : nullptr;
-    if(launch_policy(d, R, (const double *)dev, map, (const double *)((char *)dev + val_off), shared,
-                     dist ? (const double *)((char *)dev + dist_off) : nullptr, dist_shared, alpha, feedback, (double *)dv[0], (int *)dv[1],
-                     (double *)dv[2], (double *)dv[3], (double *)dv[4]))
-        return 1;
-    for(int i = 0; i < 5; i++) {
-        if(!host[i]) continue;
-        void *to = pin ? (void *)((char *)pin + off[i]) : host[i];
-        HIP_TRY(hipMemcpyAsync(to, dv[i], bytes[i], hipMemcpyDeviceToHost, d->stream));
-        if(pin) d->pending.push_back({host[i], to, bytes[i], 0});
-    }
-    if(!pin) HIP_TRY(hipStreamSynchronize(d->stream));  // the one wait; deferred transfers wait in ilqg_dev_io_end
-    return 0;
-}
-
-// both entries: n_named == 0 = no table (k_policy<false>), else roll-out (b, r) under its row of `values`; dist == nullptr =
-// no disturbance, else roll-out (b, r) under its rows of `dist` (dist_shared: row r for every trajectory)
-static int policy_rollout(ilqg_dev_t *d, bool on_host, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                          const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
-                          double *u) {
+// n_named == 0 = no table (k_policy<false>), else roll-out (b, r) under its row of `values`; dist == nullptr = no disturbance,
+// else roll-out (b, r) under its rows of `dist` (dist_shared: row r for every trajectory).  The host form stages the starts,
+// then with a map the table of values, then the disturbance table if there is one, then the outputs.
+int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                            const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u,
+                            int on_device) {
     HIP_TRY(hipSetDevice(d->device));
     NEED_PARAMS(d);
     PolicyParamMap table;
     const PolicyParamMap *map = nullptr;
     if(!policy_args_ok(d, R, x0) || (n_named != 0 && !(map = policy_param_map(n_named, named, values, table)))) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
-    return on_host ? policy_rollout_staged(d, R, x0, map, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u)
-                   : launch_policy(d, R, x0, map, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u);
-}
-
-int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                            const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return policy_rollout(d, false, R, x0, n_named, named, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u);
-}
-
-int ilqg_dev_policy_rollout_host(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
-                                 const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x,
-                                 double *u) {
-    return policy_rollout(d, true, R, x0, n_named, named, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u);
+    const size_t n = (size_t)d->B * (size_t)R;
+    Staged io(d, on_device);
+    io.in(x0, n * NX * sizeof(double));
+    io.in(values, map ? (shared ? (size_t)R : n) * (size_t)map->W * sizeof(double) : 0);
+    io.in(dist, (dist_shared ? (size_t)R : n) * (size_t)d->N * NX * sizeof(double));
+    io.out(cost, n * sizeof(double));
+    io.out(ok, n * sizeof(int));
+    io.out(x_end, n * NX * sizeof(double));
+    io.out(x, n * (size_t)(d->N + 1) * NX * sizeof(double));
+    io.out(u, n * (size_t)d->N * NU * sizeof(double));
+    if(io.open() || launch_policy(d, R, x0, map, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u)) return 1;
+    return io.close();
 }
 
 int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {
@@ -1607,21 +1569,6 @@ int ilqg_dev_put_x0_device(ilqg_dev_t *d, const double *x0) {
         Timed t(d, ILQG_K_TRANSPOSE);
         hipLaunchKernelGGL(k_nom_io, grid1(n, 256), dim3(256), 0, d->stream, d->P.nom, const_cast<double *>(x0), d->B, d->N, 1, NX, NOM_X, 1);
         if(!WAVE_MAP) hipLaunchKernelGGL(k_to_dev, grid1(n, 256), dim3(256), 0, d->stream, x0, d->P.f[ILQG_F_X], d->B, d->Bp, 1, NX, NX);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ilqg_dev_put_u_tail_device(ilqg_dev_t *d, const double *tail, int steps) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(steps < 1 || steps > d->N) {
-        g_err = "ilqg_dev_put_u_tail_device: bad step count";
-        return 1;
-    }
-    if(all_home(d)) return 1;
-    {
-        Timed t(d, ILQG_K_TRANSPOSE);
-        hipLaunchKernelGGL(k_put_u_steps, grid1((size_t)d->B * steps * NU, 256), dim3(256), 0, d->stream, d->P, tail, d->N - steps, steps);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1666,20 +1613,16 @@ int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail
         return 1;
     }
     if(steps == 0) return 0;
-    const double *tail_dev = nullptr;
-    if(tail) {
-        void *dev, *pin;
-        if(stage(d, (size_t)steps * sizeof(double), &dev, &pin)) return 1;
-        if(stage_in(d, dev, pin, tail, (size_t)steps * sizeof(double))) return 1;
-        tail_dev = (const double *)dev;
-    }
+    Staged io(d);
+    io.in(tail, (size_t)steps * sizeof(double));
+    if(io.open()) return 1;
     {
         Timed t(d, ILQG_K_SHIFT_PARAM);
-        hipLaunchKernelGGL(k_shift_param, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index].get(), d->N + 1, steps, tail_dev);
+        hipLaunchKernelGGL(k_shift_param, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index].get(), d->N + 1, steps, tail);
     }
     HIP_TRY(hipGetLastError());
     d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters
-    return tail ? io_done(d) : 0;
+    return io.close();
 }
 
 // the same per row of a per-trajectory window: k_shift_param_rows, one workgroup per trajectory
@@ -1695,20 +1638,15 @@ int ilqg_dev_shift_param_batch(ilqg_dev_t *d, int index, int steps, const double
         return 1;
     }
     if(steps == 0) return 0;
-    const double *tail_dev = tail;
-    if(tail && !on_device) {
-        void *dev, *pin;
-        const size_t bytes = (size_t)d->B * (size_t)steps * sizeof(double);
-        if(stage(d, bytes, &dev, &pin)) return 1;
-        if(stage_in(d, dev, pin, tail, bytes)) return 1;
-        tail_dev = (const double *)dev;
-    }
+    Staged io(d, on_device);
+    io.in(tail, (size_t)d->B * (size_t)steps * sizeof(double));
+    if(io.open()) return 1;
     {
         Timed t(d, ILQG_K_SHIFT_PARAM_ROWS);
-        hipLaunchKernelGGL(k_shift_param_rows, dim3(d->B), dim3(PARAM_BLOCK), 0, d->stream, d->sr_rows[s].get(), d->N + 1, steps, tail_dev);
+        hipLaunchKernelGGL(k_shift_param_rows, dim3(d->B), dim3(PARAM_BLOCK), 0, d->stream, d->sr_rows[s].get(), d->N + 1, steps, tail);
     }
     HIP_TRY(hipGetLastError());
-    return (tail && !on_device) ? io_done(d) : 0;
+    return io.close();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
