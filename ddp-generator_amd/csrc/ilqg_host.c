@@ -1270,7 +1270,7 @@ int ilqg_batch_receding_plant_windows(ilqg_batch_t *c, int rounds, int steps, in
     return receding(c, &a);
 }
 
-/* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param), and in the host
+/* the window of a per-time-step parameter moves with the horizon: on the device in place (k_shift_param_rows), and in the host
  * mirror c->p[i], from which a later ilqg_batch_set_param of another parameter re-pushes the whole table */
 int ilqg_batch_shift_param(ilqg_batch_t *c, const char *name, int steps, const double *tail) {
     const int i = find_param(name);

@@ -882,42 +882,31 @@ __device__ __forceinline__ size_t cur_ustride(const DevPtrs &P) { return WAVE_MA
 __device__ __forceinline__ size_t mul_ix(const DevPtrs &P, int W, int k, int b) {
     return (size_t)k * W * P.Bp + (size_t)(b >> 6) * (W * WAVE) + (b & 63);
 }
-__device__ __forceinline__ void load_mul(const DevPtrs &P, int k, int b, multipliersEl_t &m) {
-    if(ME > 0) {
-        double v[MEW];
-        const double *s = P.f[ILQG_F_MUL] + mul_ix(P, ME, k, b);
+// one strided copy each way: field F holds M doubles per (trajectory, step), which the struct Mul is made of
+template <int F, int M, class Mul>
+__device__ __forceinline__ void load_strided(const DevPtrs &P, int k, int b, Mul &m) {
+    if(M > 0) {
+        double v[M > 0 ? M : 1];
+        const double *s = P.f[F] + mul_ix(P, M, k, b);
 #pragma unroll
-        for(int i = 0; i < ME; i++) v[i] = s[i * WAVE];
-        __builtin_memcpy(&m, v, sizeof(double) * ME);
+        for(int i = 0; i < M; i++) v[i] = s[i * WAVE];
+        __builtin_memcpy(&m, v, sizeof(double) * M);
     }
 }
-__device__ __forceinline__ void store_mul(const DevPtrs &P, int k, int b, const multipliersEl_t &m) {
-    if(ME > 0) {
-        double v[MEW];
-        __builtin_memcpy(v, &m, sizeof(double) * ME);
-        double *s = P.f[ILQG_F_MUL] + mul_ix(P, ME, k, b);
+template <int F, int M, class Mul>
+__device__ __forceinline__ void store_strided(const DevPtrs &P, int k, int b, const Mul &m) {
+    if(M > 0) {
+        double v[M > 0 ? M : 1];
+        __builtin_memcpy(v, &m, sizeof(double) * M);
+        double *s = P.f[F] + mul_ix(P, M, k, b);
 #pragma unroll
-        for(int i = 0; i < ME; i++) s[i * WAVE] = v[i];
+        for(int i = 0; i < M; i++) s[i * WAVE] = v[i];
     }
 }
-__device__ __forceinline__ void load_mul_fin(const DevPtrs &P, int b, multipliersFin_t &m) {
-    if(MF > 0) {
-        double v[MFW];
-        const double *s = P.f[ILQG_F_MULF] + mul_ix(P, MF, 0, b);
-#pragma unroll
-        for(int i = 0; i < MF; i++) v[i] = s[i * WAVE];
-        __builtin_memcpy(&m, v, sizeof(double) * MF);
-    }
-}
-__device__ __forceinline__ void store_mul_fin(const DevPtrs &P, int b, const multipliersFin_t &m) {
-    if(MF > 0) {
-        double v[MFW];
-        __builtin_memcpy(v, &m, sizeof(double) * MF);
-        double *s = P.f[ILQG_F_MULF] + mul_ix(P, MF, 0, b);
-#pragma unroll
-        for(int i = 0; i < MF; i++) s[i * WAVE] = v[i];
-    }
-}
+__device__ __forceinline__ void load_mul(const DevPtrs &P, int k, int b, multipliersEl_t &m) { load_strided<ILQG_F_MUL, ME>(P, k, b, m); }
+__device__ __forceinline__ void store_mul(const DevPtrs &P, int k, int b, const multipliersEl_t &m) { store_strided<ILQG_F_MUL, ME>(P, k, b, m); }
+__device__ __forceinline__ void load_mul_fin(const DevPtrs &P, int b, multipliersFin_t &m) { load_strided<ILQG_F_MULF, MF>(P, 0, b, m); }
+__device__ __forceinline__ void store_mul_fin(const DevPtrs &P, int b, const multipliersFin_t &m) { store_strided<ILQG_F_MULF, MF>(P, 0, b, m); }
 
 // ---------------------------------------------------------------------------
 // host layout [b][k][f]  <->  device layout [k][b/64][f][b%64] of the lane mapping (the wave mapping's
@@ -980,11 +969,11 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 
 #include "k_common.inc"  // k_select, k_adopt, k_update, k_multipliers, unit-test kernels
 
-#include "k_shift.inc"  // k_shift_lane / k_shift_wave, k_put_u_steps, k_log_steps (receding horizon)
+#include "k_shift.inc"  // the in-place shift stated once; k_shift_lane / k_shift_wave, k_put_u_steps, k_log_steps (receding horizon)
 
 #include "k_best.inc"  // k_best_of, k_shift_winners_lane / k_shift_winners_wave (candidates per agent)
 
-#include "k_mpc_io.inc"  // k_head, k_shift_param (the control interval of a caller with its own plant)
+#include "k_mpc_io.inc"  // k_head, k_shift_param_rows, k_shift_windows (the control interval of a caller with its own plant)
 
 #include "k_policy.inc"  // k_policy (roll-outs of every plan's feedback policy from the caller's starts)
 

@@ -118,7 +118,7 @@ enum {
     ILQG_K_SHIFT,    /* receding horizon: k_shift_lane / k_shift_wave (ilqg_dev_shift) */
     ILQG_K_LOG,      /*                   k_log_steps (ilqg_dev_loop_apply) */
     ILQG_K_HEAD,     /*                   k_head (ilqg_dev_head) */
-    ILQG_K_SHIFT_PARAM, /*                k_shift_param (ilqg_dev_shift_param) */
+    ILQG_K_SHIFT_PARAM, /*                k_shift_param_rows on the one shared row (ilqg_dev_shift_param) */
     ILQG_K_POLICY,   /* k_policy (ilqg_dev_policy_rollout) */
     ILQG_K_POLICY_PARAMS, /* k_policy<true> (ilqg_dev_policy_rollout with a table) */
     ILQG_K_PLANT,    /* k_plant (ilqg_dev_loop_apply with plants) */

@@ -1308,29 +1308,38 @@ int ilqg_dev_rollout_init(ilqg_dev_t *d) {
     return roll_leave(d);
 }
 
+}  // extern "C"
+// (shift_plans is a template and cannot have C linkage: it stands between two extern blocks, as each_future / windows_move do)
 // Receding horizon: the plan moves `steps` time steps towards the start where it is (k_shift.inc).  One pass over U in the
-// lane mapping — the controls are read wherever the current trajectory lives and land in the array U, so the all_home()
-// of the initial roll-out that follows has nothing left to copy — and one over the records' u in the wave mapping.
-int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0) {
-    HIP_TRY(hipSetDevice(d->device));
-    if(steps < 0 || steps >= d->N) {
-        g_err = "ilqg_dev_shift: steps must be in 0 .. n_hor - 1";
-        return 1;
-    }
+// lane mapping — the controls are read wherever the source's trajectory lives and land in the array U, so the location
+// indices are cleared behind it and the all_home() of the initial roll-out that follows has nothing left to copy — and one
+// over the records' u in the wave mapping.  What ilqg_dev_shift and ilqg_dev_shift_winners share: `steps` in range (who:
+// the entry's name in front of the text; the winners entry asks before it plans its transfers), and ONE launch of this
+// mapping's kernel (wave_grid: its workgroups in the wave mapping) under `slot` with the clear behind it.
+static int shift_steps_ok(ilqg_dev_t *d, const char *who, int steps) {
+    if(steps >= 0 && steps < d->N) return 1;
+    g_err = std::string(who) + ": steps must be in 0 .. n_hor - 1";
+    return 0;
+}
+template <class Kernel, class... Args>
+static int shift_plans(ilqg_dev_t *d, int slot, Kernel kernel, int wave_grid, Args... args) {
     {
-        Timed t(d, ILQG_K_SHIFT);
-#if ILQG_WAVE_MAP
-        hipLaunchKernelGGL(k_shift_wave, dim3(d->B), dim3(SHIFT_BLOCK), 0, d->stream, d->P, steps, use_plan_x0);
-#else
-        hipLaunchKernelGGL(k_shift_lane, dim3((unsigned)((size_t)(NX > NU ? NX : NU) * d->Bp / WAVE)), dim3(WAVE * SHIFT_WAVES), 0, d->stream, d->P, steps, use_plan_x0);
-#endif
+        Timed t(d, slot);
+        const size_t grid = WAVE_MAP ? (size_t)wave_grid : (size_t)(NX > NU ? NX : NU) * d->Bp / WAVE;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(SHIFT_THREADS), 0, d->stream, d->P, args...);
     }
     HIP_TRY(hipGetLastError());
-#if !ILQG_WAVE_MAP
-    if(d->loc_set >= 0) HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
-    d->loc_set = -1;
-#endif
+    if constexpr(!WAVE_MAP) {
+        if(d->loc_set >= 0) HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
+        d->loc_set = -1;
+    }
     return 0;
+}
+extern "C" {
+int ilqg_dev_shift(ilqg_dev_t *d, int steps, int use_plan_x0) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(!shift_steps_ok(d, "ilqg_dev_shift", steps)) return 1;
+    return shift_plans(d, ILQG_K_SHIFT, k_shift, d->B, steps, use_plan_x0);
 }
 
 int ilqg_dev_put_u_tail(ilqg_dev_t *d, const double *tail, int steps, int on_device) {
@@ -1395,16 +1404,11 @@ int ilqg_dev_best_of(ilqg_dev_t *d, int K, int first, const double *score, int *
     return io.close();
 }
 
-// ilqg_dev_shift with the winner's plan as every slot's source: one pass that brings U home, as there, so the location
-// indices are cleared behind it and the all_home() of the initial roll-out that follows has nothing left to copy.
+// ilqg_dev_shift with the winner's plan as every slot's source: the same check, launch and clear (shift_plans)
 int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, int steps, const double *x0_new, const double *u_tail, const double *du,
                            int on_device) {
     HIP_TRY(hipSetDevice(d->device));
-    if(!segments_ok(d, K, first)) return 1;
-    if(steps < 0 || steps >= d->N) {
-        g_err = "ilqg_dev_shift_winners: steps must be in 0 .. n_hor - 1";
-        return 1;
-    }
+    if(!segments_ok(d, K, first) || !shift_steps_ok(d, "ilqg_dev_shift_winners", steps)) return 1;
     if(!winner) {
         g_err = "ilqg_dev_shift_winners: winner is NULL";
         return 1;
@@ -1416,21 +1420,7 @@ int ilqg_dev_shift_winners(ilqg_dev_t *d, int K, int first, const int *winner, i
     io.in(x0_new, G * NX * sizeof(double));
     io.in(u_tail, G * steps * NU * sizeof(double));
     io.in(du, (size_t)d->B * d->N * NU * sizeof(double));
-    if(io.open()) return 1;
-    {
-        Timed t(d, ILQG_K_SHIFT_WINNERS);
-#if ILQG_WAVE_MAP
-        hipLaunchKernelGGL(k_shift_winners_wave, dim3(d->B / K), dim3(SHIFT_BLOCK), 0, d->stream, d->P, K, first, winner, steps, x0_new, u_tail, du);
-#else
-        hipLaunchKernelGGL(k_shift_winners_lane, dim3((unsigned)((size_t)(NX > NU ? NX : NU) * d->Bp / WAVE)), dim3(WAVE * SHIFT_WAVES), 0, d->stream, d->P, K,
-                           first, winner, steps, x0_new, u_tail, du);
-#endif
-    }
-    HIP_TRY(hipGetLastError());
-#if !ILQG_WAVE_MAP
-    if(d->loc_set >= 0) HIP_TRY(hipMemsetAsync(d->P.i[ILQG_I_LOC], 0, d->Bp * sizeof(int), d->stream));
-    d->loc_set = -1;
-#endif
+    if(io.open() || shift_plans(d, ILQG_K_SHIFT_WINNERS, k_shift_winners, d->B / K, K, first, winner, steps, x0_new, u_tail, du)) return 1;
     return io.close();
 }
 
@@ -1618,7 +1608,7 @@ int ilqg_dev_shift_param(ilqg_dev_t *d, int index, int steps, const double *tail
     if(io.open()) return 1;
     {
         Timed t(d, ILQG_K_SHIFT_PARAM);
-        hipLaunchKernelGGL(k_shift_param, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index].get(), d->N + 1, steps, tail);
+        hipLaunchKernelGGL(k_shift_param_rows, dim3(1), dim3(PARAM_BLOCK), 0, d->stream, d->param_bufs[index].get(), d->N + 1, steps, tail);  // (one row)
     }
     HIP_TRY(hipGetLastError());
     d->work_consts = d->half_consts[0] = d->half_consts[1] = false;  // constant record entries depend on the parameters

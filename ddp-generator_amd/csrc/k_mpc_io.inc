@@ -54,39 +54,14 @@ __global__ void __launch_bounds__(WAVE * HEAD_WAVES) k_head(DevPtrs P, int steps
     }
 }
 
-// The window of ONE per-time-step parameter (n = n_hor + 1 doubles in global memory, param_bufs) moves `steps` values
-// on, in place: p'[k] = p[k + steps], the last `steps` values from tail [steps] or, with tail null, p[n - 1] held.  One
-// workgroup, ascending blocks of its size: all loads of a block, a barrier, its stores (the pattern of k_shift_wave: a
-// block reads [k0 + steps, k0 + block + steps) and writes [k0, k0 + block), the blocks before it wrote nothing beyond
-// k0; p[n - 1], which a null tail repeats, is written by the last block alone, behind that block's reads).
-constexpr int PARAM_BLOCK = 256;
-__global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param(double *__restrict__ p, int n, int steps, const double *__restrict__ tail) {
-    const int t = (int)threadIdx.x;
-    if(steps <= 0) return;
-    for(int k0 = 0; k0 < n; k0 += PARAM_BLOCK) {
-        const int k = k0 + t, from = k + steps;
-        double v = 0.0;
-        if(k < n) v = from < n ? p[from] : (tail ? tail[from - n] : p[n - 1]);
-        __syncthreads();
-        if(k < n) p[k] = v;
-    }
-}
-
-// The per-row form, for the per-trajectory windows (ilqg_dev_shift_param_batch): rows [B][n], tail [B][steps] or null.  The
-// row is picked by the workgroup index; within a row the same ascending blocks, the same barrier, the same argument — no
-// other workgroup touches the row.  Index arithmetic over B n in size_t.
+// The windows of a per-time-step parameter (n = n_hor + 1 doubles each, in global memory) move `steps` values on, in place:
+// p'[k] = p[k + steps], the last `steps` values from the row's tail or, with tail null, p[n - 1] held — shift_row
+// (k_shift.inc), one workgroup per row: rows [grid][n], tail [grid][steps] or null.  The per-trajectory windows
+// (ilqg_dev_shift_param_batch) are B rows, the one shared window (param_bufs, ilqg_dev_shift_param) is one.  Index
+// arithmetic over B n in size_t.
 __global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param_rows(double *__restrict__ rows, int n, int steps, const double *__restrict__ tail) {
-    const int t = (int)threadIdx.x;
     if(steps <= 0) return;
-    double *p = rows + (size_t)blockIdx.x * (size_t)n;
-    const double *tl = tail ? tail + (size_t)blockIdx.x * (size_t)steps : nullptr;
-    for(int k0 = 0; k0 < n; k0 += PARAM_BLOCK) {
-        const int k = k0 + t, from = k + steps;
-        double v = 0.0;
-        if(k < n) v = from < n ? p[from] : (tl ? tl[from - n] : p[n - 1]);
-        __syncthreads();
-        if(k < n) p[k] = v;
-    }
+    shift_row(rows + (size_t)blockIdx.x * (size_t)n, n, steps, tail ? tail + (size_t)blockIdx.x * (size_t)steps : nullptr);
 }
 
 // ALL windows of a context move with the horizon in ONE launch, fed from futures that already lie on the device
@@ -94,10 +69,10 @@ __global__ void __launch_bounds__(PARAM_BLOCK) k_shift_param_rows(double *__rest
 // the problem — its slot, grid.y — a descriptor by value: the window's base, its row count (B for a parameter with rows per
 // trajectory, 1 for the shared window), the base of its future or null (hold the last value, per row) and the future's row
 // stride (rounds * steps, or 0 for a shared future).  grid.x is the row; the workgroups beyond a slot's row count return at
-// once.  The tail of this round is columns [col, col + steps) of the row's future, col = round * steps.  Within a row the
-// ascending blocks of k_shift_param_rows, the same barrier, the same argument for moving in place; no other workgroup touches
-// the row.  Index arithmetic over B n and B rounds steps in size_t.  Plain loads and stores, no LDS.  A template on the number
-// of slots, so that it exists only in libraries whose problem has a per-time-step parameter.
+// once.  The tail of this round is columns [col, col + steps) of the row's future, col = round * steps.  Within a row
+// shift_row, one workgroup per row as in k_shift_param_rows.  Index arithmetic over B n and B rounds steps in size_t.  Plain
+// loads and stores, no LDS.  A template on the number of slots, so that it exists only in libraries whose problem has a
+// per-time-step parameter.
 struct WindowDesc {
     double *base;
     const double *future;
@@ -110,16 +85,7 @@ struct WindowSet {
 };
 template <int n_slots>
 __global__ void __launch_bounds__(PARAM_BLOCK) k_shift_windows(WindowSet<n_slots> S, int n, int steps, int col) {
-    const int t = (int)threadIdx.x;
     const WindowDesc w = S.w[blockIdx.y];
     if(steps <= 0 || (int)blockIdx.x >= w.rows) return;  // (uniform over the workgroup: nobody is left at the barrier)
-    double *p = w.base + (size_t)blockIdx.x * (size_t)n;
-    const double *tl = w.future ? w.future + (size_t)blockIdx.x * w.stride + (size_t)col : nullptr;
-    for(int k0 = 0; k0 < n; k0 += PARAM_BLOCK) {
-        const int k = k0 + t, from = k + steps;
-        double v = 0.0;
-        if(k < n) v = from < n ? p[from] : (tl ? tl[from - n] : p[n - 1]);
-        __syncthreads();
-        if(k < n) p[k] = v;
-    }
+    shift_row(w.base + (size_t)blockIdx.x * (size_t)n, n, steps, w.future ? w.future + (size_t)blockIdx.x * w.stride + (size_t)col : nullptr);
 }

@@ -44,22 +44,24 @@ def ilqg():
     return m
 
 
-def setup(name, batch):
-    """(problem, fd, strict, n_hor, params, opts, x0, u0) of a batch of `batch` starts"""
+def setup(name, batch, n_hor=None):
+    """(problem, fd, strict, n_hor, params, opts, x0, u0) of a batch of `batch` starts; n_hor: the problem's usual horizon"""
     if name in ("carparking", "carparking_wave"):
         from conftest import load_package
-        x0, u0 = load_package().synth.car_batch(batch, 500, first=40)
+        N = n_hor or 500
+        x0, u0 = load_package().synth.car_batch(batch, N, first=40)
         # the second half starts four times as far out with ten times the control noise: by the seventh iteration a few of these
         # accept a step size of the line search's SECOND stage (CPU oracle: 4 of 100), the others one of the first
         x0[batch // 2:] *= 4.0
         u0[batch // 2:] *= 10.0
-        return "carparking", 0, ("wave" if name == "carparking_wave" else False), 500, CAR_PARAMS, {}, x0, u0
+        return "carparking", 0, ("wave" if name == "carparking_wave" else False), N, CAR_PARAMS, {}, x0, u0
     if name == "hxtest":
         x0, u0 = hx_inputs(batch)
         return "hxtest", 1, False, HX_N, HX_PARAMS, {}, x0, u0
     if name == "synth16x8":
-        x0, u0 = syn_inputs(batch, 60)
-        return "synth16x8", 1, False, 60, SYN_PARAMS_TIGHT, {}, x0, u0
+        N = n_hor or 60
+        x0, u0 = syn_inputs(batch, N)
+        return "synth16x8", 1, False, N, SYN_PARAMS_TIGHT, {}, x0, u0
     if name == "synth10hx":
         x0, u0 = syn10_inputs(batch, 50)
         return "synth10hx", 0, False, 50, SYN10_PARAMS, {}, x0, u0
@@ -135,6 +137,50 @@ def test_shift_equals_the_host_composition(ilqg, name, groups):
     dev.shift(0)
     host.init(xh[:, 0], uh)
     assert_state_equal(state(dev), state(host), "steps = 0")
+    dev.close()
+    host.close()
+
+
+@pytest.mark.parametrize("name,N", [("carparking", 6), ("carparking", 64), ("carparking", 65), ("carparking", 130),
+                                    ("carparking_wave", 6), ("carparking_wave", 64), ("carparking_wave", 65), ("carparking_wave", 130),
+                                    ("synth16x8", 31), ("synth16x8", 32), ("synth16x8", 33)])
+def test_shift_at_the_kernels_boundaries(ilqg, name, N):
+    """The plain shift where its kernels' loops end (the shapes of test_gpu_best_of's boundary test, whose kernels share
+    these loops): n_hor = 6, 64, 65, 130 is one, exactly one, one plus one and three rounds of k_shift_lane's 64 steps, and
+    one to three blocks of k_shift_wave's 256 / N_U = 128 steps; synth16x8 (N_U = 8) at 31, 32, 33 lies around that form's
+    block of 32 steps.  B = 72: a tail tile of 8 lanes.  steps in {1, n_hor - 1}, x0 and tail given or neither; against the
+    composition through the host, bit for bit, right after the shift and two iterations on.
+    Where the plans lie: after the three iterations in front of the first shift every plan of these starts lies in a kept
+    roll-out plane in the lane mapping (printed; measured up to twelve iterations: 72 of 72 at n_hor = 6, 64 and 65, 71 of 72
+    at 130 from the eleventh on), which k_shift_lane only copies.  So each case shifts a SECOND time at once: the first shift
+    has brought every plan home to X / U, and the second moves all of them IN PLACE, which is what the rounds' order and
+    barrier are for."""
+    B = 72
+    problem, fd, strict, N, params, opts, x0, u0 = setup(name, B, N)
+    rng = np.random.default_rng(N)
+    kw = dict(batch=B, n_hor=N, params=params, opts=dict(opts, max_iter=40), strict=strict)
+    dev, host = ilqg.BatchSolver(problem, fd, **kw), ilqg.BatchSolver(problem, fd, **kw)
+    nx, nu = dev.problem.nx, dev.problem.nu
+    for s in (1, N - 1):
+        for form in ("both", "neither"):
+            for b in (dev, host):
+                b.init(x0, u0)
+                b.iterate(3)
+            acc, idx = dev.ints("accepted"), dev.ints("alpha_idx")
+            plane = (acc == 1) & (idx <= 4)  # (test_shift_equals_the_host_composition: where the current trajectory lives)
+            print("%s N=%d s=%d %s: %d of %d trajectories in a kept roll-out plane" % (name, N, s, form, int(plane.sum()), B))
+            for turn in ("from where the iterations left the plans", "again, in place"):
+                xh, uh = host.x(), host.u()
+                x0_new = xh[:, s] + 0.01 * rng.standard_normal((B, nx)) if form == "both" else None
+                u_tail = 0.4 * rng.standard_normal((B, s, nu)) if form == "both" else None
+                dev.shift(s, x0_new, u_tail)
+                tail = u_tail if u_tail is not None else np.repeat(uh[:, -1:], s, axis=1)
+                host.init(x0_new if x0_new is not None else xh[:, s], np.concatenate([uh[:, s:], tail], axis=1))
+                what = "%s N=%d s=%d %s" % (name, N, s, form)
+                assert_state_equal(state(dev), state(host), what + " after the shift " + turn)
+            dev.iterate(2)
+            host.iterate(2)
+            assert_state_equal(state(dev), state(host), what + " two iterations on")
     dev.close()
     host.close()
 
