@@ -381,6 +381,83 @@ int drv_get_trace(drv_t *d, int cap, double *lambda, double *gnorm, double *dV0,
     return d->n_trace;
 }
 
+/* ---- the generated file's additive forms (batched back-ends), on the host ----
+ * They are static functions and tables of iLQG_func.c: reachable only where that file is part of THIS translation unit
+ * (driver_with_func.c; oracle/Makefile lib*_forms.so).  Each entry exists exactly where the generated file emits the form
+ * (the macros it defines), so its absence from a library is the generator's statement that the problem is excluded. */
+#ifdef DRV_FUNC_IN_UNIT
+#if FULL_DDP && ILQG_TENSOR_NBASIS > 0
+/* the factored tensors of every step of the nominal (whose elements hold the auxiliaries of a forward_pass):
+ * basis [n_hor][ILQG_TENSOR_NBASIS] as bp_tensor_basis() gives it, ten [n_hor][N_X*(sizeofQxx + sizeofQuu + sizeofQxu)] =
+ * fxx fuu fxu as coef * basis[slice].  1 ok, 0 a guard failed */
+int drv_tensor_nbasis(void) { return ILQG_TENSOR_NBASIS; }
+int drv_factored_tensors(drv_t *d, double *ten, double *basis) {
+    int k, i, e;
+    for(k = 0; k < d->n_hor; k++) {
+        double *b = basis + (size_t)k * ILQG_TENSOR_NBASIS;
+        double *r = ten + (size_t)k * N_X * (sizeofQxx + sizeofQuu + sizeofQxu);
+        if(!bp_tensor_basis(b, &d->o.nominal->t[k], k, d->o.p)) return 0;
+        for(i = 0; i < N_X; i++)
+            for(e = 0; e < sizeofQxx; e++) *r++ = ilqg_tensor_coef_xx[i * sizeofQxx + e] * b[ilqg_tensor_slice_xx[i]];
+        for(i = 0; i < N_X; i++)
+            for(e = 0; e < sizeofQuu; e++) *r++ = ilqg_tensor_coef_uu[i * sizeofQuu + e] * b[ilqg_tensor_slice_uu[i]];
+        for(i = 0; i < N_X; i++)
+            for(e = 0; e < sizeofQxu; e++) *r++ = ilqg_tensor_coef_xu[i * sizeofQxu + e] * b[ilqg_tensor_slice_xu[i]];
+    }
+    return 1;
+}
+/* the tables themselves: coef [N_X*(sizeofQxx + sizeofQuu + sizeofQxu)] (xx, uu, xu), slice [3][N_X] */
+void drv_tensor_tables(double *coef, int *slice) {
+    memcpy(coef, ilqg_tensor_coef_xx, sizeof(ilqg_tensor_coef_xx));
+    memcpy(coef + N_X * sizeofQxx, ilqg_tensor_coef_uu, sizeof(ilqg_tensor_coef_uu));
+    memcpy(coef + N_X * (sizeofQxx + sizeofQuu), ilqg_tensor_coef_xu, sizeof(ilqg_tensor_coef_xu));
+    memcpy(slice, ilqg_tensor_slice_xx, sizeof(int) * N_X);
+    memcpy(slice + N_X, ilqg_tensor_slice_uu, sizeof(int) * N_X);
+    memcpy(slice + 2 * N_X, ilqg_tensor_slice_xu, sizeof(int) * N_X);
+}
+#endif
+
+#ifdef ILQG_ROLLOUT_PARTS
+/* ilqg_step_part over all parts at every (x, u) of the nominal: x_next [n_hor][N_X], cost [n_hor] = ((term[0] + term[1])
+ * + term[2]) + ...  1 ok, 0 a guarded value was NaN or Inf */
+int drv_step_parts(drv_t *d, double *x_next, double *cost) {
+    int k, part, i, bad = 0;
+    for(k = 0; k < d->n_hor; k++) {
+        trajEl_t *t = &d->o.nominal->t[k];
+        double term[ILQG_ROLLOUT_TERMS], c;
+        for(part = 0; part < ILQG_ROLLOUT_PARTS; part++)
+            ilqg_step_part(part, x_next + (size_t)k * N_X, term, &bad, t->x, t->u, k, d->o.p, d->n_hor);
+        c = term[0];
+        for(i = 1; i < ILQG_ROLLOUT_TERMS; i++) c = c + term[i];
+        cost[k] = c;
+    }
+    return !bad;
+}
+#endif
+
+#ifdef ILQG_DERIV_PARTS
+/* ilqg_deriv_prepare + ilqg_deriv_part over all parts, scattered through ILQG_DERIV_OUTPUTS into the elements of the
+ * nominal themselves (drv_get_derivs reads them; the record's fxx[0 .. ILQG_TENSOR_NBASIS) then holds the products, its
+ * other entries what init_opt wrote).  1 ok, 0 a guarded value was NaN or Inf */
+int drv_deriv_parts(drv_t *d) {
+    int k, q, o, bad = 0;
+    for(k = 0; k < d->n_hor; k++) {
+        trajEl_t *t = &d->o.nominal->t[k];
+        ilqg_deriv_aux_t aux;
+        double prod[ILQG_DERIV_NPROD], basis[ILQG_TENSOR_NBASIS], out[ILQG_DERIV_PARTS * ILQG_DERIV_PART_OUT];
+        ilqg_deriv_prepare(&aux, prod, basis, &bad, t->x, t->u, k, d->o.p, d->n_hor);
+        for(q = 0; q < ILQG_DERIV_PARTS; q++)
+            ilqg_deriv_part(q, out + q * ILQG_DERIV_PART_OUT, &bad, &aux, prod, basis, t->x, t->u, k, d->o.p, d->n_hor);
+        o = 0;
+#define DRV_SCATTER(member, index) t->member[index] = out[o++];
+        ILQG_DERIV_OUTPUTS(DRV_SCATTER)
+#undef DRV_SCATTER
+    }
+    return !bad;
+}
+#endif
+#endif /* DRV_FUNC_IN_UNIT */
+
 /* ---- many independent solves on host threads (CPU baseline of bench.py) ----
  * Trajectories i = 0..n-1 with x0 [n][N_X], u0 [n][n_hor][N_U]; options and
  * parameters are taken from `tmpl`.  Static split over `n_threads` threads, each

@@ -151,6 +151,11 @@ def lib_path(kind, problem="carparking", full_ddp=0):
         return os.path.join(HERE, "_ref", "libref_%s_fd%d.so" % (problem, full_ddp))
     if kind == "oracle":
         return os.path.join(HERE, "liboracle_%s_fd%d.so" % (problem, full_ddp))
+    # 'oracle' / 'ref' with the generated file in the harness's translation unit (FULL_DDP=1 only): Driver.forms()
+    if kind == "oracle_forms":
+        return os.path.join(HERE, "liboracle_%s_fd%d_forms.so" % (problem, full_ddp))
+    if kind == "ref_forms":
+        return os.path.join(HERE, "_ref", "libref_%s_fd%d_forms.so" % (problem, full_ddp))
     raise ValueError(kind)
 
 
@@ -196,6 +201,13 @@ def _bind(lib):
         lib.drv_cost_resweep.argtypes = [C.c_void_p]
     if hasattr(lib, "drv_get_bp_calls_pending"):
         lib.drv_get_bp_calls_pending.argtypes = [C.c_void_p]
+    if hasattr(lib, "drv_factored_tensors"):
+        lib.drv_factored_tensors.argtypes = [C.c_void_p, _dp, _dp]
+        lib.drv_tensor_tables.argtypes = [_dp, _ip]
+    if hasattr(lib, "drv_step_parts"):
+        lib.drv_step_parts.argtypes = [C.c_void_p, _dp, _dp]
+    if hasattr(lib, "drv_deriv_parts"):
+        lib.drv_deriv_parts.argtypes = [C.c_void_p]
     if hasattr(lib, "drv_solve_many"):
         lib.drv_solve_many.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _ip, _ip]
     return lib
@@ -321,6 +333,35 @@ class Driver:
         fin = np.zeros(self.nx + self.sxx)
         self.lib.drv_get_derivs(self.h, rec, fin)
         return rec, fin
+
+    def forms(self):
+        """which of the generated file's forms for batched back-ends this library can call ('*_forms' builds)"""
+        return {f for f in ("factored_tensors", "step_parts", "deriv_parts") if hasattr(self.lib, "drv_" + f)}
+
+    def factored_tensors(self):
+        """(fxx fuu fxu [N, n (sxx + suu + n m)] as coef * basis[slice], basis [N, NBASIS]) along the nominal"""
+        nb = self.lib.drv_tensor_nbasis()
+        ten = np.zeros((self.N, self.nx * (self.sxx + self.suu + self.nx * self.nu)))
+        basis = np.zeros((self.N, nb))
+        assert self.lib.drv_factored_tensors(self.h, ten, basis) == 1
+        return ten, basis
+
+    def tensor_tables(self):
+        """(coef [n (sxx + suu + n m)], slice [3, n]) of the factored tensors: xx, uu, xu"""
+        coef = np.zeros(self.nx * (self.sxx + self.suu + self.nx * self.nu))
+        sl = np.zeros((3, self.nx), dtype=np.int32)
+        self.lib.drv_tensor_tables(coef, sl)
+        return coef, sl
+
+    def step_parts(self):
+        """(x_next [N, n], cost [N]) of ilqg_step_part over all parts at the nominal's (x, u)"""
+        nxt, cost = np.zeros((self.N, self.nx)), np.zeros(self.N)
+        assert self.lib.drv_step_parts(self.h, nxt, cost) == 1
+        return nxt, cost
+
+    def deriv_parts(self):
+        """ilqg_deriv_prepare + ilqg_deriv_part over all parts, scattered into the nominal's records (derivs() reads them)"""
+        return self.lib.drv_deriv_parts(self.h)
 
     def set_derivs(self, rec, fin):
         self.lib.drv_set_derivs(self.h, np.ascontiguousarray(rec, dtype=np.float64), np.ascontiguousarray(fin, dtype=np.float64))

@@ -519,9 +519,20 @@ def lambda_goldens():
     print("lambda cases: %d cases, %d sequences, %d arrays, %d bytes" % (len(LC.CASES), len(LC.SEQS), len(out), os.path.getsize(LC.GOLDEN)))
 
 
+def deriv_truth_goldens():
+    """tests/deriv_cases.py: per case the points of the reference build's roll-out, parameters, multipliers, weights, the
+    derivatives of the problem's DEFINITION at them (mpmath; nothing of any build) and the reference build's measured worst
+    normalised error against them"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import deriv_cases as DC
+    out = DC.golden_of("ref")
+    np.savez_compressed(DC.GOLDEN, **out)
+    print("derivative truth: %d cases, %d arrays, %d bytes" % (len(DC.CASES), len(out), os.path.getsize(DC.GOLDEN)))
+
+
 def main(argv):
     """all fixtures, or only the named groups: brachi almix kernels car lockstep hx regtype2 regtype2cases linesearch multipliers
-    lambda synth synthp console vsref"""
+    lambda synth synthp console vsref derivtruth"""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     groups = {
         "brachi": brachi_goldens,
@@ -539,6 +550,7 @@ def main(argv):
         "synthp": lambda: synth_goldens(1, N=12, problem="synth16p", SYN_PARAMS=SYNP_PARAMS_TIGHT),
         "console": console_goldens,
         "vsref": vsref_goldens,
+        "derivtruth": deriv_truth_goldens,
     }
     for name in (argv or list(groups)):
         groups[name]()
