@@ -12,6 +12,7 @@
  *         per-trajectory solver state live in HBM, one launch sequence per
  *         lock-step iteration, no host round trip inside an iteration.
  */
+#include <float.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -870,13 +871,42 @@ static int policy_names(ilqg_batch_t *c, const char *who, int n_names, const cha
 }
 #define POLICY_VALUES_AT(w) (shared ? values : values + (size_t)c->first[g] * (size_t)n_starts * (size_t)(w))
 
-/* The six entries below.  params: the _params forms and the _noise forms with n_names != 0 (names resolved, at least one;
+/* Process noise drawn on the device (the _drawn forms and ilqg_batch_noise_table, see include/ilqg_batch.h): what the caller
+ * gives instead of a table.  `first` is the global index of THIS batch's trajectory 0; group g draws under first + first[g]. */
+typedef struct { unsigned long long seed; const double *sigma; int shared; long long first; } drawn_t;
+/* the ONE statement of what is refused of them, for a batch and for the whole of a sharded one: the message into err [n], B =
+ * the trajectories the counter's trajectory word must hold behind `first` (the shim repeats none of it: it is given what passed) */
+static int drawn_refused(char *err, size_t n, const char *who, const drawn_t *a, int B) {
+    int i;
+    if(!a->sigma) {
+        snprintf(err, n, "%s: sigma is NULL (the standard deviations of the N_X state components, host memory)", who);
+        return 1;
+    }
+    for(i = 0; i < N_X; i++)
+        if(!(a->sigma[i] >= 0.0 && a->sigma[i] <= DBL_MAX)) {
+            snprintf(err, n, "%s: sigma[%d] = %g, must be finite and not negative", who, i, a->sigma[i]);
+            return 1;
+        }
+    if(a->first < 0) {
+        snprintf(err, n, "%s: first_trajectory = %lld, must not be negative", who, a->first);
+        return 1;
+    }
+    if((unsigned long long)a->first + (unsigned long long)B > (1ull << 32)) {
+        snprintf(err, n, "%s: first_trajectory = %lld with B = %d trajectories: first_trajectory + B must not exceed 2^32 "
+                 "(the counter's trajectory word has 32 bits)", who, a->first, B);
+        return 1;
+    }
+    return 0;
+}
+static int drawn_args(ilqg_batch_t *c, const char *who, const drawn_t *a) { return drawn_refused(c->err, sizeof(c->err), who, a, c->B); }
+
+/* The entries below.  drawn: the _drawn forms (else NULL).  params: the _params forms and the _noise forms with n_names != 0 (names resolved, at least one;
  * else n_names is 0 here and names, values and shared are not read); on_device: the _device forms (device memory of the
  * caller, in the order of its stream, no wait); dist: the disturbance table of the _noise forms, [B][n_starts][n_hor][N_X] or
  * with dist_shared [n_starts][n_hor][N_X], NULL in the others. */
 static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_device, int n_starts, const double *x0, int n_names,
-                          const char *const *names, const double *values, int shared, const double *dist, int dist_shared, double alpha,
-                          int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream) {
+                          const char *const *names, const double *values, int shared, const double *dist, int dist_shared, const drawn_t *drawn,
+                          double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream) {
     const char *const what = params ? "policy_rollout_params" : "policy_rollout";
     const char *const what_stream = params ? "policy_rollout_params: stream" : "policy_rollout: stream";
     const named_ptr_t ptrs[] = {{x0, "x0"}, {params ? values : NULL, "values"}, {dist, "disturbance"}, {cost, "cost"}, {ok, "ok"},
@@ -884,12 +914,17 @@ static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_d
     int g, named[POLICY_MAX_NAMES], W = 0;
     if(policy_args(c, who, n_starts, x0)) return 1;
     if(params && policy_names(c, who, n_names, names, values, named, &W)) return 1;
+    if(drawn && drawn_args(c, who, drawn)) return 1;
     if(on_device && device_ptrs(c, who, ptrs, 8)) return 1;
     if(!cost && !ok && !x_end && !x && !u) return 0;
     if(push_config(c)) return 1;
     if(on_device && stream_in(c, stream, what_stream)) return 1;
     EACH_GROUP(g) {
-        if(ilqg_dev_policy_rollout(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared,
+        if(drawn ? ilqg_dev_policy_rollout_drawn(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared,
+                                                 drawn->seed, drawn->sigma, drawn->shared, drawn->first + c->first[g], alpha, feedback,
+                                                 POLICY_AT(cost, 1), POLICY_AT(ok, 1), POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X),
+                                                 POLICY_AT(u, (size_t)c->N * N_U), on_device)
+                 : ilqg_dev_policy_rollout(c->dev[g], n_starts, POLICY_AT(x0, N_X), n_names, named, params ? POLICY_VALUES_AT(W) : NULL, shared,
                                    dist_shared ? dist : POLICY_AT(dist, (size_t)c->N * N_X), dist_shared, alpha, feedback, POLICY_AT(cost, 1), POLICY_AT(ok, 1),
                                    POLICY_AT(x_end, N_X), POLICY_AT(x, (size_t)(c->N + 1) * N_X), POLICY_AT(u, (size_t)c->N * N_U), on_device))
             return fail(c, what);
@@ -900,25 +935,25 @@ static int policy_rollout(ilqg_batch_t *c, const char *who, int params, int on_d
 
 int ilqg_batch_policy_rollout(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                               double *x_end, double *x, double *u) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout", 0, 0, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, alpha, feedback, cost, ok, x_end, x, u, NULL);
+    return policy_rollout(c, "ilqg_batch_policy_rollout", 0, 0, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, NULL, alpha, feedback, cost, ok, x_end, x, u, NULL);
 }
 
 int ilqg_batch_policy_rollout_device(ilqg_batch_t *c, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                                      double *x_end, double *x, double *u, void *stream) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout_device", 0, 1, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, alpha, feedback, cost, ok, x_end, x, u,
+    return policy_rollout(c, "ilqg_batch_policy_rollout_device", 0, 1, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, NULL, alpha, feedback, cost, ok, x_end, x, u,
                           stream);
 }
 
 int ilqg_batch_policy_rollout_params(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                      int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout_params", 1, 0, n_starts, x0, n_names, names, values, shared, NULL, 0, alpha, feedback, cost, ok,
+    return policy_rollout(c, "ilqg_batch_policy_rollout_params", 1, 0, n_starts, x0, n_names, names, values, shared, NULL, 0, NULL, alpha, feedback, cost, ok,
                           x_end, x, u, NULL);
 }
 
 int ilqg_batch_policy_rollout_params_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
                                             const double *values, int shared, double alpha, int feedback, double *cost, int *ok, double *x_end,
                                             double *x, double *u, void *stream) {
-    return policy_rollout(c, "ilqg_batch_policy_rollout_params_device", 1, 1, n_starts, x0, n_names, names, values, shared, NULL, 0, alpha, feedback,
+    return policy_rollout(c, "ilqg_batch_policy_rollout_params_device", 1, 1, n_starts, x0, n_names, names, values, shared, NULL, 0, NULL, alpha, feedback,
                           cost, ok, x_end, x, u, stream);
 }
 
@@ -929,7 +964,7 @@ int ilqg_batch_policy_rollout_noise(ilqg_batch_t *c, int n_starts, const double 
                                     int *ok, double *x_end, double *x, double *u) {
     const int params = n_names != 0;
     return policy_rollout(c, "ilqg_batch_policy_rollout_noise", params, 0, n_starts, x0, params ? n_names : 0, names, values, params ? shared : 0,
-                          disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u, NULL);
+                          disturbance, disturbance_shared, NULL, alpha, feedback, cost, ok, x_end, x, u, NULL);
 }
 
 int ilqg_batch_policy_rollout_noise_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
@@ -937,7 +972,64 @@ int ilqg_batch_policy_rollout_noise_device(ilqg_batch_t *c, int n_starts, const 
                                            int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream) {
     const int params = n_names != 0;
     return policy_rollout(c, "ilqg_batch_policy_rollout_noise_device", params, 1, n_starts, x0, params ? n_names : 0, names, values,
-                          params ? shared : 0, disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u, stream);
+                          params ? shared : 0, disturbance, disturbance_shared, NULL, alpha, feedback, cost, ok, x_end, x, u, stream);
+}
+
+/* The same roll-outs with the noise drawn on the device from a seed (see include/ilqg_batch.h): the arguments of the _noise
+ * forms with the table replaced by what the draw needs. */
+int ilqg_batch_policy_rollout_drawn(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory,
+                                    double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    const int params = n_names != 0;
+    const drawn_t drawn = {seed, sigma, noise_shared, first_trajectory};
+    return policy_rollout(c, "ilqg_batch_policy_rollout_drawn", params, 0, n_starts, x0, params ? n_names : 0, names, values, params ? shared : 0,
+                          NULL, 0, &drawn, alpha, feedback, cost, ok, x_end, x, u, NULL);
+}
+
+int ilqg_batch_policy_rollout_drawn_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
+                                           const double *values, int shared, unsigned long long seed, const double *sigma, int noise_shared,
+                                           long long first_trajectory, double alpha, int feedback, double *cost, int *ok, double *x_end,
+                                           double *x, double *u, void *stream) {
+    const int params = n_names != 0;
+    const drawn_t drawn = {seed, sigma, noise_shared, first_trajectory};
+    return policy_rollout(c, "ilqg_batch_policy_rollout_drawn_device", params, 1, n_starts, x0, params ? n_names : 0, names, values,
+                          params ? shared : 0, NULL, 0, &drawn, alpha, feedback, cost, ok, x_end, x, u, stream);
+}
+
+/* the same draws as a table: w [B][n_starts][n_hor][N_X], every group its rows; shared [n_starts][n_hor][N_X], written by group 0 */
+static int noise_table(ilqg_batch_t *c, const char *who, int on_device, int n_starts, const drawn_t *drawn, double *w, void *stream) {
+    const named_ptr_t ptrs[] = {{w, "w"}};
+    int g;
+    if(n_starts < 1) {
+        snprintf(c->err, sizeof(c->err), "%s: n_starts = %d, must be at least 1", who, n_starts);
+        return 1;
+    }
+    if(drawn_args(c, who, drawn)) return 1;
+    if(!w) {
+        snprintf(c->err, sizeof(c->err), "%s: w is NULL (the table, [B][n_starts][n_hor][N_X] or with noise_shared [n_starts][n_hor][N_X])", who);
+        return 1;
+    }
+    if(on_device && (device_ptrs(c, who, ptrs, 1) || stream_in(c, stream, "noise_table: stream"))) return 1;
+    EACH_GROUP(g) {
+        if(drawn->shared && g > 0) break;
+        if(ilqg_dev_noise_table(c->dev[g], n_starts, drawn->seed, drawn->sigma, drawn->shared, drawn->first + c->first[g],
+                                drawn->shared ? w : POLICY_AT(w, (size_t)c->N * N_X), on_device))
+            return fail(c, "noise_table");
+        if(on_device && ilqg_dev_stream_out(c->dev[g], stream)) return fail(c, "noise_table: stream");
+    }
+    return 0;
+}
+
+int ilqg_batch_noise_table(ilqg_batch_t *c, int n_starts, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory,
+                           double *w) {
+    const drawn_t drawn = {seed, sigma, noise_shared, first_trajectory};
+    return noise_table(c, "ilqg_batch_noise_table", 0, n_starts, &drawn, w, NULL);
+}
+
+int ilqg_batch_noise_table_device(ilqg_batch_t *c, int n_starts, unsigned long long seed, const double *sigma, int noise_shared,
+                                  long long first_trajectory, double *w, void *stream) {
+    const drawn_t drawn = {seed, sigma, noise_shared, first_trajectory};
+    return noise_table(c, "ilqg_batch_noise_table_device", 1, n_starts, &drawn, w, stream);
 }
 
 /* the wave mapping carries no parameters per trajectory: refused by every entry that would set or read them */
@@ -2702,18 +2794,25 @@ int ilqg_multi_head(ilqg_multi_t *m, int steps, double *x, double *u, double *l,
             return multi_fail(m, g);
     return 0;
 }
-/* the three entries below: every shard's part through the worker of ilqg_batch_policy_rollout / _params / _noise (a full
- * disturbance table sharded by rows, a shared one given to every shard) */
+/* the four entries below: every shard's part through the worker of ilqg_batch_policy_rollout / _params / _noise / _drawn (a full
+ * disturbance table sharded by rows, a shared one given to every shard; drawn noise under the shard's own first trajectory) */
 static int multi_policy_rollout(ilqg_multi_t *m, const char *who, int params, int n_starts, const double *x0, int n_names, const char *const *names,
-                                const double *values, int shared, const double *dist, int dist_shared, double alpha, int feedback, double *cost,
-                                int *ok, double *x_end, double *x, double *u) {
+                                const double *values, int shared, const double *dist, int dist_shared, const drawn_t *drawn, double alpha, int feedback,
+                                double *cost, int *ok, double *x_end, double *x, double *u) {
     const size_t W = (params && values && !shared) ? rows_width(n_names, names) : 0;
     const size_t r = n_starts > 0 ? (size_t)n_starts : 0;
     int g;
+    /* (the whole batch's range of trajectory words, before the first shard launches: a shard sees only its own) */
+    if(drawn && drawn_refused(m->err, sizeof(m->err), "ilqg_multi_policy_rollout_drawn", drawn, m->B)) return 1;
     EACH_SHARD(g) {
         const size_t at = (size_t)m->first[g] * r;
+        drawn_t mine;
+        if(drawn) {
+            mine = *drawn;
+            mine.first += m->first[g];
+        }
         if(policy_rollout(m->shard[g], who, params, 0, n_starts, x0 ? x0 + at * N_X : NULL, n_names, names, values ? values + at * W : NULL, shared,
-                          (dist && !dist_shared) ? dist + at * (size_t)m->N * N_X : dist, dist_shared, alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
+                          (dist && !dist_shared) ? dist + at * (size_t)m->N * N_X : dist, dist_shared, drawn ? &mine : NULL, alpha, feedback, cost ? cost + at : NULL, ok ? ok + at : NULL, x_end ? x_end + at * N_X : NULL,
                           x ? x + at * (size_t)(m->N + 1) * N_X : NULL, u ? u + at * (size_t)m->N * N_U : NULL, NULL))
             return multi_fail(m, g);
     }
@@ -2721,11 +2820,11 @@ static int multi_policy_rollout(ilqg_multi_t *m, const char *who, int params, in
 }
 int ilqg_multi_policy_rollout(ilqg_multi_t *m, int n_starts, const double *x0, double alpha, int feedback, double *cost, int *ok,
                               double *x_end, double *x, double *u) {
-    return multi_policy_rollout(m, "ilqg_batch_policy_rollout", 0, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, alpha, feedback, cost, ok, x_end, x, u);
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout", 0, n_starts, x0, 0, NULL, NULL, 0, NULL, 0, NULL, alpha, feedback, cost, ok, x_end, x, u);
 }
 int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                      int shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
-    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_params", 1, n_starts, x0, n_names, names, values, shared, NULL, 0, alpha, feedback, cost,
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_params", 1, n_starts, x0, n_names, names, values, shared, NULL, 0, NULL, alpha, feedback, cost,
                                 ok, x_end, x, u);
 }
 int ilqg_multi_policy_rollout_noise(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
@@ -2733,7 +2832,15 @@ int ilqg_multi_policy_rollout_noise(ilqg_multi_t *m, int n_starts, const double 
                                     int *ok, double *x_end, double *x, double *u) {
     const int params = n_names != 0;
     return multi_policy_rollout(m, "ilqg_batch_policy_rollout_noise", params, n_starts, x0, params ? n_names : 0, names, params ? values : NULL,
-                                params ? shared : 0, disturbance, disturbance_shared, alpha, feedback, cost, ok, x_end, x, u);
+                                params ? shared : 0, disturbance, disturbance_shared, NULL, alpha, feedback, cost, ok, x_end, x, u);
+}
+int ilqg_multi_policy_rollout_drawn(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory,
+                                    double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+    const int params = n_names != 0;
+    const drawn_t drawn = {seed, sigma, noise_shared, first_trajectory};
+    return multi_policy_rollout(m, "ilqg_batch_policy_rollout_drawn", params, n_starts, x0, params ? n_names : 0, names, params ? values : NULL,
+                                params ? shared : 0, NULL, 0, &drawn, alpha, feedback, cost, ok, x_end, x, u);
 }
 /* the two entries below: every shard's part through its own entry, ilqg_batch_receding_plant or (windowed) _plant_windows.  A
  * future is offset by the shard's first trajectory where its name has rows in the shard; what the shard would refuse (a name

@@ -19,6 +19,8 @@
 //   k_select     lane = traj           line_search selection  line_search.c:37-75
 //   k_update     lane = traj           accept / reject        iLQG.c:311-361
 //   k_policy     lane = (traj, start)  forward_pass from the caller's starts, nothing stored in the batch
+//   k_policy_drawn                     the same with process noise drawn in registers from a seed (k_noise.inc); N_X <= 8 only:
+//                                      where N_X > 8 k_policy itself draws, on a run-time argument (k_policy.inc)
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -975,7 +977,9 @@ __global__ void k_from_dev(const double *__restrict__ dev, double *__restrict__ 
 
 #include "k_mpc_io.inc"  // k_head, k_shift_param_rows, k_shift_windows (the control interval of a caller with its own plant)
 
-#include "k_policy.inc"  // k_policy (roll-outs of every plan's feedback policy from the caller's starts)
+#include "k_noise.inc"  // the draw of the roll-outs' process noise stated once; k_noise_fill (the same draws as a table)
+
+#include "k_policy.inc"  // k_policy, k_policy_drawn (roll-outs of every plan's feedback policy from the caller's starts)
 
 #include "k_plant.inc"  // k_plant (the plant of a closed loop: `steps` steps per round from a state of its own)
 

@@ -131,6 +131,9 @@ enum {
 enum {
     ILQG_K_BEST_OF = ILQG_K_COUNT, /* candidates per agent: k_best_of (ilqg_dev_best_of) */
     ILQG_K_SHIFT_WINNERS,          /*                       k_shift_winners_lane / _wave (ilqg_dev_shift_winners) */
+    ILQG_K_POLICY_DRAWN,           /* process noise drawn on the device: the drawn launch of ilqg_dev_policy_rollout_drawn — k_policy_drawn, or (N_X > 8) k_policy with `spec` */
+    ILQG_K_POLICY_DRAWN_PARAMS,    /*                       the same with a table of parameter rows (k_policy_drawn<true> / k_policy<true>) */
+    ILQG_K_NOISE_FILL,             /*                       k_noise_fill (ilqg_dev_noise_table) */
     ILQG_K_TOTAL
 };
 
@@ -270,6 +273,23 @@ int ilqg_dev_head(ilqg_dev_t *d, int steps, double *x, double *u, double *l, dou
 int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
                             const double *dist, int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u,
                             int on_device);
+/* The same roll-outs with the process noise DRAWN ON THE DEVICE (k_noise.inc, k_policy_drawn): no table, no upload and no
+ * memory proportional to R.  Row (b, r, k) is w[i] = sigma[i] z[i], z the standard normals of Philox4x32-10 under the key
+ * (seed & 0xffffffff, seed >> 32) at the counter (k, r, first_trajectory + b, i / 4) — with noise_shared != 0 the trajectory
+ * word is 0: every trajectory gets the draws of trajectory 0 —, added by the rule of `dist` above.  A draw depends on its
+ * counter alone: its bits are those of any other R, stream group, shard (first_trajectory = the context's first trajectory
+ * in the caller's batch) or chunk.  sigma: N_X doubles in HOST memory in every form, each finite and >= 0; first_trajectory
+ * >= 0 and first_trajectory + batch <= 2^32 (the caller has checked: ilqg_host.c).  Every other argument as in
+ * ilqg_dev_policy_rollout.  The launch runs under timing slots of its own, "k_policy_drawn" / "k_policy_drawn_params": in a
+ * library of a problem with N_X <= 8 they time the kernels of that name; in one with N_X > 8 there is no such kernel and they
+ * time k_policy launched with its third noise argument (k_policy.inc says why).
+ * noise_table: the same draws as a table, w [batch][R][n_hor][N_X] or with noise_shared [R][n_hor][N_X] (k_noise_fill) — what
+ * ilqg_dev_policy_rollout's `dist` of the same call is, bit for bit.  Changes nothing of the context. */
+int ilqg_dev_policy_rollout_drawn(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                  unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory, double alpha, int feedback,
+                                  double *cost, int *ok, double *x_end, double *x, double *u, int on_device);
+int ilqg_dev_noise_table(ilqg_dev_t *d, int R, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory, double *w,
+                         int on_device);
 /* The receding-horizon loop that stays on the device: `rounds` times { ilqg_dev_iterate; ilqg_dev_loop_apply; ilqg_dev_loop_shift;
  * ilqg_dev_rollout_init; ilqg_dev_reset } between one ilqg_dev_loop_begin and one ilqg_dev_loop_read — the caller's loop;
  * nothing in it waits or copies.  What the loop is, is stated once, here: */

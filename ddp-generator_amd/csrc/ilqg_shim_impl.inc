@@ -131,6 +131,7 @@ struct DevBuffers {
     // the parameter rows [B][W] with their map, the disturbances [B][rounds * steps][NX]
     Buffer<double> plant_xp, plant_cost, plant_values, plant_dist;
     Buffer<int> plant_failed;
+    Buffer<NoiseSpec> noise_spec;          // what a drawn launch reads of its caller (k_noise.inc), written in stream order by noise_spec_put
     // per-trajectory problem parameters (ilqg_dev_set_params_batch): the rows [B][W]; the buffer only grows and outlives a cleared set
     Buffer<double> pb_values;
     // per-time-step parameters per trajectory (ilqg_dev_set_param_steps_batch): for the s-th parameter of size -1 its rows
@@ -625,7 +626,7 @@ const char *ilqg_dev_kernel_name(int k) {
                                               "k_log_steps", "k_head", "k_shift_param", "k_policy", "k_policy_params", "k_plant", "k_shift_param_rows",
                                               "k_shift_windows", "k_history"};
     // (the slots behind the history's, in ilqg_shim.h's second list)
-    static const char *later[ILQG_K_TOTAL - ILQG_K_COUNT] = {"k_best_of", "k_shift_winners"};
+    static const char *later[ILQG_K_TOTAL - ILQG_K_COUNT] = {"k_best_of", "k_shift_winners", "k_policy_drawn", "k_policy_drawn_params", "k_noise_fill"};
     if(k >= ILQG_K_COUNT && k < ILQG_K_TOTAL) return later[k - ILQG_K_COUNT];
     return (k >= 0 && k < ILQG_K_COUNT) ? names[k] : "?";
 }
@@ -1508,16 +1509,29 @@ static const PolicyParamMap *policy_param_map(int n_named, const int *named, con
 }
 // map == nullptr: k_policy<false>; else the same under the rows of `values` (device memory), k_policy<true>.  Each has its
 // own timing slot.
+// spec == nullptr: no noise or the table `dist`; else the noise drawn from *spec (device memory; dist is not read), under the
+// timing slots of the drawn form: k_policy_drawn where the library has that kernel, k_policy's third noise argument where it
+// has one kernel (ILQG_POLICY_ONE_KERNEL, k_policy.inc).
 static int launch_policy(ilqg_dev_t *d, int R, const double *x0, const PolicyParamMap *map, const double *values, int shared, const double *dist,
-                         int dist_shared, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
+                         int dist_shared, const NoiseSpec *spec, double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u) {
     if(roll_enter(d)) return 1;
     const dim3 grid = grid1((size_t)d->B * (size_t)R, ROLL_BLOCK);
     {   // (with a per-trajectory table — lane mapping only — the trajectory's row goes first, the roll-out's behind it)
-        Timed t(d, map ? ILQG_K_POLICY_PARAMS : ILQG_K_POLICY, roll_stream(d));
+        Timed t(d, spec ? (map ? ILQG_K_POLICY_DRAWN_PARAMS : ILQG_K_POLICY_DRAWN) : (map ? ILQG_K_POLICY_PARAMS : ILQG_K_POLICY), roll_stream(d));
         with_rows(d, [&](auto... tr) {
             with_own_rows(map != nullptr, [&](auto... own) {
+#if ILQG_POLICY_ONE_KERNEL
                 hipLaunchKernelGGL((k_policy<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P, d->O,
-                                   d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, dist, dist_shared ? 1 : 0, tr..., own...);
+                                   d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, spec ? nullptr : dist, dist_shared ? 1 : 0, spec, tr...,
+                                   own...);
+#else
+                if(spec)
+                    hipLaunchKernelGGL((k_policy_drawn<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid, dim3(ROLL_BLOCK), 0,
+                                       roll_stream(d), d->P, d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, spec, tr..., own...);
+                else
+                    hipLaunchKernelGGL((k_policy<sizeof...(own) != 0, decltype(tr)..., decltype(own)...>), grid, dim3(ROLL_BLOCK), 0, roll_stream(d), d->P,
+                                       d->O, d->pv, R, x0, alpha, feedback ? 1 : 0, cost, ok, x_end, x, u, dist, dist_shared ? 1 : 0, tr..., own...);
+#endif
             }, values, shared ? 1 : 0, map ? *map : PolicyParamMap{});
         });
     }
@@ -1547,7 +1561,77 @@ int ilqg_dev_policy_rollout(ilqg_dev_t *d, int R, const double *x0, int n_named,
     io.out(x_end, n * NX * sizeof(double));
     io.out(x, n * (size_t)(d->N + 1) * NX * sizeof(double));
     io.out(u, n * (size_t)d->N * NU * sizeof(double));
-    if(io.open() || launch_policy(d, R, x0, map, values, shared, dist, dist_shared, alpha, feedback, cost, ok, x_end, x, u)) return 1;
+    if(io.open() || launch_policy(d, R, x0, map, values, shared, dist, dist_shared, nullptr, alpha, feedback, cost, ok, x_end, x, u)) return 1;
+    return io.close();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Process noise drawn on the device (k_noise.inc).  The caller's seed, sigma (HOST memory in every form), shared flag and
+// first trajectory travel as ONE NoiseSpec in the context's own device buffer, copied in the order of the context's stream:
+// a launch that follows on that stream (or, between roll_enter and roll_leave, on the roll-out family's) reads this call's
+// block, and the next call's copy waits for it.  sigma and first_trajectory arrive checked (ilqg_host.c drawn_refused: sigma
+// N_X finite doubles >= 0, 0 <= first_trajectory, first_trajectory + batch <= 2^32).
+// ---------------------------------------------------------------------------------------------------------------------
+static int noise_spec_put(ilqg_dev_t *d, const char *who, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory) {
+    NoiseSpec s;
+    s.key0 = (unsigned)(seed & 0xffffffffull);
+    s.key1 = (unsigned)(seed >> 32);
+    s.first = (unsigned)first_trajectory;
+    s.shared = noise_shared ? 1 : 0;
+    for(int i = 0; i < NX; i++) s.sigma[i] = sigma[i];
+    if(d->noise_spec.reserve(sizeof(NoiseSpec))) return 1;
+    // (pageable memory of this frame: the runtime has taken its copy when the call returns)
+    HIP_TRY(hipMemcpyAsync(d->noise_spec.get(), &s, sizeof(NoiseSpec), hipMemcpyHostToDevice, d->stream));
+    return 0;
+}
+int ilqg_dev_policy_rollout_drawn(ilqg_dev_t *d, int R, const double *x0, int n_named, const int *named, const double *values, int shared,
+                                  unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory, double alpha, int feedback,
+                                  double *cost, int *ok, double *x_end, double *x, double *u, int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    NEED_PARAMS(d);
+    PolicyParamMap table;
+    const PolicyParamMap *map = nullptr;
+    if(!policy_args_ok(d, R, x0) || (n_named != 0 && !(map = policy_param_map(n_named, named, values, table)))) return 1;
+    if(!cost && !ok && !x_end && !x && !u) return 0;
+    const size_t n = (size_t)d->B * (size_t)R;
+    if(noise_spec_put(d, "policy_rollout_drawn", seed, sigma, noise_shared, first_trajectory)) return 1;
+    Staged io(d, on_device);
+    io.in(x0, n * NX * sizeof(double));
+    io.in(values, map ? (shared ? (size_t)R : n) * (size_t)map->W * sizeof(double) : 0);
+    io.out(cost, n * sizeof(double));
+    io.out(ok, n * sizeof(int));
+    io.out(x_end, n * NX * sizeof(double));
+    io.out(x, n * (size_t)(d->N + 1) * NX * sizeof(double));
+    io.out(u, n * (size_t)d->N * NU * sizeof(double));
+    if(io.open() || launch_policy(d, R, x0, map, values, shared, nullptr, 0, d->noise_spec.get(), alpha, feedback, cost, ok, x_end, x, u)) return 1;
+    return io.close();
+}
+
+int ilqg_dev_noise_table(ilqg_dev_t *d, int R, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory, double *w,
+                         int on_device) {
+    HIP_TRY(hipSetDevice(d->device));
+    if(R < 1) {
+        g_err = "noise_table: n_starts must be at least 1";
+        return 1;
+    }
+    if(!w) {
+        g_err = "noise_table: w is NULL (the table, [batch][n_starts][n_hor][N_X] or shared [n_starts][n_hor][N_X])";
+        return 1;
+    }
+    const size_t rows = (noise_shared ? (size_t)1 : (size_t)d->B) * (size_t)R * (size_t)d->N;
+    if((rows + 255) / 256 > (size_t)0x7fffffff) {
+        g_err = "noise_table: n_starts is too large for one launch";
+        return 1;
+    }
+    if(noise_spec_put(d, "noise_table", seed, sigma, noise_shared, first_trajectory)) return 1;
+    Staged io(d, on_device);
+    io.out(w, rows * NX * sizeof(double));
+    if(io.open()) return 1;
+    {
+        Timed t(d, ILQG_K_NOISE_FILL);
+        hipLaunchKernelGGL(k_noise_fill, grid1(rows, 256), dim3(256), 0, d->stream, (const NoiseSpec *)d->noise_spec.get(), rows, R, d->N, w);
+    }
+    HIP_TRY(hipGetLastError());
     return io.close();
 }
 

@@ -34,6 +34,7 @@
 // included; such a lane stays out of the later guarded steps as one whose guard failed does.  A lane's row is NX doubles
 // from its own 8-byte-aligned place, read right before the add: requested ahead of the step, as k_plant does with its
 // one lane per trajectory, the row lives across the step and costs its registers (profiles/r17_policy_noise.txt).
+// k_policy_drawn is the same roll-out with the row DRAWN in registers behind the step instead of read (below, k_noise.inc).
 __device__ __forceinline__ void load_policy_step(NomStep &s, const NomPtrs &q, bool use_l, bool use_K) {
 #pragma unroll
     for(int i = 0; i < NU; i++) s.u[i] = q.u[i * XSI];
@@ -79,132 +80,39 @@ __device__ __forceinline__ void policy_control(double (&uin)[NU], const NomStep 
     }
 }
 
-template <bool PER_ROLLOUT_PARAMS, class... Rows>
-__global__ __launch_bounds__(ROLL_BLOCK) void k_policy(DevPtrs P, ilqg_dev_opts_t O, ParamValues A, int R, const double *__restrict__ x0,
-                                                       double alpha, int feedback, double *__restrict__ ocost, int *__restrict__ ook,
-                                                       double *__restrict__ oxe, double *__restrict__ ox, double *__restrict__ ou,
-                                                       const double *__restrict__ dist, int dist_shared, Rows... rows) {
-    // the pack: [the context's per-trajectory table, its map,] [values, shared, map of the roll-outs' own rows] (RowPack)
-    const size_t g = (size_t)blockIdx.x * ROLL_BLOCK + threadIdx.x;
-    if(g >= (size_t)P.B * (size_t)R) return;
-    const int b = (int)(g / (size_t)R);
-    const int N = P.N;
-    const bool use_l = (alpha != 0.0), use_K = (feedback != 0);
+// One text for the policy roll-out kernels (k_policy_body.inc), included once per kernel and no forceinline body: a kernel's
+// name is its timing slot and its resources, and with the roll-out in a function of its own the inliner treats the callbacks
+// differently (see ILQG_FORWARD_STEP in ilqg_kernels.hip) — measured, k_policy<false> went from 1 293 to 1 221 instructions in
+// CarParking's library and from 4 794 to 9 290 with 1 329 spilled registers in the n = 16 pair's.
+//
+// Process noise drawn on the device (spec: NoiseSpec in device memory, k_noise.inc).  Behind step k the lane draws the
+// ceil(NX / 4) counter blocks (k, r, t, j) of its row and adds them where the table's row is added — the same rule, and with
+// the table k_noise_fill writes for the same NoiseSpec the same bits in every output.  No table, no memory proportional to R.
+//   N_X <= 8   a kernel of its own, k_policy_drawn: every k_policy instantiation is the code it was before there was a second
+//              form (profiles/r23_policy_drawn.txt), and neither kernel uses scratch memory.
+//   N_X > 8    (the problems whose roll-outs keep their trajEl_t in scratch memory, 3 472 to 48 432 bytes per lane) ONE
+//              kernel, k_policy, with `spec` as a third run-time noise argument beside `dist` — null: the call as it was, a
+//              wave-uniform branch per step.  A second kernel name would be a second kernel with scratch memory, which
+//              tests/test_kernel_budget.py allows the names of tests/golden/kernel_scratch_parent.json only (the reason
+//              `dist` is a run-time argument too).  The drawn launch still has its own timing slot: the slot is the shim's.
+#if N_X > 8
+#define ILQG_POLICY_ONE_KERNEL 1
+#define ILQG_POLICY_KERNEL k_policy
+#define ILQG_POLICY_DRAWN 2
+#include "k_policy_body.inc"
+#undef ILQG_POLICY_KERNEL
+#undef ILQG_POLICY_DRAWN
+#else
+#define ILQG_POLICY_ONE_KERNEL 0
+#define ILQG_POLICY_KERNEL k_policy
+#define ILQG_POLICY_DRAWN 0
+#include "k_policy_body.inc"
+#undef ILQG_POLICY_KERNEL
+#undef ILQG_POLICY_DRAWN
 
-    double xc[NX];
-    bool finite = true;
-#pragma unroll
-    for(int i = 0; i < NX; i++) {
-        xc[i] = x0[g * NX + i];  // o->x0 (iLQG_func.tem:141-142)
-        finite &= (__builtin_fabs(xc[i]) < __builtin_inf());
-    }
-    if(!finite) {
-        if(ook) ook[g] = 0;
-        if(ocost) ocost[g] = __builtin_nan("");
-        return;
-    }
-
-    // this roll-out's row of the disturbance table at step k: ((dist_shared ? r : g) * N + k) * NX, moved on step by step.
-    // Computed HERE, in front of the parameters: behind them the scalar registers are the parameters' (k_policy<true> of
-    // synth16p, the n = 16 pair with stored tensors, has none left for dist_shared: its library then does not compile).
-    size_t wat = (dist_shared ? g - (size_t)b * (size_t)R : g) * (size_t)N * NX;
-    asm volatile("" : "+v"(wat));
-
-    ILQG_CALLBACKS(C, H);
-    apply_rows<PER_ROLLOUT_PARAMS ? OWN_ROLLOUT : OWN_NONE>(C_values, C_table, P, b, g, (int)(g - (size_t)b * (size_t)R), rows...);
-    load_penalty_weights(C, P, b);
-    el_t ct;
-    multipliersEl_t mk;
-    multipliersEl_t *const mp = HAS_MUL ? &mk : nullptr;
-#if ILQG_DEV_EL
-    ilqgdev::set_mode(ilqgdev::DISCARD);
-    [[clang::always_inline]]  // (see k_rollout)
+#define ILQG_POLICY_KERNEL k_policy_drawn
+#define ILQG_POLICY_DRAWN 1
+#include "k_policy_body.inc"
+#undef ILQG_POLICY_KERNEL
+#undef ILQG_POLICY_DRAWN
 #endif
-    init_running(&ct, &C.o1);
-
-    NomPtrs q;
-    q.x = cur_x(P, 0, b);
-    q.u = cur_u(P, 0, b);
-    q.l = nomp(P, 0, b) + NOM_L;
-    q.K = nomp(P, 0, b) + NOM_K;
-    const size_t xs = cur_xstride(P), us = cur_ustride(P);
-    constexpr int ks = RN;
-    size_t xat = g * (size_t)(N + 1) * NX, uat = g * (size_t)N * NU;  // this roll-out's step in x / u
-
-    double csum = 0.0;
-    int okc = 1;
-    NomStep cur = {};
-    load_policy_step(cur, q, use_l, use_K);
-    drain_memory_ops();
-    for(int k = 0; k < N; k++) {
-        NomPtrs qn;
-        qn.x = q.x + xs;
-        qn.u = q.u + us;
-        qn.l = q.l + ks;
-        qn.K = q.K + ks;
-        double xin[NX], uin[NU];
-#pragma unroll
-        for(int i = 0; i < NX; i++) xin[i] = xc[i];
-        policy_control(uin, cur, q.K, xin, alpha, use_l, use_K);
-
-        // the next step's nominal data, in flight while the step computes (the records have a step N; the tiled U has not)
-        if(k + 1 >= N) qn.u = q.u;
-        load_policy_step(cur, qn, use_l, use_K);
-
-        if(HAS_MUL) load_mul(P, k, b, mk);
-        double xnext[NX];
-        auto step = ILQG_FORWARD_STEP(false, ct, mp, k, N, C, xin, uin, xnext);
-        const int r = run_step(H, okc, step);
-        okc &= r;
-        csum += ct.c;
-        if(ox) {
-#pragma unroll
-            for(int i = 0; i < NX; i++) ox[xat + i] = ct.x[i];
-            xat += NX;
-        }
-        if(ou) {
-#pragma unroll
-            for(int i = 0; i < NU; i++) ou[uat + i] = ct.u[i];
-            uat += NU;
-        }
-        if(dist) {  // x_{k+1} <- x_next + w_k: the row is read HERE, behind the step (held across it, it costs the step's registers)
-            bool good = true;
-#pragma unroll
-            for(int i = 0; i < NX; i++) {
-                xnext[i] = xnext[i] + dist[wat + i];
-                good &= (__builtin_fabs(xnext[i]) < __builtin_inf());
-            }
-            wat += NX;
-            okc &= good ? 1 : 0;
-        }
-#pragma unroll
-        for(int i = 0; i < NX; i++) xc[i] = xnext[i];
-        q = qn;
-    }
-    {
-        trajFin_t cf;
-        multipliersFin_t mf;
-        if(HAS_MUL) load_mul_fin(P, b, mf);
-        init_final(&cf, &C.o);
-        auto fin = [&]() {
-#pragma unroll
-            for(int i = 0; i < NX; i++) cf.x[i] = xc[i];
-            int r = calcFVariableAux(&cf, HAS_MUL ? &mf : nullptr, &C.o);
-            r &= ddpF(&cf, &C.o);
-            return r;
-        };
-        const int r = run_step(H, okc, fin);
-        okc &= r;
-        csum += cf.c;
-        if(ox) {
-#pragma unroll
-            for(int i = 0; i < NX; i++) ox[xat + i] = cf.x[i];
-        }
-        if(oxe) {
-#pragma unroll
-            for(int i = 0; i < NX; i++) oxe[g * NX + i] = cf.x[i];
-        }
-    }
-    if(ocost) ocost[g] = csum;
-    if(ook) ook[g] = (okc && H.nonfinite == 0.0) ? 1 : 0;
-}

@@ -454,20 +454,57 @@ def _rollout_disturbance(solver, disturbance, R, device=None):
     return _cuda_address(a, shape, device, "%s: %s" % (who, what)), shared, a
 
 
-def _policy_rollout(solver, entry, x0, alpha, feedback, trajectories, params, disturbance=None):
+def _drawn_noise(solver, who, noise, shared, first_trajectory, disturbance=None):
+    """(seed, sigma as N_X C doubles, shared, first_trajectory), the arguments of the _drawn entries and of noise_table, from
+    noise = (seed, sigma): a seed in 0 .. 2^64-1 and sigma [nx], the standard deviation of every state component (a scalar:
+    the same for all), finite and not negative.  Checked here, before any library call."""
+    nx, B = solver.problem.nx, solver.B
+    if disturbance is not None:
+        raise IlqgError("%s: noise and disturbance are both given: the noise is either drawn on the device (noise) or the caller's table "
+                        "(disturbance); noise_table(...) gives the drawn noise as a table to add a term to" % who)
+    if not isinstance(noise, (tuple, list)) or len(noise) != 2:
+        raise IlqgError("%s: noise must be a pair (seed, sigma), not %r" % (who, noise))
+    seed, sigma = noise
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise IlqgError("%s: noise: the seed must be an integer in 0 .. 2^64-1, not %r" % (who, seed))
+    if _is_cuda(sigma):
+        raise IlqgError("%s: noise: sigma is a tensor on the device: sigma is host memory in every form (%d numbers)" % (who, nx))
+    try:
+        a = np.asarray(sigma, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise IlqgError("%s: noise: sigma must be %d real numbers, not %r" % (who, nx, sigma))
+    if a.ndim == 0:
+        a = np.full(nx, float(a))
+    if a.shape != (nx,):
+        raise IlqgError("%s: noise: sigma has shape %s, expected (%d,) = (nx,), or a scalar for every component" % (who, tuple(a.shape), nx))
+    if not np.all(np.isfinite(a) & (a >= 0.0)):
+        raise IlqgError("%s: noise: sigma must be finite and not negative, not %s" % (who, a.tolist()))
+    first = first_trajectory
+    if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or int(first) < 0 or int(first) + B > 2 ** 32:
+        raise IlqgError("%s: first_trajectory must be an integer with 0 <= first_trajectory and first_trajectory + B <= 2^32 (B = %d), not %r"
+                        % (who, B, first))
+    return int(seed), (C.c_double * nx)(*a.tolist()), 1 if shared else 0, int(first)
+
+
+def _policy_rollout(solver, entry, x0, alpha, feedback, trajectories, params, disturbance=None, noise=None, noise_shared=False, first_trajectory=0):
     """BatchSolver.policy_rollout / MultiSolver.policy_rollout in host memory: the checks, the arrays and the one library call.
-    Without a disturbance the entries that have always been there are called with the arguments they have always had; with
-    one, the superset entry `entry`_noise (n_names = 0: no parameter table)."""
+    Without a disturbance and without noise the entries that have always been there are called with the arguments they have
+    always had; with a disturbance the superset entry `entry`_noise, with noise `entry`_drawn (n_names = 0: no parameter table)."""
     x0 = _policy_starts(x0, solver.B, solver.problem.nx)
     R, named = x0.shape[1], ()
     out, ptr = _rollout_outputs(solver, R, trajectories)
+    if noise is not None:
+        drawn = _drawn_noise(solver, "policy_rollout", noise, noise_shared, first_trajectory, disturbance)
+        named = (0, None, None, 0)
     if disturbance is not None:
         dist, dist_shared, keep = _rollout_disturbance(solver, disturbance, R)
         named = (0, None, None, 0)
     if params is not None:
         names, values, shared = _rollout_params(solver, params, R)
         named = (len(names), names, _address(values), shared)
-    if disturbance is not None:
+    if noise is not None:
+        entry, named = entry + "_drawn", named + drawn
+    elif disturbance is not None:
         entry, named = entry + "_noise", named + (dist, dist_shared)
     elif params is not None:
         entry += "_params"
@@ -617,6 +654,13 @@ def load_library(problem="carparking", full_ddp=0, strict=False):
         lib.ilqg_batch_policy_rollout_noise.argtypes = noise
         lib.ilqg_batch_policy_rollout_noise_device.argtypes = noise + [v]
         lib.ilqg_multi_policy_rollout_noise.argtypes = noise
+    if hasattr(lib, "ilqg_batch_policy_rollout_drawn"):  # (and under process noise drawn on the device from a seed)
+        drawn = [v, C.c_int, v, C.c_int, C.POINTER(C.c_char_p), v, C.c_int, C.c_ulonglong, v, C.c_int, C.c_longlong, C.c_double, C.c_int, v, v, v, v, v]
+        lib.ilqg_batch_policy_rollout_drawn.argtypes = drawn
+        lib.ilqg_batch_policy_rollout_drawn_device.argtypes = drawn + [v]
+        lib.ilqg_multi_policy_rollout_drawn.argtypes = drawn
+        lib.ilqg_batch_noise_table.argtypes = [v, C.c_int, C.c_ulonglong, v, C.c_int, C.c_longlong, v]
+        lib.ilqg_batch_noise_table_device.argtypes = [v, C.c_int, C.c_ulonglong, v, C.c_int, C.c_longlong, v, v]
     if hasattr(lib, "ilqg_batch_set_params_batch"):  # (and for problem parameters per trajectory)
         lib.ilqg_batch_set_params_batch.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v]
         lib.ilqg_batch_set_params_batch_device.argtypes = [v, C.c_int, C.POINTER(C.c_char_p), v, v]
@@ -927,7 +971,8 @@ class BatchSolver:
         self._ck(entry(self.h, int(steps), *ptr, stream))
         return out
 
-    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False, params=None, disturbance=None):
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, device=False, params=None, disturbance=None, noise=None,
+                       noise_shared=False, first_trajectory=0):
         """every plan's feedback policy rolled out from R starts per trajectory on the GPU (ilqg_batch_policy_rollout):
         x0 [B,R,nx], or [R,nx] for every trajectory; u_k = u_nom_k [+ alpha l_k if alpha != 0] [+ L_k (x_k - x_nom_k) if
         feedback], clamped, through the problem's dynamics and cost.  The policy is what head(N, gains=True) returns — behind
@@ -946,12 +991,21 @@ class BatchSolver:
         goes on from x_next + disturbance[b, r, k] behind step k = 0 .. N-1 — [B,R,N,nx], or [R,N,nx] for every trajectory
         (common random numbers).  The control of step k+1 is computed at the disturbed state; row N-1 moves x_end, x[N] and the
         state the final cost is evaluated at; ok is 0 too where a disturbed state is not finite.  A numpy array, or with
-        device=True a contiguous float64 torch tensor on the solver's GPU.  None: the call without a table, unchanged."""
+        device=True a contiguous float64 torch tensor on the solver's GPU.  None: the call without a table, unchanged.
+        noise = (seed, sigma): the same push DRAWN ON THE DEVICE (ilqg_batch_policy_rollout_drawn; no table, no memory
+        proportional to R): disturbance[b, r, k, i] = sigma[i] z, z a standard normal of the counter-based generator
+        Philox4x32-10 under the 64-bit seed at the counter (k, r, first_trajectory + b, i // 4) (Box-Muller in double
+        precision, the tail ends at 6.7 sigma).  sigma [nx] or a scalar, host memory in every form.  A draw depends on its
+        counter alone: roll-out (b, r) has the same bits for any R, stream groups and shards, and a batch rolled out in chunks
+        equals the whole with first_trajectory = each chunk's first trajectory.  noise_shared: every trajectory gets the
+        draws of trajectory 0 (common random numbers).  noise_table(R, seed, sigma, ...) is the same noise as a table: given
+        as `disturbance` it yields the same bits.  noise together with disturbance is refused."""
         nx, B, named = self.problem.nx, self.B, ()
         if not device:
             if _is_cuda(x0):
                 raise IlqgError("policy_rollout: x0 is a tensor on the device: pass device=True")
-            return _policy_rollout(self, "ilqg_batch_policy_rollout", x0, alpha, feedback, trajectories, params, disturbance)
+            return _policy_rollout(self, "ilqg_batch_policy_rollout", x0, alpha, feedback, trajectories, params, disturbance, noise, noise_shared,
+                                   first_trajectory)
         if not _is_cuda(x0):
             raise IlqgError("policy_rollout: device=True and x0 is in host memory: pass a float64 torch tensor on the solver's GPU")
         if len(x0.shape) != 3 or int(x0.shape[1]) < 1:
@@ -960,20 +1014,47 @@ class BatchSolver:
         px = _cuda_address(x0, (B, R, nx), self.device, "x0")
         if params is not None:
             names, cols, shared = _rollout_params(self, params, R, self.device)
+        if noise is not None:
+            drawn = _drawn_noise(self, "policy_rollout", noise, noise_shared, first_trajectory, disturbance)
+            named = (0, None, None, 0)
         if disturbance is not None:
             dist, dist_shared, keep_dist = _rollout_disturbance(self, disturbance, R, self.device)
             named = (0, None, None, 0)
-        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_noise_device" if disturbance is not None else
+        entry = _receding_entry(self.lib, "ilqg_batch_policy_rollout_drawn_device" if noise is not None else
+                                "ilqg_batch_policy_rollout_noise_device" if disturbance is not None else
                                 "ilqg_batch_policy_rollout_device" if params is None else "ilqg_batch_policy_rollout_params_device")
         torch, dev, stream = _torch_stream(self.device)
         out, ptr = _rollout_outputs(self, R, trajectories, torch, dev)
         if params is not None:
             values, keep = _tensor_table(torch, dev, cols)
             named = (len(names), names, values, shared)
-        if disturbance is not None:
+        if noise is not None:
+            named = named + drawn
+        elif disturbance is not None:
             named = named + (dist, dist_shared)
         self._ck(entry(self.h, R, px, *named, float(alpha), 1 if feedback else 0, *ptr, stream))
         return out
+
+    def noise_table(self, R, seed, sigma, shared=False, first_trajectory=0, device=False):
+        """the process noise policy_rollout(noise=(seed, sigma), noise_shared=shared, first_trajectory=...) draws for R roll-outs
+        per trajectory, as a table (ilqg_batch_noise_table; k_noise_fill, the same device function): [B,R,N,nx], or with shared
+        [R,N,nx].  policy_rollout(disturbance=table) yields what the drawn call yields, bit for bit; table[:, 0, :rounds*steps]
+        is a disturbance for receding_plant; a caller adds a term of their own to it.  A numpy array, or with device=True a
+        float64 torch tensor on the solver's GPU, written in the order of torch's current stream without a host wait
+        (ilqg_batch_noise_table_device).  Nothing in the batch changes."""
+        if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or R < 1:
+            raise IlqgError("noise_table: R must be an integer >= 1 (roll-outs per trajectory), not %r" % (R,))
+        drawn = _drawn_noise(self, "noise_table", (seed, sigma), shared, first_trajectory)
+        shape = ((int(R), self.N, self.problem.nx) if shared else (self.B, int(R), self.N, self.problem.nx))
+        if not device:
+            w = np.zeros(shape)
+            self._ck(_receding_entry(self.lib, "ilqg_batch_noise_table")(self.h, int(R), *drawn, _address(w)))
+            return w
+        entry = _receding_entry(self.lib, "ilqg_batch_noise_table_device")
+        torch, dev, stream = _torch_stream(self.device)
+        w = torch.empty(shape, dtype=torch.float64, device=dev)
+        self._ck(entry(self.h, int(R), *drawn, C.c_void_p(w.data_ptr() or None), stream))
+        return w
 
     def shift_param(self, name, steps, tail=None):
         """the window of ONE per-time-step parameter moves `steps` values on (ilqg_batch_shift_param): p'[k] = p[k+steps],
@@ -1359,11 +1440,14 @@ class MultiSolver:
         self._ck(_receding_entry(self.lib, "ilqg_multi_head")(self.h, int(steps), *ptr))
         return out
 
-    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, params=None, disturbance=None):
+    def policy_rollout(self, x0, alpha=1.0, feedback=True, trajectories=False, params=None, disturbance=None, noise=None, noise_shared=False,
+                       first_trajectory=0):
         """BatchSolver.policy_rollout of every shard (ilqg_multi_policy_rollout, with params ilqg_multi_policy_rollout_params,
-        with a disturbance ilqg_multi_policy_rollout_noise: a [B,R,N,nx] table sharded by rows, a [R,N,nx] one given to every shard),
+        with a disturbance ilqg_multi_policy_rollout_noise: a [B,R,N,nx] table sharded by rows, a [R,N,nx] one given to every shard;
+        with noise = (seed, sigma) ilqg_multi_policy_rollout_drawn: every shard draws under its own first trajectory, the bits of the single batch),
         numpy arrays"""
-        return _policy_rollout(self, "ilqg_multi_policy_rollout", x0, alpha, feedback, trajectories, params, disturbance)
+        return _policy_rollout(self, "ilqg_multi_policy_rollout", x0, alpha, feedback, trajectories, params, disturbance, noise, noise_shared,
+                               first_trajectory)
 
     def receding_plant(self, rounds, steps, iterations, feedback=True, x_plant=None, params=None, disturbance=None, windows=None):
         """BatchSolver.receding_plant of every shard, one shard after the other (ilqg_multi_receding_plant, with windows

@@ -312,6 +312,33 @@ int ilqg_batch_policy_rollout_noise(ilqg_batch_t *c, int n_starts, const double 
 int ilqg_batch_policy_rollout_noise_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
                                            const double *values, int shared, const double *disturbance, int disturbance_shared, double alpha,
                                            int feedback, double *cost, int *ok, double *x_end, double *x, double *u, void *stream);
+/* THE SAME ROLL-OUTS WITH THE PROCESS NOISE DRAWN ON THE DEVICE FROM A SEED: no table, no upload, no memory proportional to
+ * n_starts.  The arguments of the _noise forms with `disturbance, disturbance_shared` replaced by
+ *     seed, sigma, noise_shared, first_trajectory
+ * and w[b][r][k][i] = sigma[i] z[b][r][k][i], added by the rule above.  z: standard normals from the counter-based generator
+ * Philox4x32-10 (Random123) under the key (seed & 0xffffffff, seed >> 32) at the counter (k, r, t, i / 4), t the GLOBAL
+ * trajectory index first_trajectory + b — with noise_shared != 0 t = 0: every trajectory gets the draws of trajectory 0,
+ * common random numbers —, turned into normals by Box-Muller in double precision (two words a pair; the tail ends at 6.7
+ * sigma); each w is rounded to double before it is added.  A draw depends on its counter alone, so roll-out (b, r) has the
+ * same bits whatever n_starts, the stream groups, the shards (ilqg_multi_* passes each shard its own first trajectory) or a
+ * caller who rolls a large batch out in chunks with first_trajectory = the chunk's first trajectory.
+ * ilqg_batch_noise_table writes the same draws as a table, w [B][n_starts][n_hor][N_X] or with noise_shared
+ * [n_starts][n_hor][N_X]: given to the _noise forms as `disturbance` it yields what the _drawn forms yield, bit for bit in
+ * every output; it is also the table for ilqg_batch_receding_plant, for inspection, or for a caller who adds a term of their own.
+ * sigma: N_X doubles in HOST memory in every form.  Refused before anything is launched or changed, the argument named: sigma
+ * NULL, a sigma entry negative or not finite, first_trajectory < 0, first_trajectory + B > 2^32, what the _noise forms refuse
+ * of n_starts, x0 and the names, and host memory in the device forms (x0, values, the outputs, w). */
+int ilqg_batch_policy_rollout_drawn(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory,
+                                    double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
+int ilqg_batch_policy_rollout_drawn_device(ilqg_batch_t *c, int n_starts, const double *x0, int n_names, const char *const *names,
+                                           const double *values, int shared, unsigned long long seed, const double *sigma, int noise_shared,
+                                           long long first_trajectory, double alpha, int feedback, double *cost, int *ok, double *x_end,
+                                           double *x, double *u, void *stream);
+int ilqg_batch_noise_table(ilqg_batch_t *c, int n_starts, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory,
+                           double *w);
+int ilqg_batch_noise_table_device(ilqg_batch_t *c, int n_starts, unsigned long long seed, const double *sigma, int noise_shared,
+                                  long long first_trajectory, double *w, void *stream);
 /* THE CLOSED LOOP OF PLANNER AND PLANT, resident on the device for `rounds` control intervals — ilqg_batch_receding with a
  * plant that has a state of its own, may differ from the model and may be disturbed: what closed-loop cost the controllers
  * reach when the wheelbase is 5 % off and the state is pushed at every step.  Each of the `rounds` rounds is
@@ -625,6 +652,11 @@ int ilqg_multi_policy_rollout_params(ilqg_multi_t *m, int n_starts, const double
 int ilqg_multi_policy_rollout_noise(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
                                     int shared, const double *disturbance, int disturbance_shared, double alpha, int feedback, double *cost,
                                     int *ok, double *x_end, double *x, double *u);
+/* ilqg_batch_policy_rollout_drawn per shard (host memory): shard g draws under first_trajectory + its own first trajectory,
+ * so the bits are those of the single batch */
+int ilqg_multi_policy_rollout_drawn(ilqg_multi_t *m, int n_starts, const double *x0, int n_names, const char *const *names, const double *values,
+                                    int shared, unsigned long long seed, const double *sigma, int noise_shared, long long first_trajectory,
+                                    double alpha, int feedback, double *cost, int *ok, double *x_end, double *x, double *u);
 /* ilqg_batch_receding_plant per shard, one shard after the other (host memory): every [B]... array is offset by the shard's first trajectory */
 int ilqg_multi_receding_plant(ilqg_multi_t *m, int rounds, int steps, int iterations, int feedback, double *x_plant, int n_names,
                               const char *const *names, const double *values, const double *disturbance, double *x_applied, double *u_applied,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Roll-outs of the policy from perturbed starts (BatchSolver.policy_rollout, k_policy) against the line search's roll-outs.
 
-    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search] [--params] [--noise]
+    python tools/policy_profile.py [--config headline|config5|both] [--repeats 10] [--warmup 3] [--rs 1,8,64] [--scalar-search] [--params] [--noise] [--drawn]
 
 One process per invocation, one stream group (a launch's HIP-event time is then that launch alone).  The yardstick is the
 line search of the SAME run with ls_keep = 0, ls_split = 0: k_rollout[search] rolls out (active trajectories) x n_alpha
@@ -22,6 +22,12 @@ to the same alternation: R = 8, costs only, device form, with a table per roll-o
 GPU) and with one [R, N, nx] table shared by every trajectory, each as a ratio to the plain k_policy launch at R = 8 of the
 same run (the leg "device R=8").  That plain launch is also what a build of the parent commit is compared with — the same
 tool run there, alternating with this one: a null table is meant to cost nothing measurable.
+
+--drawn (implies --noise) adds the roll-outs whose noise is drawn on the device (policy_rollout(noise=(seed, sigma)),
+k_policy_drawn, a timing slot of its own) to the same alternation, costs only, device form: R = 8 with noise per trajectory and
+with shared noise, as ratios to the plain launch, to the launch under a table per roll-out and to the launch under the shared
+table of the same run; and R = 64, drawn only, with the size of the table it does without.  noise_table (k_noise_fill) at R = 8
+is timed too.  No bar is set on these ratios: they are findings.
 """
 import argparse
 import os
@@ -39,7 +45,7 @@ def spread(v, unit="ms"):
     return "median %10.4f %s  min %10.4f  max %10.4f  (n = %d)" % (np.median(v), unit, v.min(), v.max(), len(v))
 
 
-def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=False, with_noise=False):
+def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=False, with_noise=False, with_drawn=False):
     import torch
     if scalar_search:  # (read once, when the context is made)
         os.environ["ILQG_NO_ROLLOUT_PARTS"] = "1"
@@ -61,9 +67,9 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
     s.sync()
     rng = np.random.default_rng(3)
     plan_x0 = s.head(1)["x"][:, 0]
-    rmax = max(rs + [8])
+    rmax = max(rs + [8] + ([64] if with_drawn else []))
     starts = torch.from_numpy(plan_x0[:, None, :] + 0.1 * rng.standard_normal((B, rmax, nx))).cuda()
-    dev_starts = {R: starts[:, :R].contiguous() for R in set(rs + [8])}
+    dev_starts = {R: starts[:, :R].contiguous() for R in set(rs + [8] + ([64] if with_drawn else []))}
     host8 = dev_starts[8].cpu().numpy()
 
     def sync():
@@ -105,8 +111,23 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
         legs += [(name, 8) for name in noise]
         print("   --noise: a table per roll-out of %.2f GB, a shared one of %.1f KB" % (B * 8 * N * nx * 8 / 1e9, 8 * N * nx * 8 / 1e3), flush=True)
 
+    drawn = {}
+    if with_drawn:
+        sigma = np.full(nx, 0.01)
+        drawn = {"drawn R=8": (8, False), "drawn shared R=8": (8, True), "drawn R=64": (64, False), "fill R=8": (8, False)}
+        legs += [(name, R) for name, (R, _) in drawn.items()]
+        print("   --drawn: seed 20261021, sigma 0.01; at R = 64 a table per roll-out would be %.1f GB" % (B * 64 * N * nx * 8 / 1e9), flush=True)
+
+    def slot(name):
+        return ("k_rollout[search]" if name == "search" else "k_policy_params" if name in tables else "k_noise_fill" if name.startswith("fill")
+                else "k_policy_drawn" if name in drawn else "k_policy")
+
     def leg(name, R):
-        if name in noise:
+        if name.startswith("fill"):
+            s.noise_table(R, 20261021, sigma, device=True)
+        elif name in drawn:
+            s.policy_rollout(dev_starts[R], device=True, noise=(20261021, sigma), noise_shared=drawn[name][1])
+        elif name in noise:
             s.policy_rollout(dev_starts[R], device=True, disturbance=noise[name])
         elif name in tables:
             s.policy_rollout(dev_starts[R], device=True, params=tables[name])
@@ -132,7 +153,7 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
     n_alpha = 8  # standard_parameters (iLQG.c:74): no option of this run changes the list of step sizes
     for r in range(repeats):
         for name, R in legs:
-            which = "k_rollout[search]" if name == "search" else "k_policy_params" if name in tables else "k_policy"
+            which = slot(name)
             active = s.active() if name == "search" else B
             sync()
             n0, ms0 = kernel(which)
@@ -151,7 +172,7 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
     s.timing(False)
     print("the searches rolled out %d .. %d active trajectories x %d step sizes" % (min(actives), max(actives), n_alpha))
     for name, R in legs:
-        which = "k_rollout[search]" if name == "search" else "k_policy_params" if name in tables else "k_policy"
+        which = slot(name)
         print("%-12s %-18s per launch   %s" % (name, which, spread(kern[name])))
         print("%-12s %-18s per roll-out %s" % ("", "", spread(per[name], "ns")))
     base = np.median(per["search"])
@@ -171,6 +192,19 @@ def run(ilqg, synth, config, repeats, warmup, rs, scalar_search, with_params=Fal
         m, p0 = np.median(kern[name]), np.median(kern["device R=8"])
         print("ratio per launch, k_policy %-16s / k_policy device R=8 (no table): %.3f  (medians; its repeats span %.3f .. %.3f of its median, the plain launch's %.3f .. %.3f of its)" % (
             name, m / p0, np.min(kern[name]) / m, np.max(kern[name]) / m, np.min(kern["device R=8"]) / p0, np.max(kern["device R=8"]) / p0))
+    if with_drawn:
+        def ratio(a, b, what):
+            m, p0 = np.median(kern[a]), np.median(kern[b])
+            print("ratio per launch, %-44s %.3f  (medians; its repeats span %.3f .. %.3f of its median, the other's %.3f .. %.3f of its)" % (
+                what + ":", m / p0, np.min(kern[a]) / m, np.max(kern[a]) / m, np.min(kern[b]) / p0, np.max(kern[b]) / p0))
+        ratio("drawn R=8", "device R=8", "drawn / plain, R = 8")
+        ratio("drawn R=8", "noise full R=8", "drawn / table per roll-out, R = 8")
+        ratio("drawn shared R=8", "noise shared R=8", "drawn shared / shared table, R = 8")
+        if 64 in rs:
+            ratio("drawn R=64", "costs R=64", "drawn / plain, R = 64")
+        print("drawn R=64: %.4f ms per launch (median), %.2f ns per roll-out; the table it does without: %.1f GB" % (
+            np.median(kern["drawn R=64"]), np.median(per["drawn R=64"]), B * 64 * N * nx * 8 / 1e9))
+        print("noise_table R=8 (k_noise_fill, %.2f GB written): %.4f ms per launch (median)" % (B * 8 * N * nx * 8 / 1e9, np.median(kern["fill R=8"])))
     if with_params:
         print("ratio per launch, shared [R, W] table / per-trajectory [B, R, W] table at R = 8, all parameters named: %.3f" % (
             np.median(kern["shared R=8"]) / np.median(kern["all R=8"])))
@@ -194,12 +228,14 @@ def main():
                     "parameters named, a single one named, and a shared against a per-trajectory table at R = 8")
     ap.add_argument("--noise", action="store_true", help="also the roll-outs under a disturbance table at R = 8, costs only: a table per roll-out "
                     "and one shared by every trajectory, as ratios to the plain launch of the same run")
+    ap.add_argument("--drawn", action="store_true", help="also the roll-outs whose noise is drawn on the device (k_policy_drawn) at R = 8 and "
+                    "R = 64, costs only, as ratios to the plain launch and to the launches under a table (implies --noise)")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.load_package()
     from ddp_generator_amd import ilqg, synth
     for config in (("headline", "config5") if a.config == "both" else (a.config,)):
-        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search, a.params, a.noise)
+        run(ilqg, synth, config, a.repeats, a.warmup, [int(r) for r in a.rs.split(",")], a.scalar_search, a.params, a.noise or a.drawn, a.drawn)
 
 
 if __name__ == "__main__":
